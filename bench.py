@@ -1,12 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- measures the hot path on MI355X.  Contract: see the repo task statement.
 
-  python bench.py --gpus N --steps K --warmup W [--workload all|train|iou3d|infer]
+  python bench.py --gpus N --steps K --warmup W [--workload all|train|iou3d|infer] [--full] [--dump-outputs DIR]
 
-Prints ONE JSON line on rank 0.  BASELINE.json's metric has two halves, and the default workload (`all`) measures both in one
-line: the top-level fields are images/sec of the cubercnn_DLA34_FPN training step (batch 4/GPU, synthetic 512x512 Omni3D-shaped
-inputs, configs[1] / configs[2]), the `iou3d` object is configs[4] (100k dt x gt box pairs per GPU through box3d_overlap) with
-its own roofline and CPU baseline.
+Prints ONE JSON line on rank 0.  The top-level fields are images/sec of the cubercnn_DLA34_FPN training step (batch 4/GPU,
+synthetic 512x512 Omni3D-shaped inputs, configs[1] / configs[2]); `ms_per_step` is one timed step.  A plain run sets up, warms up,
+times exactly K steps and prints the line.  `--full` adds everything else the benchmark measures: five windows of K steps (the
+median is the value), the second half of BASELINE.json's metric (the `iou3d` object, configs[4]: 100k dt x gt box pairs per GPU
+through box3d_overlap, with its own roofline and CPU baseline), the roofline and per-kernel tables, the CPU baselines, the drop-in
+loop and the side legs (inference, ResNet34, bf16 split); the whole record goes to bench_detail.json.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32, < 64 MB; inputs are seeded).
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself, one process per GPU, the way the
 reference's script does (tools/train_net.py:500-510 `launch(main, args.num_gpus, ...)`): bench.py re-executes itself under
@@ -199,7 +202,9 @@ def run_iou3d(args, world, rank):
                              "SQ_ACTIVE_INST_VALU x 4 / (GRBM_GUI_ACTIVE / 8 x 1024 SIMDs) from the committed PMC pass in `valu`",
                      "valu": pmc},
     }
-    if rank == 0:       # the CPU leg is reported at N = 1 only (the other ranks would wait on it)
+    if args.dump_outputs and rank == 0:
+        res["_outputs"] = {"iou3d_pair_iou": out.float().cpu().numpy()}
+    if rank == 0 and args.full:       # the CPU leg is reported at N = 1 only (the other ranks would wait on it)
         try:
             res["cpu_baseline"] = cpu_baseline_iou3d(dt, gt) if world == 1 else {"value": None, "unit": "pairs/s", "cores": 0, "kind": "port",
                                                                                    "sample": "reported at N=1 only"}
@@ -271,7 +276,7 @@ def extra_leg(argv, env):
     import subprocess
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "dtype", "scaling", "config")
     try:
-        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1"] + argv, env=dict(os.environ, **env), capture_output=True,
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full"] + argv, env=dict(os.environ, **env), capture_output=True,
                              text=True, timeout=600)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
         r = json.loads(line)
@@ -298,6 +303,20 @@ def write_detail(res):
         except OSError as e:
             err = f"{type(e).__name__}: {e}"
     return {"file": None, "error": err[:120]}
+
+
+DUMP_CAP = 64 << 20      # bytes of all arrays written by --dump-outputs
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: one float32 / float64 DIR/<name>.npy per array the timed path handed back"""
+    assert arrays, "--dump-outputs: this workload returned no outputs"
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_CAP, f"--dump-outputs: {total} bytes over the {DUMP_CAP}-byte cap"
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def _r(x, nd=4):
@@ -410,6 +429,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=None, choices=[None, "all", "train", "iou3d", "infer"])
+    ap.add_argument("--full", action="store_true", help="also the side measurements (iou3d, rooflines, CPU baselines, drop-in loop, "
+                                                        "side legs, five timing windows) and bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -425,10 +447,11 @@ def main():
     else:
         from omni3d_amd.bench_train import run_train
         res = run_train(args, world, rank)
-        if workload == "all":
+        if workload == "all" and args.full:
             # second half of BASELINE.json's metric ("...; IoU3D boxes/sec", configs[4]) in the same driver-run line
             io = run_iou3d(args, world, rank)
             if rank == 0:
+                res.setdefault("_outputs", {}).update(io.get("_outputs") or {})
                 res["iou3d"] = {k: io[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "scaling", "dtype",
                                                    "config", "roofline", "cpu_baseline")}
             if world == 1 and DEVICE == "cuda" and os.environ.get("OMNI_BENCH_SKIP_EXTRA") != "1":
@@ -448,12 +471,15 @@ def main():
                                              "OMNI_BENCH_SKIP_ROOFLINE": "1", "OMNI_BENCH_SKIP_DROPIN": "1"})
     observe_ranks(world, local, info)
     if rank == 0:
+        outputs = res.pop("_outputs", None)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs or {})
         res["n_gpus"] = world
         res["launch"] = info
         if DEVICE != "cuda" or (world > 1 and not info.get("one_gpu_per_rank")):
             res["functional_check_only"] = ("ranks share a device or run host-compiled kernels: this line checks the N-rank code path, "
                                             "its numbers are not measurements of the product")
-        print(json.dumps(compact_line(res, write_detail(res))))
+        print(json.dumps(compact_line(res, write_detail(res) if args.full else None)))
     if world > 1:
         dist.barrier()      # rank 0 times the roofline kernels after the step loop: leave together
         dist.destroy_process_group()

@@ -81,7 +81,10 @@ def run_train(args, world, rank):
     guard = StepGuard(LOSS_NAMES, cfg.MODEL.STABILIZE, cfg.SOLVER.CHECKPOINT_PERIOD, DEVICE)
     opt.skip_flag = guard.skip
 
+    last = {}
+
     def finish(losses, total):
+        last["losses"], last["total"] = losses, total      # what the caller of the step receives (--dump-outputs)
         # (the step's own record lives in the guard: guard.out = [skipped, retry, total loss, 10 losses] of the last step, guard.state[2]
         # = steps skipped so far -- read once before / after the timed windows instead of two copy launches per step)
         opt.check_nonfinite(guard.nonfinite_flag)
@@ -150,10 +153,10 @@ def run_train(args, world, rank):
 
     step = graph_step if graphed is not None else eager_step
 
-    # executed (Winograd-aware) flops of one step: count the multiply-adds of every MFMA launch during one eager step
+    # executed (Winograd-aware) flops of one step: count the multiply-adds of every MFMA launch during one eager step (--full only)
     from omni3d_amd.profile_io import ExecutedFlops
-    executed_flops = 0.0
-    if DEVICE == "cuda":
+    executed_flops = None
+    if DEVICE == "cuda" and args.full:
         with ExecutedFlops() as counter:
             eager_step()
         executed_flops = counter.flops
@@ -162,7 +165,7 @@ def run_train(args, world, rank):
     # the power / clock state of sustained training, not the first 0.3 s after idle (fixed count: every rank issues the same collectives)
     n_cond = int(os.environ.get("OMNI_BENCH_CONDITION_STEPS", "150" if DEVICE == "cuda" else "0"))
     from omni3d_amd.profile_io import GpuState
-    gpu = GpuState(torch.cuda.current_device()) if DEVICE == "cuda" else None
+    gpu = GpuState(torch.cuda.current_device()) if DEVICE == "cuda" and args.full else None
     state = {"idle": gpu.sample() if gpu else None}
     for i in range(n_cond):
         step()
@@ -172,8 +175,9 @@ def run_train(args, world, rank):
         step()
     # WINDOWS back-to-back windows of exactly `--steps` steps, each bracketed by synchronize + barrier on both sides and reduced with
     # MAX over the ranks; the line's `ms_per_step` / `value` are the MEDIAN window (min / max beside it).  Between the enqueue of a
-    # window and its synchronize the device is still busy: that is when clocks / power / temperature are read.
-    n_win = max(1, int(os.environ.get("OMNI_BENCH_WINDOWS", "5")))
+    # window and its synchronize the device is still busy: that is when clocks / power / temperature are read.  A plain run times
+    # one window (exactly `--steps` steps); --full times five.
+    n_win = max(1, int(os.environ.get("OMNI_BENCH_WINDOWS", "5" if args.full else "1")))
     windows, enqueue, under_load = [], [], []
     state0 = guard.state.clone()
     first_out = None
@@ -207,10 +211,11 @@ def run_train(args, world, rank):
     state["under_load_all_windows"] = under_load
     state["neighbours"] = gpu.neighbours() if gpu else None
     state["pci_address"] = gpu.address if gpu else None
+    outputs = train_outputs(last["losses"], last["total"], opt) if args.dump_outputs and rank == 0 else None
     # one more window of the same length WITH the per-stage device timestamps (end of every critical-path graph M_k and of every
     # weight-gradient graph W_k after the step's first launch): never part of the measured windows
     stage_ends = None
-    if DEVICE == "cuda" and getattr(graphed, "stages", None) and os.environ.get("OMNI_BENCH_SKIP_STAGE_ENDS") != "1":
+    if DEVICE == "cuda" and args.full and getattr(graphed, "stages", None) and os.environ.get("OMNI_BENCH_SKIP_STAGE_ENDS") != "1":
         from omni3d_amd.cubercnn.solver import graphed as _gm
         was = _gm._PIPE_TIMING
         _gm.set_pipe_timing(True)
@@ -253,16 +258,16 @@ def run_train(args, world, rank):
                     "median": 1e3 * dt / args.steps, "max": 1e3 * max(windows) / args.steps,
                     "value_is": f"median of {n_win} back-to-back windows of {args.steps} steps, each bracketed by synchronize + barrier, MAX over ranks",
                     "conditioning_steps_before_warmup": n_cond},
-        "gpu_state": state,
+        "gpu_state": state if gpu else None,
         "stage_ends": stage_ends,
         "launch_mode": graph_note,
         "step_mfma_frac": step_tf / FP32_MFMA_PEAK_TF,
         "step_algorithmic_tflops_per_gpu": step_tf,
         # the flops the MFMA kernels really execute (Winograd layers at the size of their point GEMMs: 2.25x / 4x fewer than the
         # direct-convolution count above) -- this, not the algorithmic figure, is the hardware's MFMA utilisation over the whole step
-        "step_executed_gflop": executed_flops / 1e9,
-        "step_executed_tflops_per_gpu": executed_flops * args.steps / dt / 1e12,
-        "step_executed_mfma_frac": executed_flops * args.steps / dt / 1e12 / FP32_MFMA_PEAK_TF,
+        "step_executed_gflop": None if executed_flops is None else executed_flops / 1e9,
+        "step_executed_tflops_per_gpu": None if executed_flops is None else executed_flops * args.steps / dt / 1e12,
+        "step_executed_mfma_frac": None if executed_flops is None else executed_flops * args.steps / dt / 1e12 / FP32_MFMA_PEAK_TF,
         "loss_first_last": [final_losses[0], final_losses[-1]],
         "skipped_steps": skipped_steps,
         "guard": "rolling-loss divergence test + NaN/Inf gradient scan + retry decision on the device, one 12-float all-reduce/step",
@@ -272,7 +277,9 @@ def run_train(args, world, rank):
     if NONSTANDARD:
         res["nonstandard"] = {"ims_per_gpu": IMS_PER_GPU, "image_size": IMAGE_SIZE, "overrides": OVERRIDES, "device": DEVICE,
                               "note": "not BASELINE.json's configuration: functional check only"}
-    if rank == 0 and DEVICE != "cuda":
+    if outputs is not None:
+        res["_outputs"] = outputs
+    if rank == 0 and (DEVICE != "cuda" or not args.full):      # a plain run: the step time only
         res["roofline"], res["cpu_baseline"] = None, None
     elif rank == 0 and os.environ.get("OMNI_BENCH_SKIP_ROOFLINE") == "1":      # A/B sweeps: the step time only
         res["roofline"], res["cpu_baseline"] = None, None
@@ -319,6 +326,29 @@ def run_train(args, world, rank):
         else:
             res["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": 0, "kind": "port", "sample": "reported at N=1 only"}
     return res
+
+
+DUMP_SAMPLE = 6 << 20      # elements kept of a flat parameter / gradient vector by --dump-outputs (24 MiB each in float32)
+
+
+def fixed_sample(flat, k=DUMP_SAMPLE, seed=0):
+    """the whole vector when it is short, else the same seeded, sorted choice of k of its elements on every run -> float32 numpy"""
+    n = flat.numel()
+    if n <= k:
+        return flat.detach().float().cpu().numpy()
+    import numpy as np
+    idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    return flat.detach()[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+
+
+def train_outputs(losses, total, opt):
+    """what the last timed step handed its caller: the 10 losses and their sum, the gradient it computed and the parameters after its
+    update (fixed seeded samples of the flat vectors) -> {name: float32 numpy array}"""
+    out = {"loss_" + k.replace("/", "_"): losses[k].detach().float().reshape(1).cpu().numpy() for k in sorted(losses)}
+    out["total_loss"] = total.detach().float().reshape(1).cpu().numpy()
+    out["grads"] = fixed_sample(opt.flat_grad)
+    out["params"] = fixed_sample(opt.flat_param)
+    return out
 
 
 def dropin_loop(iters=30, sync_every=1):
@@ -532,7 +562,19 @@ def run_infer(args, world, rank):
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"cubercnn_{MODEL_NAME} inference, batch 4/GPU, synthetic Omni3D 512x512, random-init weights "
                                    "(score threshold 0.01 keeps ~all 100 detections/image)",
-                       "detections_first_image": int(len(out[0]["instances"]))}}
+                       "detections_first_image": int(len(out[0]["instances"]))},
+            "_outputs": infer_outputs(out) if args.dump_outputs and rank == 0 else None}
+
+
+def infer_outputs(out):
+    """every field of every image's detections of the last timed pass -> {"infer_img<n>_<field>": float32 numpy array}"""
+    res = {}
+    for n, o in enumerate(out):
+        for k, v in o["instances"].get_fields().items():
+            t = getattr(v, "tensor", v)
+            if torch.is_tensor(t):
+                res[f"infer_img{n}_{k}"] = t.detach().float().cpu().numpy()
+    return res
 
 
 def _time_launch(fn, iters):

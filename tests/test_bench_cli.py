@@ -30,7 +30,7 @@ def _run(args, extra_env):
 
 def test_bench_starts_its_own_ranks(emu_lib, tmp_path):
     import hashlib
-    res = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"],
+    res = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                {"OMNI_BENCH_IMS": "1", "OMNI_BENCH_SIZE": "64", "OMNI_BENCH_OVERRIDES": TINY, "OMNI_BENCH_WINDOWS": "3",
                 "OMNI_BENCH_DETAIL_DIR": str(tmp_path)})
     assert res["n_gpus"] == 2 and res["steps"] == 2 and res["warmup"] == 1
@@ -55,6 +55,26 @@ def test_bench_starts_its_own_ranks(emu_lib, tmp_path):
     full = json.loads(text)
     assert len(full["launch"]["devices"]) == 2 and full["iou3d"]["config"]["pairs_per_gpu"] == 256 and full["iou3d"]["n_gpus"] == 2
     assert full["ms_per_step"] == w["median"] or abs(full["ms_per_step"] - w["median"]) < 1e-3 * w["median"]
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_one(emu_lib, tmp_path):
+    """without --full: one window of exactly --steps steps, none of the side measurements, no detail file; --dump-outputs writes
+    the last timed step's losses, gradient and parameters as float32 .npy files"""
+    import numpy as np
+    dump = tmp_path / "out"
+    res = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)],
+               {"OMNI_BENCH_IMS": "1", "OMNI_BENCH_SIZE": "64", "OMNI_BENCH_OVERRIDES": TINY, "OMNI_BENCH_DETAIL_DIR": str(tmp_path)})
+    assert res["n_gpus"] == 1 and res["steps"] == 3 and res["warmup"] == 1 and res["unit"] == "images/s" and res["dtype"] == "f32"
+    assert res["windows"]["ms_per_step"] == [res["ms_per_step"]] and abs(res["value"] - 1e3 / res["ms_per_step"]) < 1e-3 * res["value"]
+    assert "iou3d" not in res and res["roofline"] is None and res["cpu_baseline"] is None and res["detail"] is None
+    assert not (tmp_path / "bench_detail.json").exists()
+    files = {f.name: np.load(f) for f in dump.iterdir()}
+    assert {"total_loss.npy", "grads.npy", "params.npy", "loss_rpn_cls.npy"} <= set(files) and len(files) == 13
+    assert all(a.dtype == np.float32 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    losses = [float(a[0]) for k, a in files.items() if k.startswith("loss_")]
+    assert abs(sum(losses) - float(files["total_loss.npy"][0])) <= 1e-4 * max(1.0, abs(sum(losses)))
+    assert abs(float(files["total_loss.npy"][0]) - res["loss_first_last"][1]) <= 1e-5 * max(1.0, abs(res["loss_first_last"][1]))
+    assert np.isfinite(files["params.npy"]).all() and np.abs(files["grads.npy"]).max() > 0
 
 
 def test_line_cap_holds_for_the_full_size_detail():

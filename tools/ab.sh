@@ -6,7 +6,7 @@ REPO=$(pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp
 for rep in 1 2; do
 for v in "$@"; do
   if [ "$v" = "-" ]; then e=""; else e="$v"; fi
-  r=$(env $e OMNI_BENCH_CONDITION_STEPS=50 OMNI_BENCH_SKIP_STAGE_ENDS=1 OMNI_PIPE_TIMING=1 OMNI_BENCH_SKIP_CPU=1 OMNI_BENCH_SKIP_ROOFLINE=1 timeout 300 python bench.py --workload train --steps 30 --warmup 5 2>&1 | grep -E "pipe timing|images/sec")
+  r=$(env $e OMNI_BENCH_CONDITION_STEPS=50 OMNI_BENCH_SKIP_STAGE_ENDS=1 OMNI_PIPE_TIMING=1 OMNI_BENCH_SKIP_CPU=1 OMNI_BENCH_SKIP_ROOFLINE=1 timeout 300 python bench.py --full --workload train --steps 30 --warmup 5 2>&1 | grep -E "pipe timing|images/sec")
   echo "[$v] $(echo "$r" | grep -o 'M0 end [0-9.]* ms') $(echo "$r" | grep -o '"ms_per_step": [0-9.]*')"
 done
 done

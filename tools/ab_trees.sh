@@ -5,7 +5,7 @@
 set -u
 OTHER=${1:-_old}; REPS=${2:-2}; HERE=$(pwd)
 run() { (cd $1 && OMNI_BENCH_CONDITION_STEPS=50 OMNI_BENCH_SKIP_STAGE_ENDS=1 OMNI_PIPE_TIMING=1 OMNI_BENCH_SKIP_CPU=1 OMNI_BENCH_SKIP_ROOFLINE=1 \
-        timeout 300 python bench.py --workload train --steps 30 --warmup 5 2>&1 | grep -E "pipe timing|images/sec" \
+        timeout 300 python bench.py --full --workload train --steps 30 --warmup 5 2>&1 | grep -E "pipe timing|images/sec" \
         | python -c "
 import sys, re, json
 t = sys.stdin.read()
