@@ -580,6 +580,27 @@ int omni_adam_step(float* param, const float* grad, float* exp_avg, float* exp_a
                    float beta1, float beta2, float eps, float weight_decay, int decoupled, const float* step, float grad_scale,
                    const float* skip_flag, void* stream);
 int omni_adam_tick(float* step, const float* skip_flag, void* stream);
+/* SOLVER.CLIP_GRADIENTS: detectron2's maybe_add_gradient_clipping, which cubercnn/solver/build.py:68 applies last -- inside
+ * optimizer.step() (tools/train_net.py:250) torch.nn.utils.clip_grad_norm_ / clip_grad_value_ on EACH parameter on its own, ~230
+ * per-tensor calls -- over the flat gradient bucket.  tiles (ntiles x 3 long long) = [parameter index, first bucket element,
+ * element count], sorted by first element, covering exactly every parameter's own elements (no padding); ptab (nparams x 2 long
+ * long) = [first tile, tile count] of each parameter.  Pointers are bucket BASES; the tiles address into them.
+ *  omni_clip_norm_partials: partial[t] = sum |g|^p over tile t (max |g| for norm_type = inf), one workgroup per tile.
+ *  omni_clip_norm_coef: norm[k] = grad_scale * (parameter k's partials summed in tile order)^(1/p), coef[k] = min(max_norm /
+ *    (norm[k] + 1e-6), 1).  NaN propagates into norm and coef (also for inf); grad_scale as in omni_sgd_step.  No atomics.
+ *  omni_sgd_step_clipped / omni_adam_step_clipped: omni_sgd_step / omni_adam_step over the tiles [t0, t1) of one group's range,
+ *    the gradient read as g * grad_scale * coef[k] (clip_mode 1 = norm) or clamp(g * grad_scale, -clip_value, clip_value)
+ *    (clip_mode 2 = value, NaN stays NaN) before weight decay / momentum / moments.  The clipped gradient is not written back. */
+int omni_clip_norm_partials(const float* grad, const long long* tiles, int ntiles, float norm_type, double* partial, void* stream);
+int omni_clip_norm_coef(const double* partial, const long long* ptab, int nparams, float norm_type, float max_norm, float grad_scale,
+                        float* norm, float* coef, void* stream);
+int omni_sgd_step_clipped(float* param, const float* grad, float* momentum_buf, const long long* tiles, int t0, int t1, int clip_mode,
+                          const float* coef, float clip_value, float lr, float momentum, float dampening, float weight_decay,
+                          int nesterov, int first_step, float grad_scale, const float* skip_flag, void* stream);
+int omni_adam_step_clipped(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                           const long long* tiles, int t0, int t1, int clip_mode, const float* coef, float clip_value, float lr,
+                           float beta1, float beta2, float eps, float weight_decay, int decoupled, const float* step,
+                           float grad_scale, const float* skip_flag, void* stream);
 /* The loop's divergence guard (tools/train_net.py:157-285: allreduce_dict :186, rolling-loss test :194-215, skip / step
  * :245-253, retry decision :258-270) around ONE small all-reduce.  vec (n + 2): [n loss scalars | sum | non-finite-gradient flag];
  * omni_guard_pre writes the sum, the caller all-reduces vec over the ranks (sum), omni_guard_post averages by `world`, updates

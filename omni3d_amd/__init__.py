@@ -70,6 +70,7 @@ def install():
     table = {
         "detectron2.config": pkg + ".d2.config", "detectron2.layers": pkg + ".d2.layers",
         "detectron2.structures": pkg + ".d2.structures", "detectron2.solver": pkg + ".d2.solver",
+        "detectron2.solver.build": pkg + ".d2.solver",       # maybe_add_gradient_clipping (cubercnn/solver/build.py:4)
         "detectron2.utils.events": pkg + ".d2.events", "detectron2.utils.comm": pkg + ".d2.comm",
         "detectron2.utils.registry": pkg + ".d2.registry", "detectron2.modeling": pkg + ".cubercnn.modeling.registries",
         # the names tools/train_net.py itself imports (:11-23)

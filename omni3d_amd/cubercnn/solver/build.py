@@ -8,7 +8,8 @@ bucket (grouped by weight decay so a group is a contiguous range), gradients acc
 bucket (`param.grad` are views, so the training script's per-parameter NaN scan at tools/train_net.py:226-233
 still works), and `step()` is one fused kernel per group.  The flat gradient bucket is also what the
 data-parallel all-reduce operates on (one RCCL call, no per-tensor launches), and a fused non-finite scan of
-it can gate the step on the device."""
+it can gate the step on the device.  SOLVER.CLIP_GRADIENTS (build.py:68, maybe_add_gradient_clipping) is fused the same way: a
+per-parameter norm pass over a tile table of the bucket (two launches) and update kernels that clip the gradient as they read it."""
 import os
 
 import torch
@@ -63,6 +64,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         # gradients.  build_optimizer switches it off when somebody else owns the exchange (a DistributedDataParallel wrapper
         # whose reducer already averaged the gradients: a second pass over the 191.6 MB bucket would only cost time)
         self.exchange_in_step = True
+        self.clip = None         # SOLVER.CLIP_GRADIENTS: (type, value, norm type), set by arm_clipping
 
     def _build_buckets(self):
         plist = [(g, p) for g in self.param_groups for p in g["params"]]
@@ -153,6 +155,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self.n_stages = (max(self.stage_ranges) + 1) if self.stage_ranges else 1
         self.early_ranges = list(self.stage_ranges.get(0, []))
         self.late_ranges = [r for k in sorted(self.stage_ranges) if k > 0 for r in self.stage_ranges[k]]
+        self._clip_t = None      # the clip tiles (_clip_tables), built when clipping is first armed
 
     @staticmethod
     def _grad_stage(p):
@@ -378,6 +381,66 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 "note": "exposed_ms: device time between the events around the waits of all_reduce_finish -- the share of the exchange that "
                         "backward did not hide"}
 
+    # ---- SOLVER.CLIP_GRADIENTS (d2/solver.py maybe_add_gradient_clipping, the contract is stated there) -------------------------------
+    def arm_clipping(self, clip_type, clip_value=1.0, norm_type=2.0):
+        """Every later step() clips each parameter's gradient on its own before the update: "norm" = clip_grad_norm_(p, clip_value,
+        norm_type), "value" = clip_grad_value_(p, clip_value); None disarms.  Fused: the norm pass is two launches over the bucket, the
+        update kernels apply the coefficient (or the clamp) as they read the gradient.  Unlike the reference, p.grad keeps the
+        unclipped gradient."""
+        if clip_type is None:
+            self.clip = None
+            return
+        if clip_type not in det.CLIP_MODES:
+            raise ValueError(f"unknown gradient clip type {clip_type!r} (expected 'value' or 'norm')")
+        norm_type = float(norm_type)
+        if clip_type == "norm" and not norm_type > 0:
+            raise ValueError(f"NORM_TYPE must be > 0 (or inf), got {norm_type}")
+        self._clip_tables()
+        self.clip = (clip_type, float(clip_value), norm_type)
+
+    def _clip_tables(self):
+        """Host-side tile table over the parameters' own elements (the zero padding of fused groups and of the 16-byte alignment is
+        left out), sorted by bucket offset: tiles (T, 3) = [index in _ordered_params(), first element, count <= CLIP_TILE]; ptab
+        (P, 2) = [first tile, tile count] per parameter; the tile range of every segment; the device buffers of the norm pass."""
+        if self._clip_t is not None:
+            return self._clip_t
+        import bisect
+        T = det.CLIP_TILE
+        params = self._ordered_params()
+        rows = []
+        for k, p in enumerate(params):
+            off, n = self._slot[id(p)]
+            rows += [(off + s, k, min(T, n - s)) for s in range(0, n, T)]
+        rows.sort()
+        assert all(a + n <= self.flat_grad.numel() for a, _, n in rows)
+        ptab = [[0, 0] for _ in params]
+        for t, (_, k, _) in enumerate(rows):
+            if ptab[k][1] == 0:
+                ptab[k][0] = t
+            ptab[k][1] += 1
+        starts = [a for a, _, _ in rows]
+        dev = self.flat_grad.device
+        self._clip_t = {
+            "tiles": torch.tensor([[k, a, n] for a, k, n in rows], dtype=torch.int64).reshape(-1, 3).to(dev),
+            "ptab": torch.tensor(ptab, dtype=torch.int64).reshape(-1, 2).to(dev),
+            "segments": [(bisect.bisect_left(starts, s), bisect.bisect_left(starts, e)) for s, e, _ in self.segments],
+            "partial": torch.zeros(len(rows), dtype=torch.float64, device=dev),
+            "norm": torch.zeros(len(params), dtype=torch.float32, device=dev),
+            "coef": torch.ones(len(params), dtype=torch.float32, device=dev),
+        }
+        return self._clip_t
+
+    @property
+    def clip_norms(self):
+        """device (P,): each parameter's gradient norm as the last norm-clipped step() saw it (the averaged gradient), in
+        _ordered_params() order"""
+        return None if self._clip_t is None else self._clip_t["norm"]
+
+    def _clip_norm_pass(self):
+        t, (_, value, norm_type) = self._clip_t, self.clip
+        det.clip_norm_partials(self.flat_grad, t["tiles"], norm_type, t["partial"])
+        det.clip_norm_coef(t["partial"], t["ptab"], norm_type, value, self._grad_scale, t["norm"], t["coef"])
+
     @torch.no_grad()
     def check_nonfinite(self, flag):
         """flag (1,) device float: set to 1 if any gradient element is NaN/Inf (tools/train_net.py:222-233)."""
@@ -403,6 +466,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
                 self.all_reduce_grads()
+        if self.clip is not None and self.clip[0] == "norm":
+            self._clip_norm_pass()           # the exchange has finished: the norms are those of the averaged gradients
         self._step_segments()
         from ..modeling.layers import PARAM_EPOCH
         PARAM_EPOCH[0] += 1                  # (inference-side caches of values derived from parameters: layers.BatchNorm2d)
@@ -432,8 +497,14 @@ class FlatSGD(_FlatOptimizer):
 
     def _step_segments(self):
         first = self._steps == 0
-        for start, end, gi in self.segments:
+        for i, (start, end, gi) in enumerate(self.segments):
             g = self.param_groups[gi]          # looked up at step time: hyper-parameters are whatever the live groups say now
+            if self.clip is not None:
+                t0, t1 = self._clip_t["segments"][i]
+                det.sgd_step_clipped(self.flat_param, self.flat_grad, self.flat_mom, self._clip_t["tiles"], t0, t1, self.clip[0],
+                                     self._clip_t["coef"], self.clip[1], g["lr"], g["momentum"], g["dampening"], g["weight_decay"],
+                                     g["nesterov"], first_step=first, skip_flag=self.skip_flag, grad_scale=self._grad_scale)
+                continue
             det.sgd_step(self.flat_param[start:end], self.flat_grad[start:end], self.flat_mom[start:end], g["lr"],
                          g["momentum"], g["dampening"], g["weight_decay"], g["nesterov"], first_step=first, skip_flag=self.skip_flag,
                          grad_scale=self._grad_scale)
@@ -497,8 +568,16 @@ class FlatAdam(_FlatOptimizer):
     def _step_segments(self):
         det.adam_tick(self.dev_step, self.skip_flag)
         st = self.flat_state
-        for start, end, gi in self.segments:
+        for i, (start, end, gi) in enumerate(self.segments):
             g = self.param_groups[gi]
+            if self.clip is not None:
+                t0, t1 = self._clip_t["segments"][i]
+                det.adam_step_clipped(self.flat_param, self.flat_grad, st["exp_avg"], st["exp_avg_sq"],
+                                      st["max_exp_avg_sq"] if g["amsgrad"] else None, self._clip_t["tiles"], t0, t1, self.clip[0],
+                                      self._clip_t["coef"], self.clip[1], g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                                      g["weight_decay"], self.decoupled, self.dev_step, skip_flag=self.skip_flag,
+                                      grad_scale=self._grad_scale)
+                continue
             vmax = st["max_exp_avg_sq"][start:end] if g["amsgrad"] else None
             det.adam_step(self.flat_param[start:end], self.flat_grad[start:end], st["exp_avg"][start:end], st["exp_avg_sq"][start:end],
                           vmax, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.decoupled, self.dev_step,
@@ -644,7 +723,8 @@ def build_optimizer(cfg, model):
     if under_ddp and own:
         from .ddp import broadcast_replica
         broadcast_replica(inner, opt)      # the initial parameter / buffer broadcast DDP's constructor skipped for ignored names
-    return opt
+    from ...d2.solver import maybe_add_gradient_clipping
+    return maybe_add_gradient_clipping(cfg, opt)   # last, as build.py:68: SOLVER.CLIP_GRADIENTS arms the fused per-parameter clip
 
 
 def freeze_bn(network):

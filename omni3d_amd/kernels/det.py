@@ -484,6 +484,44 @@ def adam_tick(step, skip_flag=None):
     L.call("omni_adam_tick", _lib.ptr(step), _lib.ptr(skip_flag), _lib.stream_of(step))
 
 
+# ---- SOLVER.CLIP_GRADIENTS over the flat bucket (csrc/optim.hip; tables built by cubercnn/solver/build.py _FlatOptimizer) --------
+CLIP_TILE = 8192       # elements per tile of the clip table: one workgroup of the norm and the clipped update kernels each
+CLIP_MODES = {"norm": 1, "value": 2}
+
+
+def clip_norm_partials(grad, tiles, norm_type, partial):
+    """partial[t] (float64) = sum |grad|^p over tile t (max |grad| for p = inf); tiles (ntiles, 3) int64 address into `grad`"""
+    L = _dev(grad, tiles, partial)
+    L.call("omni_clip_norm_partials", _lib.ptr(grad), _lib.ptr(tiles), tiles.shape[0], float(norm_type), _lib.ptr(partial),
+           _lib.stream_of(grad))
+
+
+def clip_norm_coef(partial, ptab, norm_type, max_norm, grad_scale, norm, coef):
+    """per parameter: norm = grad_scale * (its partials)^(1/p), coef = min(max_norm / (norm + 1e-6), 1)"""
+    L = _dev(partial, ptab, norm, coef)
+    L.call("omni_clip_norm_coef", _lib.ptr(partial), _lib.ptr(ptab), ptab.shape[0], float(norm_type), float(max_norm), float(grad_scale),
+           _lib.ptr(norm), _lib.ptr(coef), _lib.stream_of(partial))
+
+
+def sgd_step_clipped(param, grad, buf, tiles, t0, t1, clip_mode, coef, clip_value, lr, momentum=0.9, dampening=0.0, weight_decay=0.0,
+                     nesterov=False, first_step=False, skip_flag=None, grad_scale=1.0):
+    """sgd_step over the tiles [t0, t1) of the flat buckets (param / grad / buf: bucket bases), gradient clipped as it is read"""
+    L = _dev(param, grad, buf, tiles, coef, skip_flag)
+    L.call("omni_sgd_step_clipped", _lib.ptr(param), _lib.ptr(grad), _lib.ptr(buf), _lib.ptr(tiles), int(t0), int(t1),
+           CLIP_MODES[clip_mode], _lib.ptr(coef), float(clip_value), float(lr), float(momentum), float(dampening), float(weight_decay),
+           int(nesterov), int(first_step), float(grad_scale), _lib.ptr(skip_flag), _lib.stream_of(param))
+
+
+def adam_step_clipped(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, tiles, t0, t1, clip_mode, coef, clip_value, lr, beta1, beta2, eps,
+                      weight_decay, decoupled, step, skip_flag=None, grad_scale=1.0):
+    """adam_step over the tiles [t0, t1) of the flat buckets, gradient clipped as it is read"""
+    L = _dev(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, tiles, coef, step, skip_flag)
+    L.call("omni_adam_step_clipped", _lib.ptr(param), _lib.ptr(grad), _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), _lib.ptr(max_exp_avg_sq),
+           _lib.ptr(tiles), int(t0), int(t1), CLIP_MODES[clip_mode], _lib.ptr(coef), float(clip_value), float(lr), float(beta1),
+           float(beta2), float(eps), float(weight_decay), int(decoupled), _lib.ptr(step), float(grad_scale), _lib.ptr(skip_flag),
+           _lib.stream_of(param))
+
+
 def nonfinite_any(grad, flag):
     L = _dev(grad, flag)
     L.call("omni_nonfinite_any", _lib.ptr(grad), grad.numel(), _lib.ptr(flag), _lib.stream_of(grad))
