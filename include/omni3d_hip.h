@@ -127,16 +127,6 @@ int omni_gemm_batched_split(const float* A, const float* B, float* out, int batc
  * element written once by its owner -- deterministic, no atomics, no zero-fill. */
 int omni_conv2d_s2_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K, int lddy, int lddx,
                          int accumulate, void* stream);
-/* Round 6: n <= 64 direct weight gradients (nn.Conv2d backward of the 1 x 1 roots / projections / laterals and the stride-2 3 x 3
- * layers, cubercnn/modeling/backbone/dla.py:43-51, 159-172, 205-214; detectron2 FPN laterals) in as few launches as their tile shapes
- * allow -- normally one per backward stage.  Dense tensors (ldx = C, lddy = K), square filters; arrays are HOST arrays of n entries.
- * nsrc[i] > 0: x of problem i is the channel concatenation of xs[i * 6 + s] (widths cs[i * 6 + s]), as omni_conv2d_wgrad_multi_det.
- * Deterministic form (ctr != NULL): every problem keeps the split structure of its own omni_conv2d_wgrad_det launch -- bit-identical
- * results; plan != NULL: plan[2] = counters, plan[3] = workspace floats needed, nothing is launched. */
-int omni_conv2d_wgrad_batch_det(const void* const* x, const void* const* dy, const void* const* dw, const int* N, const int* H, const int* W,
-                                const int* C, const int* K, const int* R, const int* stride, const int* pad, const int* accumulate,
-                                const void* const* xs, const int* cs, const int* nsrc, int n, float* ws, long long ws_floats, int* ctr,
-                                int n_ctr, long long* plan, void* stream);
 /* omni_conv2d_wgrad_det for an input that is the channel concatenation of nsrc <= 6 dense NHWC tensors (omni_conv2d_fwd_multi_det):
  * dw (K, 1, 1, sum cs) = dy^T x of the DLA Root's 1 x 1 convolution (dla.py:166-172) without the concatenated copy; cs[s] % 4 == 0,
  * xs / cs HOST arrays, dy (N, H, W, K) with pixel pitch lddy.  Bit-identical to the single-tensor entry on the concatenated input.
@@ -645,14 +635,6 @@ int omni_maxpool3s2_bwd(const float* x, const float* dy, float* dx, int N, int H
 /* tile = 2: F(2x2,3x3), P = 16 points;  tile = 4: F(4x4,3x3), P = 36 points, H and W multiples of 4.  T = N*(H/tile)*(W/tile);
  * the [16] above reads [P]. */
 int omni_wino_in(const float* x, float* V, int N, int H, int W, int C, int tile, void* stream);
-/* conv -> BatchNorm(+ReLU) -> 3x3 conv (the inside of every DLA / torchvision BasicBlock, dla.py:60-66): omni_bn_finalize_fwd turns the
- * first convolution's epilogue statistics into (scale, shift) and omni_wino_in_affine applies them (+ ReLU) while it loads the input
- * tiles of the second -- affine = [scale (C) | shift (C)], zero padding outside the image as for the normalised tensor, which is
- * never stored.  affine NULL == omni_wino_in. */
-int omni_wino_in_affine(const float* x, const float* affine, int relu, float* V, int N, int H, int W, int C, int tile, void* stream);
-int omni_bn_finalize_fwd(const float* partial, int nblk, const float* gamma, const float* beta, float* running_mean,
-                         float* running_var, float* mean_rstd, float* scale_shift, int P, int C, float eps, float momentum,
-                         void* stream);
 int omni_wino_out(const float* M, const float* bias, float* y, int N, int H, int W, int K, int relu, int tile, void* stream);
 int omni_wino_dy(const float* dy, float* dM, int N, int H, int W, int K, int tile, void* stream);
 /* omni_wino_weights for n <= 48 filters in ONE launch (the weights are fixed during a step: every filter transform of the forward pass
@@ -661,15 +643,6 @@ int omni_wino_weights_multi(const void* const* g, const void* const* U, const vo
                             const int* tile, int n, void* stream);
 /* backward: dM (as omni_wino_dy) and V_dy (as omni_wino_in of dy) from one read of dy */
 int omni_wino_dy_in(const float* dy, float* dM, float* Vd, int N, int H, int W, int K, int tile, void* stream);
-/* Row-range forms (round 4): the Winograd-domain array is a row range of a wider (points, rows_total, channels) array holding the tiles
- * of several tensors side by side -- the FPN levels under the RPN's shared 3x3 convolution (detectron2 StandardRPNHead.conv,
- * configs/Base.yaml:49) -- so that ONE batched GEMM over rows_total rows serves all of them.  V / M / dM / Vd point at the tensor's
- * first row; plane = rows_total * channels floats between point planes.  omni_wino_out_rows: carry != NULL selects the fan-in form of
- * omni_wino_out_carry (no bias / ReLU then). */
-int omni_wino_in_rows(const float* x, float* V, int N, int H, int W, int C, int tile, long long plane, void* stream);
-int omni_wino_out_rows(const float* M, const float* bias /*nullable*/, const float* carry /*nullable*/, long long ldc, float* y, int N,
-                       int H, int W, int K, int relu, int tile, long long plane, void* stream);
-int omni_wino_dy_in_rows(const float* dy, float* dM, float* Vd, int N, int H, int W, int K, int tile, long long plane, void* stream);
 int omni_wino_weights(const float* g, float* U /*nullable*/, float* U_flip /*nullable: U'*/, int K, int C, int tile, void* stream);
 int omni_wino_dweights(const float* dU, float* dg, int K, int C, int accumulate, int tile, void* stream);
 /* n <= 16 of them in one launch, each ADDED into its gradient view; sources naming the same dg (the RPN's shared convolution: one

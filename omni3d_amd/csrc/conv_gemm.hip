@@ -620,8 +620,8 @@ __global__ void __launch_bounds__(256) conv_dgrad_kernel(ConvP p) {
 //   Each thread owns one (tap, c) float4 column of B and walks its BI pixel rows with incremental
 //   (oh, ow, offset) cursors -- no integer division inside the slab loop.
 // =================================================================================================
-// The body takes its place in the launch as arguments (bx / by / bz of gx / gy workgroups) so that ONE launch can carry several
-// problems (conv_wgrad_multi_kernel below: a workgroup looks its problem up and runs this body with that problem's coordinates).
+// The body takes its place in the launch as arguments (bx / by / bz of gx / gy workgroups); conv_wgrad_kernel passes its own block
+// indices and grid extents.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int BK>
 __device__ __forceinline__ void conv_wgrad_body(ConvP& p, int pix_per_split, int bx, int by, int bz, int gx, int gy, float* smem) {
     constexpr int WM = BM / (32 * WAVES_M), WN = BN / (32 * WAVES_N);
@@ -899,31 +899,6 @@ __global__ void __launch_bounds__(256) conv_wgrad_pf_kernel(ConvP p, int pix_per
     }
     conv_wgrad_body_pf<BM, BN, WAVES_M, WAVES_N, BK, PF>(p, pix_per_split, bx, by, gx, gy, smem);
 }
-
-// Round 6: the direct weight gradients of one backward stage in ONE launch (the Winograd-domain ones have had
-// gemm_tn_multi_kernel since round 4: 0.23 -> 0.66 of peak inside the step).  The 23 direct launches of a step -- 1 x 1 roots,
-// projections and laterals, stride-2 3 x 3 layers: 1-2.4 GFLOP each -- ran at 0.23-0.30 of peak inside the step: every launch ramps up
-// and drains on its own while the weight-gradient stream shares the chip with the critical path.  Here problem q owns the workgroups
-// [first[q], first[q + 1]) of a 1-D grid, local index l -> (tile l % tiles[q], split l / tiles[q]); arithmetic, split structure,
-// workspace slots and counters of every problem are exactly those of its own launch of conv_wgrad_kernel (bit-identical results).
-constexpr int WGRAD_MULTI_MAX = 12;      // 12 x sizeof(ConvP) + the index arrays stay below the 4 KB of kernel arguments
-struct ConvWMulti {
-    ConvP p[WGRAD_MULTI_MAX];
-    int pps[WGRAD_MULTI_MAX], tiles[WGRAD_MULTI_MAX], splits[WGRAD_MULTI_MAX], first[WGRAD_MULTI_MAX + 1];
-    int n;
-};
-template <int BM, int BN, int WAVES_M, int WAVES_N, int BK = 32>
-__global__ void __launch_bounds__(256) conv_wgrad_multi_kernel(ConvWMulti m) {
-    __shared__ __attribute__((aligned(16))) float smem[2 * BK * (BM + BN)];
-    int q = 0;
-#pragma unroll
-    for (int i = 1; i < WGRAD_MULTI_MAX; ++i)
-        if (i < m.n && (int)blockIdx.x >= m.first[i]) q = i;
-    const int l = (int)blockIdx.x - m.first[q];
-    ConvP p = m.p[q];
-    conv_wgrad_body<BM, BN, WAVES_M, WAVES_N, BK>(p, m.pps[q], l % m.tiles[q], l / m.tiles[q], 0, m.tiles[q], m.splits[q], smem);
-}
-
 
 // =================================================================================================
 // Persistent batched GEMM  out[b] (M x N) = A[b] (M x K) * B[b] (N x K)^T   (the 16 Winograd-point GEMMs, K = channels)
@@ -1817,115 +1792,6 @@ int omni_conv2d_wgrad_det(const float* x, const float* dy, float* dw, int N, int
                           void* stream) {
     return conv2d_wgrad_impl(x, dy, dw, N, H, W, C, K, R, S, stride, pad, ldx, lddy, accumulate, tile, stream,
                              DetArgs{ws, ws_floats, (unsigned*)ctr, n_ctr, plan});
-}
-
-// Round 6: n direct weight gradients (dense tensors: ldx = C, lddy = K; square filters) in as few launches as their tile shapes allow
-// -- normally ONE (conv_wgrad_multi_kernel; <= 12 problems per launch, problems of another tile shape go to a launch of their own).
-// Problem i: dw[i] (K, R, R, C) (+)= dy[i] (N, OH, OW, K)^T x[i] (N, H, W, C); nsrc[i] > 0: x is the channel concatenation of the
-// nsrc[i] tensors xs[i * 6 + s] of widths cs[i * 6 + s] (1 x 1 / stride 1, as omni_conv2d_wgrad_multi_det).  Deterministic form only
-// (ctr != NULL): every problem keeps the split structure, workspace layout and counters of its own omni_conv2d_wgrad_det launch
-// (bit-identical results), at offsets inside ws / ctr; plan != NULL: plan[2] = counters, plan[3] = workspace floats, nothing launched.
-int omni_conv2d_wgrad_batch_det(const void* const* x, const void* const* dy, const void* const* dw, const int* N, const int* H, const int* W,
-                                const int* C, const int* K, const int* R, const int* stride, const int* pad, const int* accumulate,
-                                const void* const* xs, const int* cs, const int* nsrc, int n, float* ws, long long ws_floats, int* ctr,
-                                int n_ctr, long long* plan, void* stream) {
-    if (n <= 0 || n > 64 || x == nullptr || dy == nullptr || dw == nullptr) return OMNI_ERR_ARG;
-    if (plan == nullptr && ctr == nullptr) return OMNI_ERR_ARG;
-    struct One { ConvP p; WgradGeom g; long ws_off; int ctr_off; long work; };
-    One one[64];
-    long ws_need = 0;
-    long ctr_need = 1;        // (counter 0: the unsplit accumulating launches' marker, see omni_conv2d_wgrad_det)
-    int live = 0;
-    hipStream_t st = (hipStream_t)stream;
-    for (int i = 0; i < n; ++i) {
-        const int S = R[i];
-        ConvP p{(const float*)x[i], (const float*)dy[i], nullptr, (float*)dw[i], N[i], H[i], W[i], C[i], (H[i] + 2 * pad[i] - R[i]) / stride[i] + 1,
-                (W[i] + 2 * pad[i] - S) / stride[i] + 1, K[i], R[i], S, stride[i], pad[i], C[i], 0, K[i], 0, accumulate[i], 1};
-        p.stats = nullptr; p.ws = nullptr; p.ctr = nullptr; p.nsrc = 0;
-        p.xb = p.wb = p.ob = 0;
-        const int ns = nsrc != nullptr ? nsrc[i] : 0;
-        if (ns > 0) {
-            if (ns > OMNI_MAX_SRC || xs == nullptr || cs == nullptr || R[i] != 1 || stride[i] != 1 || pad[i] != 0) return OMNI_ERR_ARG;
-            p.coff[0] = 0;
-            for (int q = 0; q < OMNI_MAX_SRC; ++q) {
-                const bool ok = q < ns;
-                const int c = ok ? cs[i * OMNI_MAX_SRC + q] : 0;
-                if (ok && (xs[i * OMNI_MAX_SRC + q] == nullptr || c <= 0 || (c & 3))) return OMNI_ERR_ARG;
-                p.xs[q] = ok ? (const float*)xs[i * OMNI_MAX_SRC + q] : nullptr;
-                p.coff[q + 1] = p.coff[q] + c;
-            }
-            if (p.coff[ns] != C[i]) return OMNI_ERR_ARG;
-            p.nsrc = ns;
-            p.x = p.xs[0];
-        } else {
-            for (int q = 0; q < OMNI_MAX_SRC; ++q) { p.xs[q] = nullptr; p.coff[q] = 0; }
-            p.coff[OMNI_MAX_SRC] = 0;
-        }
-        if (p.x == nullptr || p.w == nullptr || p.out == nullptr || bad_geom(p) || (K[i] & 3) || (C[i] & 3)) return OMNI_ERR_ARG;
-        const long P = (long)N[i] * p.OH * p.OW;
-        const int Nn = R[i] * S * C[i];
-        if (P == 0) {
-            if (plan == nullptr && !accumulate[i]) omni_memset_async((void*)dw[i], 0, sizeof(float) * (size_t)K[i] * Nn, st);
-            continue;
-        }
-        One& o = one[live++];
-        o.p = p;
-        o.g = wgrad_geom(K[i], Nn, P, 0);
-        o.ws_off = ws_need;
-        o.ctr_off = (int)ctr_need;
-        o.work = (long)o.g.pps;
-        if (o.g.splits > 1) {
-            ws_need += omni_split_ws_floats(o.g.tiles, o.g.splits, (long)o.g.bm * o.g.bn);
-            ctr_need += omni_split_counters(o.g.tiles, o.g.splits);
-        }
-    }
-    if (plan != nullptr) { plan[0] = 0; plan[1] = 0; plan[2] = ctr_need; plan[3] = ws_need; return OMNI_OK; }
-    if (live == 0) return OMNI_OK;
-    if (n_ctr < ctr_need || (ws_need > 0 && (ws == nullptr || ws_floats < ws_need))) return OMNI_ERR_ARG;
-    // longest workgroups first (dispatch follows the id): the short ones fill the tail
-    for (int a = 1; a < live; ++a) {
-        const One v = one[a];
-        int b = a;
-        for (; b > 0 && one[b - 1].work < v.work; --b) one[b] = one[b - 1];
-        one[b] = v;
-    }
-    static const int shapes[4][2] = {{128, 128}, {128, 64}, {64, 64}, {32, 128}};
-    for (int sh = 0; sh < 4; ++sh) {
-        int j0 = 0;
-        while (true) {
-            ConvWMulti m;
-            m.n = 0;
-            long first = 0;
-            int j = j0;
-            for (; j < live && m.n < WGRAD_MULTI_MAX; ++j) {
-                One& o = one[j];
-                if (o.g.bm != shapes[sh][0] || o.g.bn != shapes[sh][1]) continue;
-                const long blocks = (long)o.g.tiles * o.g.splits;
-                if (first + blocks > 0x7fffffff) return OMNI_ERR_ARG;
-                o.p.ws = o.g.splits > 1 ? ws + o.ws_off : ws;
-                o.p.ctr = (unsigned*)ctr + (o.g.splits > 1 ? o.ctr_off : 0);
-                o.p.relu = 0;
-                m.p[m.n] = o.p;
-                m.pps[m.n] = o.g.pps;
-                m.tiles[m.n] = o.g.tiles;
-                m.splits[m.n] = (int)o.g.splits;
-                m.first[m.n] = (int)first;
-                first += blocks;
-                ++m.n;
-            }
-            j0 = j;
-            if (m.n == 0) break;
-            for (int q = m.n; q <= WGRAD_MULTI_MAX; ++q) m.first[q] = (int)first;
-            for (int q = m.n; q < WGRAD_MULTI_MAX; ++q) { m.pps[q] = 32; m.tiles[q] = 1; m.splits[q] = 1; m.p[q] = m.p[0]; }
-            constexpr int WBK = 32;
-            if (sh == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_multi_kernel<128, 128, 2, 2, WBK>), dim3((unsigned)first), dim3(256), 0, st, m);
-            else if (sh == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_multi_kernel<128, 64, 2, 2, WBK>), dim3((unsigned)first), dim3(256), 0, st, m);
-            else if (sh == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_multi_kernel<64, 64, 2, 2, WBK>), dim3((unsigned)first), dim3(256), 0, st, m);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_multi_kernel<32, 128, 1, 4, WBK>), dim3((unsigned)first), dim3(256), 0, st, m);
-            if (j0 >= live) break;
-        }
-    }
-    return omni_launch_status();
 }
 
 // omni_conv2d_wgrad_det for an input that is the channel concatenation of nsrc <= 6 dense NHWC tensors (see omni_conv2d_fwd_multi_det):

@@ -52,13 +52,8 @@ class StandardRPNHead(nn.Module):
                 "conv_dims": cfg.MODEL.RPN.CONV_DIMS}
 
     def _shared_conv(self, features):
-        """the shared 3x3 + ReLU over every level: one GEMM per direction for all levels when the maps allow it (functional.
-        _WinoConv3x3Levels), else one convolution per level"""
-        c = self.conv
-        on = HF._WINO_LEVELS == "1" or (HF._WINO_LEVELS == "infer" and not (self.training and torch.is_grad_enabled()))
-        if on and c.stride[0] == 1 and c.padding[0] == 1 and HF.conv3x3_levels_eligible(features, c.weight, 1, 1):
-            return HF.conv3x3_levels(features, c.weight, c.bias, relu=True)
-        return [c(x, relu=True) for x in features]
+        """the shared 3x3 + ReLU over every level, one convolution per level"""
+        return [self.conv(x, relu=True) for x in features]
 
     def forward(self, features):
         wl, wd = self.objectness_logits.weight, self.anchor_deltas.weight
@@ -217,8 +212,7 @@ class RPNWithIgnore(nn.Module):
                 # weight-gradient stream beside the bottom-up; the critical-path graph is cut HERE and its second half starts behind both
                 labels, matched_idx = hook()
             else:
-                with HF.forked():        # (a parallel branch of the captured step, joined behind the proposals; eager: a no-op)
-                    labels, matched_idx = self.label_and_sample_anchors(anchors, targets)
+                labels, matched_idx = self.label_and_sample_anchors(anchors, targets)
             losses = self.losses(levels, anchors, labels, matched_idx, targets)
             self.last_labels = labels
         else:
@@ -226,7 +220,6 @@ class RPNWithIgnore(nn.Module):
         image_hw = targets.image_hw if targets is not None else torch.tensor(
             [list(s) for s in images.image_sizes], dtype=torch.int32, device=anchors.device)
         prop, scores, count = self.predict_proposals(levels, anchors, hw_list, image_hw)
-        HF.join_branch()
         self.last = {"boxes": prop, "scores": scores, "count": count}
         if self.injected is not None and "proposals" in self.injected:
             # stage-wise parity tests: the second stage runs on a given proposal list (list of (n_i, 4) boxes in score

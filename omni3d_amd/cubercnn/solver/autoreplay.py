@@ -62,10 +62,6 @@ TRIM_GB = float(os.environ.get("OMNI_AUTO_REPLAY_TRIM_GB", "48"))        # reser
 TRIM_FREE_GB = float(os.environ.get("OMNI_AUTO_REPLAY_TRIM_FREE_GB", "64"))   # ... but only once the DEVICE has less than this left: a trim is a 0.2-2 s
 #   hipFree, and on a 288 GB device whose loop holds ~100 GB the slack is not needed by anybody (one of four bench.py runs of the final
 #   head took 38.5 instead of 28.5 ms per iteration over the multi-scale region: ~1 s of stalls in its last quarter alone)
-# A/B: stage new batches through pinned host buffers with stream-ordered copies.  MEASURED and left OFF: on this ROCm 7.2 host the 3 MB
-# of image slots take ~20 ms to cross from pinned memory (37.1 against 11.9 ms per iteration, profiles/r04_dropin_phases.log); the pageable
-# copies block the host until the previous step has drained, which costs 0.3 ms per iteration with the losses read every 1000th
-PINNED = os.environ.get("OMNI_AUTO_REPLAY_PINNED", "0") == "1"
 BUCKET = 64                                                           # ImageList's padding granularity (FPN size divisibility)
 # Thrash guard (round 5): real Omni3D training draws 25 short edges x the datasets' aspect ratios -- 66 padded (height,
 # width) pairs in 200 iterations of the synthetic Omni3D-shaped stream (bench.py `dropin_loop_multiscale_stream`), far more than the
@@ -468,9 +464,9 @@ class AutoReplay:
                 "bytes": max(0, torch.cuda.memory_reserved() - mem0) if dev.type == "cuda" else 0}
 
     def _stage(self, entry, batch):
-        """new data into the tensors the graphs were captured on.  With OMNI_AUTO_REPLAY_PINNED=1 everything crosses PCIe from pinned
-        staging buffers (two sets per captured step, taken in turn, reused only after the copies that read a set have executed) with
-        stream-ordered copies, so that the host does not wait for the device here; see PINNED for why that is not the default."""
+        """new data into the tensors the graphs were captured on.  The pageable copies block the host until the previous step has
+        drained (0.3 ms per iteration with the losses read every 1000th); staging through pinned host buffers was measured slower: the
+        3 MB of image slots take ~20 ms to cross from pinned memory (37.1 against 11.9 ms per iteration, profiles/r04_dropin_phases.log)."""
         dev = self.model.device
         sizes = [(b["image"].shape[-2], b["image"].shape[-1]) for b in batch]
         new = pack_targets(batch, sizes, getattr(self.model.roi_heads, "virtual_focal", 512.0), with_gt=True)
@@ -482,45 +478,15 @@ class AutoReplay:
             for k in ("K", "height", "width"):
                 if k in b:
                     s_[k] = b[k]
-        pin = None
-        if dev.type == "cuda" and PINNED:
-            sets = entry.setdefault("pinned", [])
-            turn = entry["turn"] = (entry.get("turn", -1) + 1) % 2
-            if len(sets) <= turn:
-                st = {"img": torch.zeros(entry["slots"].shape, dtype=entry["slots"].dtype).pin_memory(), "event": None}
-                for f in ROW_FIELDS + FIXED_FIELDS:
-                    t = getattr(sp, f)
-                    st[f] = torch.zeros(t.shape, dtype=t.dtype).pin_memory()
-                sets.append(st)
-            pin = sets[turn]
-            if pin["event"] is not None:
-                pin["event"].synchronize()                      # its copies of two iterations ago have executed (normally long ago)
-        host_imgs = pin is not None and all(not b["image"].is_cuda for b in batch)
         for n, b in enumerate(batch):
             h, w = sizes[n]
-            if host_imgs:
-                pin["img"][n, :, :h, :w].copy_(b["image"])                            # host -> pinned (the rest of the slot is masked by image_hw)
-            else:
-                entry["slots"][n, :, :h, :w].copy_(b["image"], non_blocking=True)
-        if host_imgs:
-            entry["slots"].copy_(pin["img"], non_blocking=True)                       # ONE contiguous, asynchronous copy of all slots
+            entry["slots"][n, :, :h, :w].copy_(b["image"], non_blocking=True)
         for f in ROW_FIELDS + FIXED_FIELDS:
             src, dst = getattr(new, f), getattr(sp, f)
-            n = src.shape[0] if f in ROW_FIELDS else None
-            if pin is not None:
-                if n is None:
-                    pin[f].copy_(src)
-                    dst.copy_(pin[f], non_blocking=True)
-                elif n > 0:
-                    pin[f][:n].copy_(src)
-                    dst[:n].copy_(pin[f][:n], non_blocking=True)
-            elif n is None:
-                dst.copy_(src.to(dev, non_blocking=True), non_blocking=True)
+            if f in ROW_FIELDS:
+                dst[:src.shape[0]].copy_(src.to(dev, non_blocking=True), non_blocking=True)
             else:
-                dst[:n].copy_(src.to(dev, non_blocking=True), non_blocking=True)
-        if pin is not None:
-            pin["event"] = torch.cuda.Event()
-            pin["event"].record()
+                dst.copy_(src.to(dev, non_blocking=True), non_blocking=True)
         sp.num_gt, sp.num_ign = new.num_gt, new.num_ign
 
     # ---- backward / step protocol --------------------------------------------------------------------------------------

@@ -44,17 +44,13 @@ class lean_capture:
     gc.collect() and torch.cuda.empty_cache().  A staged step is 14 captures; with one step captured per size bucket
     (solver/autoreplay.py) the empty_cache handed the eager path's cached blocks back to the driver 14 times per new bucket and the
     next eager iteration bought them again with hipMalloc (measured, round 6: -4 .. -15 GB of reserved memory per capture, single
-    iterations of 0.4-2.7 s, profiles/r06_new_shape_*.txt).  The caller synchronises and collects ONCE before its first capture.
-    OMNI_GRAPH_TORCH_CTX=1 restores torch's context manager."""
+    iterations of 0.4-2.7 s, profiles/r06_new_shape_*.txt).  The caller synchronises and collects ONCE before its first capture."""
     _stream = None
 
     def __init__(self, graph, pool=None):
         self.graph, self.pool = graph, pool
-        self.torch_ctx = torch.cuda.graph(graph, pool=pool, capture_error_mode="thread_local") if _TORCH_CTX else None
 
     def __enter__(self):
-        if self.torch_ctx is not None:
-            return self.torch_ctx.__enter__()
         if lean_capture._stream is None:
             lean_capture._stream = torch.cuda.Stream()
         self.stream = lean_capture._stream
@@ -65,78 +61,13 @@ class lean_capture:
         self.graph.capture_begin(capture_error_mode="thread_local", **kw)
 
     def __exit__(self, *exc):
-        if self.torch_ctx is not None:
-            return self.torch_ctx.__exit__(*exc)
         self.graph.capture_end()
         self.ctx.__exit__(*exc)
         torch.cuda.current_stream().wait_stream(self.stream)
         return False
 
 
-_TORCH_CTX = __import__("os").environ.get("OMNI_GRAPH_TORCH_CTX", "0") == "1"
 _GRAPH_DUMP = __import__("os").environ.get("OMNI_GRAPH_DUMP", "")
-
-
-class DeviceEvent:
-    """A HIP event for DEVICE-side ordering only: hipEventDisableTiming | hipEventDisableSystemFence.  torch.cuda.Event (and
-    Stream.wait_stream, which records one) creates its events with hipEventDisableTiming alone, and recording such an event ends with a
-    system-scope release -- "cache writeback and invalidation, and the performance impact of those actions on the execution of
-    following work" (hip_runtime_api.h).  The stage-end events of a replayed step are recorded on the critical-path stream after EVERY
-    M_k while the weight-gradient stream keeps the L2s full of dirty lines; nobody on the host reads anything at those points.
-    Recorded / waited on through the HIP runtime torch already has loaded; one object per use site, re-recorded every step."""
-    _hip = None
-    FLAGS = 0x2 | 0x20000000          # hipEventDisableTiming | hipEventDisableSystemFence
-
-    def __init__(self):
-        import ctypes
-        if DeviceEvent._hip is None:
-            DeviceEvent._hip = ctypes.CDLL("libamdhip64.so")
-        self._ct = ctypes
-        self.ev = ctypes.c_void_p()
-        rc = DeviceEvent._hip.hipEventCreateWithFlags(ctypes.byref(self.ev), ctypes.c_uint(DeviceEvent.FLAGS))
-        if rc != 0:
-            raise RuntimeError("hipEventCreateWithFlags failed: %d" % rc)
-
-    def record(self, stream):
-        rc = DeviceEvent._hip.hipEventRecord(self.ev, self._ct.c_void_p(stream.cuda_stream))
-        if rc != 0:
-            raise RuntimeError("hipEventRecord failed: %d" % rc)
-
-    def wait(self, stream):
-        """`stream` waits for the work this event was last recorded behind"""
-        rc = DeviceEvent._hip.hipStreamWaitEvent(self._ct.c_void_p(stream.cuda_stream), self.ev, self._ct.c_uint(0))
-        if rc != 0:
-            raise RuntimeError("hipStreamWaitEvent failed: %d" % rc)
-
-    def __del__(self):
-        try:
-            if self.ev:
-                DeviceEvent._hip.hipEventDestroy(self.ev)
-        except Exception:
-            pass
-
-
-# MEASURED and left OFF (profiles/r06_ab_device_events.log): 10.80-10.81 ms with device-only events against 10.74-10.77 with torch's --
-# the system-scope release is not what stretches the one stage boundary at which the weight-gradient queue is busy (~140 us instead of
-# ~14, profiles/r06_ab_labels_cuts_gaps.log), and the fence-free markers are no cheaper for the command processor.
-_PIPE_EVENTS = __import__("os").environ.get("OMNI_PIPE_EVENTS", "torch")      # "torch" | "device"
-
-
-_W_CHUNKS = int(__import__("os").environ.get("OMNI_PIPE_W_CHUNKS", "1"))
-
-
-class _GraphSeq:
-    """several graphs replayed back to back (OMNI_PIPE_W_CHUNKS)"""
-
-    def __init__(self):
-        self.graphs = []
-
-    def replay(self):
-        for g in self.graphs:
-            g.replay()
-
-    def pool(self):
-        return self.graphs[-1].pool()
 
 
 def make_side_stream(device=None):
@@ -170,7 +101,6 @@ def make_side_stream(device=None):
 
 
 SIDE_CUS_DEFAULT = 0            # 0 = no mask
-_PIPE_ORDER = __import__("os").environ.get("OMNI_PIPE_ORDER", "interleaved")
 # round 4: a cut at the pooled ROI features + the RPN losses deferred to that cut's stage, so stage 0 = forward + the FC heads'
 # backward and W_0 (the fc1-class weight gradients, 1.1 ms of work) runs beside ROIAlign's / the RPN's backward instead of beside
 # FPN + level 5 / 4 (A/B knob; the gradient bucket's stage layout follows it, solver/build.py)
@@ -485,12 +415,6 @@ class GraphedPipelined:
         torch.cuda.synchronize()
         _t1 = _time.perf_counter()
         HF.side_mode("collect")
-        # forward branches (functional.set_branch_stream): the RPN's labelling + loss beside its proposal selection, inside M0.
-        # MEASURED and left OFF (OMNI_PIPE_BRANCH=1 enables it): M0 ends 0.10 ms earlier on the device, but hipGraphLaunch of a graph
-        # with a fork blocks the host for the length of a step on ROCm 7.2 (host time of the M0 launch 0.1 -> 11.9 ms), the later
-        # stages are enqueued late and the step takes 12.5 ms instead of 11.4 (profiles/r04_ab_branch.log)
-        self.branch = torch.cuda.Stream() if os.environ.get("OMNI_PIPE_BRANCH", "0") == "1" else None
-        prev_branch = HF.set_branch_stream(self.branch)
         # deterministic split reductions (kernels/detmode.py): the critical-path graphs and the weight-gradient graphs replay
         # side by side, so each family gets its own block of arrival counters, allocated before the first capture starts
         from ...kernels import detmode, wino
@@ -499,16 +423,12 @@ class GraphedPipelined:
             stages = []
             pool_m, pool_w = self.pools if self.pools is not None else (None, None)
             self._held = []                 # closures + their inputs: kept for the lifetime of the graphs (see class docstring)
-            self.prologue = None
+            self.prologue = None            # (L, M0a) of the labels split, see _capture_stage0_labels
             while True:
-                gm = torch.cuda.CUDAGraph()
-                if not stages and self._split_forward(bottom_up):
-                    gm = self._capture_stage0_split(bottom_up)
-                    pool_m = gm.pool()
-                elif not stages and self._split_labels():
+                if not stages and self._split_labels():
                     gm, pool_w = self._capture_stage0_labels(pool_m, pool_w)
-                    pool_m = gm.pool()
                 else:
+                    gm = torch.cuda.CUDAGraph()
                     if _GRAPH_DUMP:
                         gm.enable_debug_mode()
                     with lean_capture(gm, pool_m), detmode.domain("M"):
@@ -516,28 +436,16 @@ class GraphedPipelined:
                             self.losses, self.total = self._stage0()
                         else:
                             self.cuts.backward_last()
-                    pool_m = gm.pool()
                     if _GRAPH_DUMP:                 # diagnostic (OMNI_GRAPH_DUMP=dir): the node list of every critical-path graph as a dot file
                         os.makedirs(_GRAPH_DUMP, exist_ok=True)
                         gm.debug_dump(os.path.join(_GRAPH_DUMP, "M%d.dot" % len(stages)))
+                pool_m = gm.pool()
                 fns, keep = HF.side_take()
                 # (measured, profiles/r04_ab_w_shift.log: carrying the heads' weight gradients into the NEXT stage's graph frees M1
                 # -- 1.45 -> 0.79 ms, it is HBM-bound on the p2 maps and so is the fc1 weight gradient beside it -- and M2 pays it
                 # back, 1.73 -> 2.45 ms: the two streams share one throughput, where the weight gradients land does not matter)
                 gw = None
-                if fns and _W_CHUNKS > 1:
-                    # A/B (OMNI_PIPE_W_CHUNKS=n): the stage's weight gradients as n graphs replayed one after the other -- more graph
-                    # boundaries on the weight-gradient queue, at which the command processor looks at the critical-path queue again
-                    gw = _GraphSeq()
-                    per = -(-len(fns) // _W_CHUNKS)
-                    for c0 in range(0, len(fns), per):
-                        g1 = torch.cuda.CUDAGraph()
-                        with lean_capture(g1, pool_w), detmode.domain("W"), wino.batched_wgrads():
-                            for fn in fns[c0:c0 + per]:
-                                fn()
-                        pool_w = g1.pool()
-                        gw.graphs.append(g1)
-                elif fns:
+                if fns:
                     gw = torch.cuda.CUDAGraph()
                     with lean_capture(gw, pool_w), detmode.domain("W"), wino.batched_wgrads():
                         for fn in fns:          # (the Winograd-domain GEMMs of the stage leave together when the context closes)
@@ -552,7 +460,6 @@ class GraphedPipelined:
             self.pools = (pool_m, pool_w)
             self.phase_ms = {"warmup": 1e3 * (_t1 - _t0), "capture": 1e3 * (_time.perf_counter() - _t1)}      # (diagnostic: autoreplay's OMNI_AUTO_REPLAY_TIMING)
         finally:
-            HF.set_branch_stream(prev_branch)
             HF.side_take()
             HF.side_mode(prev_mode)
 
@@ -564,56 +471,12 @@ class GraphedPipelined:
         logged scalars and static inputs stay referenced by their owners."""
         self._held = None
 
-    # ---- round 4: the head of the forward pass ---------------------------------------------------------------------------------
-    # The Winograd filter transforms of a pass (one launch, 260 MB moved, ~0.13 ms) sat at the very start of the critical path while
-    # the weight-gradient stream idles through all of forward.  Stage 0 is therefore captured as THREE graphs: P (the transforms,
-    # replayed on the side stream), M0a (zero_grad, preprocessing, stem, DLA level 0 / 1 -- no Winograd layer in there) and M0b
-    # (the rest of stage 0), which starts behind both.  The forward is cut by a callable the bottom-up runs between level 1 and 2.
-    # MEASURED and left OFF (OMNI_PIPE_PROLOGUE=1 enables it): 11.718 ms with and without.  The trace shows why: the head of M0a is
-    # itself HBM-bound (the 191 MB zero-fill of the gradient bucket 25 -> 81 us, preprocessing 8 -> 31 us beside the transform's 260 MB),
-    # so the first Winograd layer starts 7 us earlier, not 130 (profiles/r04_ab_prologue.log).
-    @staticmethod
-    def _split_forward(bottom_up):
-        import os
-        return (bottom_up is not None and hasattr(type(bottom_up), "fwd_split") and os.environ.get("OMNI_PIPE_PROLOGUE", "0") != "0")
-
-    def _capture_stage0_split(self, bottom_up):
-        from ...kernels import detmode
-        HF = self.HF
-        gp, ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        pool = torch.cuda.graph_pool_handle()
-        with torch.cuda.graph(gp, capture_error_mode="thread_local"), detmode.domain("W"):
-            pre = HF.wino_pretransform(self.model)
-        self._held.append((pre,))
-        state = {"done": False}
-
-        def split():
-            if not state["done"]:
-                state["done"] = True
-                ga.capture_end()
-                gb.capture_begin(pool=pool, capture_error_mode="thread_local")
-        torch.cuda.synchronize()
-        cap = torch.cuda.Stream()
-        cap.wait_stream(torch.cuda.current_stream())
-        bottom_up.fwd_split = split
-        try:
-            with torch.cuda.stream(cap), detmode.domain("M"), HF.wino_preloaded(pre):
-                ga.capture_begin(pool=pool, capture_error_mode="thread_local")
-                self.losses, self.total = self._stage0()
-                if not state["done"]:
-                    raise RuntimeError("the forward pass never reached its split point")
-                gb.capture_end()
-        finally:
-            bottom_up.fwd_split = None
-        torch.cuda.current_stream().wait_stream(cap)
-        self.prologue = (gp, ga)
-        return gb
-
     # Round 6: the RPN's anchor labelling + sampling (rpn_match1 / rpn_match2 / top-k of the sampling keys / rpn_finalize: four
     # latency-bound launches, ~0.12 ms with the device otherwise idle) read the anchors and the ground truth only -- nothing the network
     # computes.  Stage 0 is captured as THREE graphs: L (those four launches; replayed on the weight-gradient stream, which idles through
     # all of forward), M0a (zero_grad .. RPN head) and M0b (losses, proposals, ROI heads, the heads' backward), which starts behind both.
-    # Unlike the filter-transform prologue above, L moves no memory to speak of: it hides completely.  OMNI_PIPE_LABELS=0 switches it off.
+    # (A prologue of the Winograd filter transforms, captured the same way, was measured neutral: profiles/r04_ab_prologue.log.)
+    # L moves no memory to speak of: it hides completely.  OMNI_PIPE_LABELS=0 switches it off.
     def _split_labels(self):
         import os
         rpn = getattr(self.model, "proposal_generator", None)
@@ -633,8 +496,8 @@ class GraphedPipelined:
 
         def split():
             if not state["done"]:
-                state["done"] = True
                 ga.capture_end()
+                state["done"] = True
                 gb.capture_begin(pool=ga.pool(), capture_error_mode="thread_local")
             return pre
         if lean_capture._stream is None:
@@ -646,9 +509,16 @@ class GraphedPipelined:
             with torch.cuda.stream(cap), detmode.domain("M"):
                 kw = {"pool": pool_m} if pool_m is not None else {}
                 ga.capture_begin(capture_error_mode="thread_local", **kw)
-                self.losses, self.total = self._stage0()
-                if not state["done"]:
-                    raise RuntimeError("the forward pass never asked for the anchor labels")
+                try:
+                    self.losses, self.total = self._stage0()
+                    if not state["done"]:
+                        raise RuntimeError("the forward pass never asked for the anchor labels")
+                except BaseException:
+                    try:                    # end the capture still open (ga before the split, gb after it); its error is not the news
+                        (gb if state["done"] else ga).capture_end()
+                    except Exception:
+                        pass
+                    raise
                 gb.capture_end()
         finally:
             rpn.__dict__.pop("_label_split", None)
@@ -765,36 +635,21 @@ class GraphedPipelined:
             rec = {"t0": torch.cuda.Event(enable_timing=True), "m": [], "w": [None] * n, "x": [None] * n, "host": []}
             rec["t0"].record(main)
             self._timing.append(rec)
-        dev_ev = _PIPE_EVENTS == "device" and not timing
-        if dev_ev and getattr(self, "_dev_events", None) is None:
-            self._dev_events = [DeviceEvent() for _ in range(n + 3)]            # stage ends, prologue fork / join, end of step
-
-        def order(after, before, slot):
-            """stream `after` waits for what `before` has been given so far (device-side ordering only)"""
-            if dev_ev:
-                e = self._dev_events[slot]
-                e.record(before)
-                e.wait(after)
-            else:
-                after.wait_stream(before)
         if self.prologue is not None:
-            # P on the side stream (behind whatever the main stream did last: the optimizer's update), M0a on the main stream;
+            # L on the side stream (behind whatever the main stream did last: the optimizer's update), M0a on the main stream;
             # M0b -- stages[0] -- starts behind both
-            gp, ga = self.prologue
-            order(side, main, n)
+            gl, ga = self.prologue
+            side.wait_stream(main)
             with torch.cuda.stream(side):
-                gp.replay()
+                gl.replay()
             ga.replay()
-            order(main, side, n + 1)
+            main.wait_stream(side)
 
         def launch_w(k):                              # W_k starts when M_k has finished ...
             gw = self.stages[k][1]
             if gw is None and k > 0 and not self._replay_per_stage:
                 return []
-            if dev_ev:
-                ends[k].wait(side)
-            else:
-                side.wait_event(ends[k])
+            side.wait_event(ends[k])
             with torch.cuda.stream(side):
                 if gw is not None:
                     if timing:
@@ -825,31 +680,18 @@ class GraphedPipelined:
         # host order M_0, M_1, W_0, M_2, W_1, ...: the next critical-path graph is always queued on the main stream before the
         # side-stream launch that depends on an event (measured: a graph launch behind a cross-stream event delays every
         # launch issued after it by ~150 us)
-        if timing:
-            for k in range(n):
+        for k in range(n):
+            if timing:
                 h0 = time.perf_counter()
-                self.stages[k][0].replay()
+            self.stages[k][0].replay()
+            if timing:
                 rec["host"].append(("M%d" % k, (time.perf_counter() - h0) * 1e6))
-                ends[k] = torch.cuda.Event(enable_timing=True)
-                ends[k].record(main)
+            ends[k] = torch.cuda.Event(enable_timing=timing)
+            ends[k].record(main)
+            if timing:
                 rec["m"].append(ends[k])
-                if k >= 1:
-                    pending += launch_w(k - 1)
-            pending += launch_w(n - 1)
-        elif _PIPE_ORDER == "mfirst":               # A/B: every critical-path graph first, then the weight-gradient graphs behind their events
-            for k in range(n):
-                self.stages[k][0].replay()
-                ends[k] = self._dev_events[k] if dev_ev else torch.cuda.Event()
-                ends[k].record(main)
-            for k in range(n):
-                pending += launch_w(k)
-        else:
-            for k in range(n):
-                self.stages[k][0].replay()
-                ends[k] = self._dev_events[k] if dev_ev else torch.cuda.Event()
-                ends[k].record(main)
-                if k >= 1:
-                    pending += launch_w(k - 1)
-            pending += launch_w(n - 1)
-        order(main, side, n + 2)                      # ... and everything after the step waits for the last W
+            if k >= 1:
+                pending += launch_w(k - 1)
+        pending += launch_w(n - 1)
+        main.wait_stream(side)                        # ... and everything after the step waits for the last W
         return self.losses, self.total, pending + self._late(self._replay_per_stage)

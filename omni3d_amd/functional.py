@@ -184,8 +184,6 @@ def _side_run(fn, keepalive):
     mode = _side["mode"]
     if mode == "inline" or (dev.type != "cuda" and mode != "collect"):
         return fn()
-    if _DEBUG_DROP_SIDE:           # timing experiment only (tools): the critical path alone, parameter gradients never computed
-        return None
     _side["queue"].append(fn)
     _side["pending"].extend(keepalive)
     if mode == "collect":
@@ -201,49 +199,6 @@ def _side_run(fn, keepalive):
     return None
 
 
-# ---- a second branch inside the forward pass (round 4) ------------------------------------------------------------------------------
-# The RPN's anchor labelling + sampling + loss forward (0.14 ms of latency-bound launches) and its proposal selection (top-k, decode,
-# NMS, top-k: 0.32 ms of them) both start from the head outputs and do not read each other.  While a step is being captured
-# (solver/graphed.py installs a stream) the first runs on that stream -- a parallel branch of the SAME hipGraph -- and the capturing
-# stream waits for it where the proposals are done.  Without an installed stream (eager steps, tests) nothing changes.
-_branch = {"stream": None, "open": False}
-
-
-def set_branch_stream(stream):
-    """-> the previous one; None switches the fork off"""
-    prev, _branch["stream"], _branch["open"] = _branch["stream"], stream, False
-    return prev
-
-
-class forked:
-    """with forked(): launches inside go to the branch stream (which first waits for everything the current stream has been given);
-    join_branch() makes the current stream wait for the branch.  Custom Functions enter it INSIDE forward(), so that autograd keeps
-    seeing the ambient stream and runs their backward there."""
-
-    def __enter__(self):
-        self.ctx = None
-        st = _branch["stream"]
-        if st is not None:
-            if not _branch["open"]:
-                st.wait_stream(torch.cuda.current_stream())
-                _branch["open"] = True
-            self.ctx = torch.cuda.stream(st)
-            self.ctx.__enter__()
-        return self
-
-    def __exit__(self, *a):
-        if self.ctx is not None:
-            self.ctx.__exit__(*a)
-        return False
-
-
-def join_branch():
-    if _branch["open"]:
-        torch.cuda.current_stream().wait_stream(_branch["stream"])
-        _branch["open"] = False
-
-
-_DEBUG_DROP_SIDE = _environ.get("OMNI_DEBUG_DROP_SIDE", "0") == "1"
 BIAS_GRAD_SIDE = _environ.get("OMNI_BIAS_GRAD_SIDE", "1") != "0"
 
 
@@ -346,9 +301,6 @@ class _Conv2d(Function):
         return dx, dw, db, None, None, None, None
 
 
-_STEM_FIRST_WGRAD_SIDE = _os_environ_get("OMNI_STEM_FIRST_WGRAD_SIDE", "0") == "1"      # A/B knob
-
-
 class _StemFirst(Function):
     """The first layer (dla.py:241-245: 7x7, 3 -> 16, stride 1) on the 4-channel padded image, with the 3-channel filter read and its
     gradient written in the model's own layout (csrc/stem_conv.hip, round 6).  The image needs no gradient."""
@@ -373,13 +325,11 @@ class _StemFirst(Function):
             gw = None
         dw = None
         if ctx.needs_input_grad[1]:
-            def wgrad():
-                return conv.stem_first_wgrad(x, dy, accum_into=gw)
-            # This is the LAST weight gradient of a step (its dy is the last tensor backward produces).  Measured (round 6,
-            # profiles/r06_ab_tail_balance.log): the weight-gradient stream reaches the end of backward ~0.15 ms behind the main
-            # stream, so queued there this launch started 150 us after its input was ready; on the main stream it starts at once and
-            # the two streams end together.
-            dw = _side_run(wgrad, (x, dy)) if (gw is not None and _STEM_FIRST_WGRAD_SIDE) else wgrad()
+            # This is the LAST weight gradient of a step (its dy is the last tensor backward produces), so it runs on the main stream.
+            # Measured (round 6, profiles/r06_ab_tail_balance.log): the weight-gradient stream reaches the end of backward ~0.15 ms
+            # behind the main stream, so queued there this launch started 150 us after its input was ready; on the main stream it
+            # starts at once and the two streams end together.
+            dw = conv.stem_first_wgrad(x, dy, accum_into=gw)
         return None, dw, None
 
 
@@ -476,105 +426,6 @@ class _WinoConv3x3(Function):
         return dx, dw, db, None, None
 
 
-class _WinoConv3x3Levels(Function):
-    """ONE 3x3 / stride 1 / pad 1 convolution (one filter, one bias) applied to several tensors -- detectron2's StandardRPNHead.conv
-    over the FPN levels p2..p6 (configs/Base.yaml:49) -- with the Winograd-domain tiles of all of them side by side in one array: one
-    batched GEMM per direction for all levels instead of one per level (the p4..p6 problems are 256 / 64 / 16 tile rows: alone each
-    is a latency-bound launch), ONE weight-gradient problem whose row reduction sums the levels, and the transforms of every level
-    reading / writing their row range of the shared arrays (csrc/winograd.hip, the *_rows entry points)."""
-
-    @staticmethod
-    def forward(ctx, w, bias, relu, *xs):
-        ctx.set_materialize_grads(False)
-        ctx.direct = (_direct_grad(w), _direct_grad(bias))
-        ctx.slots = [_slot_enter(x, ctx.needs_input_grad[3 + i]) for i, x in enumerate(xs)]
-        w_given = w
-        xs, w = [_cl(x) for x in xs], _cl(w)
-        shapes = [tuple(x.shape) for x in xs]
-        tile = wino.levels_tile(shapes)
-        assert tile in (2, 4), "conv3x3_levels_eligible() first"
-        offs, rows = wino.level_rows(shapes, tile)
-        need_flip = any(x.requires_grad for x in xs)
-        key = (w.data_ptr(), tuple(w.shape), tile)
-        cache = _wino_scope["cache"]
-        U, Uf = cache.get(key, (None, None)) if cache is not None else (None, None)
-        if U is None or (need_flip and Uf is None):
-            U, Uf = wino.transform_weights(w, True, need_flip or Uf is not None, tile)
-            if cache is not None:
-                cache[key] = (U, Uf)
-                if w is w_given:
-                    _wino_scope["record"].append((w, tile, bool(need_flip or Uf is not None)))
-        V = torch.empty(((tile + 2) ** 2, rows, w.shape[1]), dtype=torch.float32, device=w.device)
-        for x, o in zip(xs, offs):
-            wino.transform_input_rows(x, V, o, tile)
-        Mt = wino.gemm_batched(V, U)
-        ys = [wino.transform_output_rows(Mt, o, (sh[0], sh[2], sh[3]), bias, relu) for sh, o in zip(shapes, offs)]
-        ctx.save_for_backward(V, w, Uf if need_flip else None, *(ys if relu else []))
-        ctx.meta = (relu, bias is not None, tile, shapes, offs, rows)
-        return tuple(ys)
-
-    @staticmethod
-    def backward(ctx, *dys):
-        V, w, Uf, *ys = ctx.saved_tensors
-        relu, has_bias, tile, shapes, offs, rows = ctx.meta
-        K = w.shape[0]
-        gw, gb = ctx.direct
-        if gw is not None and not gw.is_contiguous(memory_format=CL):
-            gw = None
-        alloc = torch.zeros if any(d is None for d in dys) else torch.empty         # (a level without a gradient contributes zero rows)
-        dM = alloc((V.shape[0], rows, K), dtype=torch.float32, device=V.device)
-        Vd = alloc((V.shape[0], rows, K), dtype=torch.float32, device=V.device)
-        db = None
-        for l, dy in enumerate(dys):
-            if dy is None:
-                continue
-            masked = relu and _relu_already_masked(dy)       # (the consumer's data-gradient kernel applied the mask)
-            dy = _cl(dy)
-            if relu and not masked:
-                dy = bnpool.relu_bwd(dy.permute(0, 2, 3, 1), ys[l].permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
-            wino.transform_dy_in_rows(dy, dM, Vd, offs[l], tile)
-            if has_bias and ctx.needs_input_grad[1]:
-                part = _bias_grad(dy.permute(0, 2, 3, 1).reshape(-1, K), gb)
-                if gb is None:
-                    db = part if db is None else db + part
-        dw = None
-        if ctx.needs_input_grad[0]:
-            if gw is not None:
-                _side_run(lambda: wino.wgrad_into(V, dM, gw), (V, dM))
-            else:
-                dw = wino.transform_dweights(wino.gemm_batched_wgrad(V, dM), None)
-        dxs = [None] * len(shapes)
-        if any(ctx.needs_input_grad[3:]):
-            if Uf is None:
-                Uf = wino.transform_weights(w, want_u=False, want_flip=True, tile=tile)[1]
-            Mx = wino.gemm_batched(Vd, Uf)
-            for l, (sh, o) in enumerate(zip(shapes, offs)):
-                if not ctx.needs_input_grad[3 + l]:
-                    continue
-
-                def dgrad(carry, sh=sh, o=o):
-                    ok = carry is not None and _carry_pitch(carry) is not None
-                    dx_ = wino.transform_output_rows(Mx, o, (sh[0], sh[2], sh[3]), carry=carry if ok else None)
-                    return dx_ if (ok or carry is None) else dx_ + carry
-                dxs[l] = _slot_deliver(ctx.slots[l], dgrad)
-        return (dw, db, None, *dxs)
-
-
-def conv3x3_levels_eligible(xs, w, stride=1, pad=1):
-    """several tensors under one 3x3 filter through the shared Winograd arrays (_WinoConv3x3Levels)?"""
-    if not (_WINOGRAD and len(xs) > 1 and w.shape[2] == 3 and w.shape[3] == 3 and stride == 1 and pad == 1):
-        return False
-    C, K = w.shape[1], w.shape[0]
-    if C % 32 or K % 32 or C < 128 or K < 128 or any(x.dim() != 4 or x.shape[1] != C or x.dtype != torch.float32 for x in xs):
-        return False
-    return wino.levels_tile([tuple(x.shape) for x in xs]) != 0
-
-
-def conv3x3_levels(xs, w, bias=None, relu=False):
-    """[conv2d(x, w, bias, 1, 1, relu) for x in xs] with one GEMM per direction for all of them (see _WinoConv3x3Levels)"""
-    return list(_WinoConv3x3Levels.apply(w, bias, bool(relu), *xs))
-
-
 class _RPNHead16(Function):
     """objectness_logits + anchor_deltas of detectron2's StandardRPNHead over all FPN levels (csrc/rpn_head.hip): ts = the per-level
     ReLU outputs of the shared 3x3 convolution, (B, 256, H, W) CL -> per-level (B, 16, H, W) CL [3 logits | 12 deltas | 0].
@@ -625,37 +476,9 @@ def rpn_head16(ts, w_obj, b_obj, w_del, b_del):
     return list(_RPNHead16.apply(w_obj, b_obj, w_del, b_del, *ts))
 
 
-_wino_scope = {"cache": None, "record": [], "preloaded": None}     # (weight address, shape) -> (U, U'), only while a model forward is running
+_wino_scope = {"cache": None, "record": []}     # (weight address, shape) -> (U, U'), only while a model forward is running
 
 
-def wino_pretransform(owner, kind="_omni_wino_plan_train"):
-    """every Winograd filter transform the next pass of `owner` will need (the plan its earlier passes left on it), as ONE launch
-    outside the pass -> {(weight address, shape, tile): (U, U')}.  solver/graphed.py captures this as its own little graph and replays
-    it on the idle weight-gradient stream beside the first layers of the forward pass (the transform moves 260 MB; it used to sit
-    at the head of the critical path).  Hand the result to `wino_preloaded` around the pass that should use it."""
-    plan = getattr(owner, kind, None) if _WINO_MULTI else None
-    out = {}
-    if not plan:
-        return out
-    items = [(w, True, flip, tile) for w, tile, flip in plan if w.is_contiguous(memory_format=CL)]
-    for k in range(0, len(items), wino.WEIGHTS_MULTI_MAX):
-        chunk = items[k:k + wino.WEIGHTS_MULTI_MAX]
-        for (w, _, _, tile), uu in zip(chunk, wino.transform_weights_multi(chunk)):
-            out[(w.data_ptr(), tuple(w.shape), tile)] = uu
-    return out
-
-
-class wino_preloaded:
-    """with wino_preloaded(d): the passes inside take their filter transforms from `d` (wino_pretransform) instead of launching them"""
-
-    def __init__(self, d):
-        self.d = d
-
-    def __enter__(self):
-        self.prev, _wino_scope["preloaded"] = _wino_scope["preloaded"], self.d
-
-    def __exit__(self, *a):
-        _wino_scope["preloaded"] = self.prev
 _WINO_MULTI = _os_environ_get("OMNI_WINO_WEIGHTS_MULTI", "1") != "0"          # A/B knob
 
 
@@ -674,10 +497,7 @@ class wino_weight_scope:
         _wino_scope["record"] = []
         self.kind = "_omni_wino_plan_train" if torch.is_grad_enabled() else "_omni_wino_plan_infer"
         plan = getattr(self.owner, self.kind, None) if (self.owner is not None and _WINO_MULTI) else None
-        pre = _wino_scope["preloaded"]
-        if pre is not None and self.kind == "_omni_wino_plan_train":
-            cache.update(pre)
-        elif plan:
+        if plan:
             items = [(w, True, flip, tile) for w, tile, flip in plan if w.is_contiguous(memory_format=CL)]
             for k in range(0, len(items), wino.WEIGHTS_MULTI_MAX):
                 chunk = items[k:k + wino.WEIGHTS_MULTI_MAX]
@@ -702,11 +522,6 @@ class wino_weight_scope:
 
 
 _WINOGRAD = _os_environ_get("OMNI_WINOGRAD", "1") != "0"
-# The RPN's shared 3x3 over all FPN levels through one GEMM per direction (conv3x3_levels).  MEASURED and left OFF for training
-# (profiles/r04_ab_wino_levels.log: 11.33-11.35 ms with, 11.25-11.34 without -- the p4..p6 GEMMs it absorbs are paid back by 36-point
-# transforms on the 16x16 / 8x8 maps and a third more rows in the p2 launch; inference: 623 against 616 images/s, but the smallest
-# levels change from the direct kernel to the transform and one reference-written inference fixture flips a detection on it).
-_WINO_LEVELS = _os_environ_get("OMNI_WINO_LEVELS", "0")               # "1" always | "0" never | "infer": eval mode only
 
 
 def conv2d(x, w, bias=None, stride=1, pad=0, relu=False, want_stats=False):
@@ -818,94 +633,6 @@ def fused_linear(x, weights, biases, rows, relu=False):
     w = torch.cat(list(weights) + ([weights[0].new_zeros(pad, cols)] if pad else []), dim=0)
     b = torch.cat(list(biases) + ([biases[0].new_zeros(pad)] if pad else []), dim=0)
     return _Linear.apply(x, w, b, relu, None, None)
-
-
-def _wino_weights(w, tile, need_flip):
-    """(U, U') of filter `w` through the pass's cache (wino_weight_scope), recording a miss for the next pass's batched launch"""
-    key = (w.data_ptr(), tuple(w.shape), tile)
-    cache = _wino_scope["cache"]
-    U, Uf = cache.get(key, (None, None)) if cache is not None else (None, None)
-    if U is None or (need_flip and Uf is None):
-        U, Uf = wino.transform_weights(w, True, need_flip or Uf is not None, tile)
-        if cache is not None:
-            cache[key] = (U, Uf)
-            _wino_scope["record"].append((w, tile, bool(need_flip or Uf is not None)))
-    return U, Uf
-
-
-class _BNReLUWinoConv(Function):
-    """conv -> BatchNorm -> ReLU -> 3x3 convolution with the normalised activation never materialised (the inside of every DLA /
-    torchvision BasicBlock, /root/reference/cubercnn/modeling/backbone/dla.py:60-66): x is the RAW output of the first convolution with
-    its epilogue statistics; BatchNorm's finalize turns them into (scale, shift), and the Winograd input transform of the second
-    convolution applies scale / shift / ReLU while it loads its tiles (omni_wino_in_affine).  Saves the write and the read of the
-    normalised tensor and one launch per block; the backward pass is the two layers' usual kernels (the BatchNorm's ReLU mask is
-    recomputed from x, so nothing needed the normalised tensor anyway)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, partials, w, want_stats):
-        ctx.set_materialize_grads(False)
-        gg, gb = _direct_grad(gamma), _direct_grad(beta)
-        ctx.bn_direct = (gg, gb) if (gg is not None and gb is not None) else None
-        ctx.w_direct = _direct_grad(w)
-        x, w = _cl(x), _cl(w)
-        mean_rstd, scale_shift = bnpool.bn_finalize_fwd(x, gamma, beta, running_mean, running_var, partials, eps, momentum)
-        tile = wino.tile_size(x.shape)
-        need_flip = wino.dgrad_eligible(x.shape)
-        U, Uf = _wino_weights(w, tile, need_flip)
-        parts = None
-        if want_stats:
-            y, V, parts = wino.conv3x3_fwd(x, w, None, False, U=U, tile=tile, want_stats=True, in_affine=scale_shift, in_relu=True)
-        else:
-            y, V = wino.conv3x3_fwd(x, w, None, False, U=U, tile=tile, in_affine=scale_shift, in_relu=True)
-        ctx.save_for_backward(x, gamma, mean_rstd, scale_shift, V, w, Uf if need_flip else None)
-        parts = _parts_out(parts, y)
-        ctx.mark_non_differentiable(parts)
-        return y, parts
-
-    @staticmethod
-    def backward(ctx, dy, _parts_grad=None):
-        x, gamma, mean_rstd, scale_shift, V, w, Uf = ctx.saved_tensors
-        dy = _cl(dy)
-        gw = ctx.w_direct
-        if gw is not None and not gw.is_contiguous(memory_format=CL):
-            gw = None
-        # the second convolution: data gradient (= the gradient of the normalised activation) and weight gradient
-        if wino.dgrad_eligible(dy.shape):
-            dmid, dw = wino.conv3x3_backward(V, dy, w, Uf, accum_into=gw, side_run=_side_run)
-        else:
-            dmid = conv.conv2d_dgrad(dy, w, (dy.shape[2], dy.shape[3]), 1, 1)
-            dw = _side_run(lambda: wino.conv3x3_wgrad(V, dy, accum_into=gw), (V, dy)) if gw is not None else wino.conv3x3_wgrad(V, dy)
-        # the BatchNorm + ReLU: mask recomputed from x and (scale, shift)
-        dx, _, dgamma, dbeta = bnpool.bn_bwd(x, dmid, None, gamma, mean_rstd, True, want_dres=False, accum_into=ctx.bn_direct,
-                                             scale_shift=scale_shift)
-        return dx, dgamma, dbeta, None, None, None, None, None, dw, None
-
-
-# OFF by default: measured SLOWER on the DLA-34 step (11.93 / 11.95 ms with, 11.89 without; profiles/r03_ab_bn_wino_fuse.log): the input
-# transform reads every activation 2.25 times (overlapping 6x6 windows) and now normalises it 2.25 times, with 8 more live registers
-# next to its 144-register tile -- that costs more than the 5 us bn_apply launch and the 2 x 4-17 MB it saves
-_BN_WINO_FUSE = _os_environ_get("OMNI_BN_WINO_FUSE", "0") != "0"      # A/B knob
-_BN_WINO_FUSE_MAX_PIX = int(_os_environ_get("OMNI_BN_WINO_FUSE_MAX_PIX", str(1 << 30)))     # ... only on maps of at most this many pixels
-
-
-def bn_relu_conv3x3(x, bn, conv_mod, want_stats):
-    """`conv_mod(bn(x, relu=True))` for a 3x3 / stride 1 / pad 1 / bias-free `conv_mod` (layers.Conv2d) behind a training-mode
-    BatchNorm `bn` (layers.BatchNorm2d) whose input `x` carries its producer's epilogue statistics: fused when the convolution takes
-    the Winograd path, the plain two-module sequence otherwise."""
-    w = conv_mod.weight
-    parts = getattr(x, "_omni_bn_partials", None)
-    if (_BN_WINO_FUSE and _WINOGRAD and parts is not None and bn.training and torch.is_grad_enabled() and conv_mod.bias is None
-            and conv_mod.stride[0] == 1 and conv_mod.padding[0] == 1 and w.requires_grad and x.requires_grad
-            and wino.eligible(x.shape, w.shape, 1, 1) and _BN_REMASK and w.is_contiguous(memory_format=CL)
-            and x.shape[0] * x.shape[2] * x.shape[3] <= _BN_WINO_FUSE_MAX_PIX):
-        y, p2 = _BNReLUWinoConv.apply(x, bn.weight, bn.bias, bn.running_mean if bn.track_running_stats else None,
-                                      bn.running_var if bn.track_running_stats else None, bn.eps, bn.momentum, parts, w, bool(want_stats))
-        if bn.track_running_stats and bn.num_batches_tracked is not None and not bn.defer_counter:
-            bn.num_batches_tracked += 1
-        if p2.shape[0] > 0:
-            y._omni_bn_partials = p2
-        return y
-    return conv_mod(bn(x, relu=True))
 
 
 _BN_REMASK = _os_environ_get("OMNI_BN_REMASK", "1") != "0"     # A/B knob
@@ -1409,12 +1136,11 @@ class _RPNLoss(Function):
     @staticmethod
     def forward(ctx, anchors, labels, matched_idx, gt, gt_off, inv_norm, weights, plain, *levels):
         ctx.set_materialize_grads(False)      # no zero tensors for the non-differentiable side outputs
-        with forked():                        # (behind the labelling, beside the proposal selection: see set_branch_stream)
-            lv = [_cl(t).permute(0, 2, 3, 1) for t in levels]
-            pack = det.LevelPack(lv)
-            sums = det.rpn_loss_fwd(pack, anchors, labels, matched_idx, gt, gt_off, plain)
-            # (fp64 sums x fp64 coefficients, rounded once into the fp32 loss vector: one launch)
-            vec = glue.scale_vec(sums, (inv_norm * weights[0], inv_norm * weights[1]), n=2)
+        lv = [_cl(t).permute(0, 2, 3, 1) for t in levels]
+        pack = det.LevelPack(lv)
+        sums = det.rpn_loss_fwd(pack, anchors, labels, matched_idx, gt, gt_off, plain)
+        # (fp64 sums x fp64 coefficients, rounded once into the fp32 loss vector: one launch)
+        vec = glue.scale_vec(sums, (inv_norm * weights[0], inv_norm * weights[1]), n=2)
         ctx.pack = pack
         ctx.save_for_backward(anchors, labels, matched_idx, gt, gt_off)
         ctx.inv_norm, ctx.weights, ctx.plain = inv_norm, weights, plain

@@ -229,80 +229,11 @@ def conv2d_wgrad(x, dy, ksize, stride=1, pad=0, accum_into=None, tile=0):
     if accum_into is not None:
         tgt = accum_into.permute(0, 2, 3, 1)
         assert tgt.is_contiguous() and tgt.shape == (K, R, S, C)
-        if tile == 0 and R == S and _defer_direct((xv, dyv, tgt, N, H, W, C, K, R, stride, pad, None)):
-            return None           # (inside wino.batched_wgrads(): leaves with the stage's other direct weight gradients in one launch)
         _wgrad_launch(L, _lib.ptr(xv), _lib.ptr(dyv), _lib.ptr(tgt), N, H, W, C, K, R, S, stride, pad, C, K, 1, tile, x)
         return None
     dw = torch.empty((K, R, S, C), dtype=torch.float32, device=x.device)
     _wgrad_launch(L, _lib.ptr(xv), _lib.ptr(dyv), _lib.ptr(dw), N, H, W, C, K, R, S, stride, pad, C, K, 0, tile, x)
     return dw.permute(0, 3, 1, 2)
-
-
-# The stage's direct weight gradients in ONE launch.  MEASURED and left OFF (OMNI_WGRAD_BATCH=1 enables it):
-# 10.85 / 10.84 ms with it against 10.83 / 10.80 ms without on one box (profiles/r06_ab_wgrad_batch.log) -- unlike the Winograd-domain
-# GEMMs (0.23 -> 0.66 of peak from the same move in round 4) these launches are not short of workgroups: each already spreads ~1024
-# of them over a split reduction, and what holds them at 0.25 of peak is the operand path of the 128 x 64 tile (PMC: MFMA-busy 0.26),
-# which a shared launch does not change.  Results are bit-identical either way (tests/test_conv.py::test_wgrad_batch_*).
-WGRAD_BATCH = os.environ.get("OMNI_WGRAD_BATCH", "0") == "1"
-_direct_deferred = None        # list while wino.batched_wgrads() is open (the weight-gradient stream's capture of one backward stage)
-
-
-def _defer_direct(item):
-    """queue an accumulating direct weight gradient (x, dy, dw view, N, H, W, C, K, R, stride, pad, sources or None) for the
-    stage's multi-problem launch; False = not inside the context (or switched off): the caller launches it itself"""
-    if _direct_deferred is None or not WGRAD_BATCH or not _det.on():
-        return False
-    _direct_deferred.append(item)
-    return True
-
-
-def open_direct_batch():
-    global _direct_deferred
-    prev, _direct_deferred = _direct_deferred, []
-    return prev
-
-
-def close_direct_batch(prev, launch=True):
-    """launch what was queued (omni_conv2d_wgrad_batch_det) and restore the enclosing state"""
-    global _direct_deferred
-    items, _direct_deferred = _direct_deferred, prev
-    if launch and items:
-        conv2d_wgrad_batch(items)
-
-
-def conv2d_wgrad_batch(items):
-    """items: [(x NHWC, dy NHWC, dw KRSC view to ADD into, N, H, W, C, K, R, stride, pad, [source NHWC tensors] or None)] -> every dw
-    += its weight gradient, in one launch per tile shape (csrc/conv_gemm.hip conv_wgrad_multi_kernel); bit-identical to
-    conv2d_wgrad(accum_into=...) / conv1x1_multi_wgrad(accum_into=...) on each.  Two items that add into the same view never share a
-    launch (their order would be the hardware's): the second one starts a new batch."""
-    import ctypes
-    batch, seen, rest = [], set(), []
-    for it in items:
-        (rest if it[2].data_ptr() in seen else batch).append(it)
-        seen.add(it[2].data_ptr())
-    n = len(batch)
-    L = _lib.check_device(*[t for it in batch for t in it[:3]])
-    P = ctypes.c_void_p
-    arr = lambda vals: ctypes.cast((P * len(vals))(*vals), P)                     # noqa: E731
-    ints = lambda vals: ctypes.cast((ctypes.c_int * len(vals))(*[int(v) for v in vals]), P)         # noqa: E731
-    xs_flat, cs_flat, nsrc = [], [], []
-    for it in batch:
-        src = it[11] or []
-        nsrc.append(len(src))
-        xs_flat += [t.data_ptr() for t in src] + [0] * (6 - len(src))
-        cs_flat += [int(t.shape[3]) for t in src] + [0] * (6 - len(src))
-    head = (arr([it[0].data_ptr() for it in batch]), arr([it[1].data_ptr() for it in batch]), arr([it[2].data_ptr() for it in batch]),
-            ints([it[3] for it in batch]), ints([it[4] for it in batch]), ints([it[5] for it in batch]), ints([it[6] for it in batch]),
-            ints([it[7] for it in batch]), ints([it[8] for it in batch]), ints([it[9] for it in batch]), ints([it[10] for it in batch]),
-            ints([1] * n), arr(xs_flat), ints(cs_flat), ints(nsrc), n)
-    like = batch[0][1]
-    st = _lib.stream_of(like)
-    plan, paddr = _det.new_plan()
-    L.call("omni_conv2d_wgrad_batch_det", *head, None, 0, None, 0, paddr, st)
-    ws, wsf, ctr, nctr = _det.workspace(like, plan)
-    L.call("omni_conv2d_wgrad_batch_det", *head, _lib.ptr(ws), wsf, _lib.ptr(ctr), nctr, None, st)
-    if rest:
-        conv2d_wgrad_batch(rest)
 
 
 def conv1x1_multi_wgrad(xs, dy, accum_into=None, tile=0):
@@ -320,8 +251,6 @@ def conv1x1_multi_wgrad(xs, dy, accum_into=None, tile=0):
     if accum_into is not None:
         tgt = accum_into.permute(0, 2, 3, 1)
         assert tgt.is_contiguous() and tgt.shape == (K, 1, 1, C)
-        if tile == 0 and n <= 6 and _defer_direct((xv[0], dyv, tgt, N, H, W, C, K, 1, 1, 0, xv)):
-            return None
         dw, acc = tgt, 1
     else:
         dw, acc = torch.empty((K, 1, 1, C), dtype=torch.float32, device=dyv.device), 0
@@ -371,10 +300,6 @@ _FC_BALANCED = os.environ.get("OMNI_FC_BALANCED", "1") != "0"
 # registers can start anywhere on the chip, and the main stream's next kernels (wino4_out: 254 VGPRs) waited out its 550 us
 # (gpurun_out/r05a_timeline.txt; VERDICT r4 weak 3 saw the same stall).  The tile kernel (152 registers, 49 KB of LDS, non-persistent)
 # is slower in isolation and shares the CUs: 10.85 -> 10.72 ms / step (profiles/r05_ab_fc1_wgrad.log; engine on 224 workgroups: 10.80).
-# OMNI_FC_WGRAD_ENGINE_MIN_ROWS=1024 restores the engine (A/B knob).
-_FC_WGRAD_ENGINE_MIN_ROWS = int(os.environ.get("OMNI_FC_WGRAD_ENGINE_MIN_ROWS", str(1 << 30)))
-_FC_WGRAD_WGS = int(os.environ.get("OMNI_FC_WGRAD_WGS", "0"))              # persistent workgroups of the engine form (0 = one per CU)
-_FC_WGRAD_SPLITS = int(os.environ.get("OMNI_FC_WGRAD_SPLITS", "-1"))      # -1 = balanced (gemm.BALANCED) | 1 = whole tiles only
 
 
 def linear_dgrad(dy, w):
@@ -400,12 +325,6 @@ def linear_wgrad(x, dy, accum_into=None):
     L = _lib.check_device(x, dy)
     if accum_into is not None:
         assert accum_into.is_contiguous() and accum_into.shape == (K, C)
-        if _FC_BALANCED and M >= _FC_WGRAD_ENGINE_MIN_ROWS and C >= 4096 and K >= 512 and (K % 4) == 0 and (C % 4) == 0:
-            # fc1-class weight gradient dW += dY^T X on the LDS-DMA engine's TN form with the balanced work split: 784 tiles of
-            # 128 x 128 are 3.06 rounds of 256 workgroups -- the plain launch pays 4 (csrc/gemm_engine.hip, BAL)
-            from . import gemm as _gemm
-            _gemm.gemm(dy, x, _gemm.TN, out=accum_into, accumulate=True, tile=2, splits=_FC_WGRAD_SPLITS, workgroups=_FC_WGRAD_WGS)
-            return None
         _wgrad_launch(L, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(accum_into), M, 1, 1, C, K, 1, 1, 1, 0, C, K, 1, 0, x)
         return None
     dw = torch.empty((K, C), dtype=torch.float32, device=x.device)

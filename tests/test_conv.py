@@ -519,114 +519,6 @@ def test_winograd_weights_multi_gpu(hip_lib):
     _run_weight_plan("cuda")
 
 
-def _run_bn_relu_wino_fusion(dev, shapes):
-    """BasicBlock (conv -> BN -> ReLU -> 3x3 conv -> BN + residual + ReLU) with bn1 + ReLU applied inside conv2's Winograd input
-    transform == the unfused sequence: outputs, input / parameter gradients, running statistics, batch counter"""
-    import copy
-    from omni3d_amd import functional as HF
-    from omni3d_amd.cubercnn.modeling.backbone.dla import BasicBlock
-    for (N, C, H, tile) in shapes:
-        torch.manual_seed(C + H)
-        blk = BasicBlock(C, C).to(dev).train()
-        for m in blk.modules():
-            if isinstance(m, torch.nn.BatchNorm2d):
-                m.weight.data.uniform_(0.5, 1.5)
-                m.bias.data.normal_(0, 0.3)
-        x0 = torch.randn(N, C, H, H).contiguous(memory_format=torch.channels_last).to(dev)
-        g = torch.randn(N, C, H, H).contiguous(memory_format=torch.channels_last).to(dev)
-        assert HF.wino.eligible(x0.shape, blk.conv2.weight.shape, 1, 1) and HF.wino.tile_size(x0.shape) == tile
-        res = {}
-        for fused in (True, False):         # (the switch is off by default: measured slower on MI355X; the path stays tested)
-            prev, HF._BN_WINO_FUSE = HF._BN_WINO_FUSE, fused
-            try:
-                b = copy.deepcopy(blk)
-                x = x0.clone().requires_grad_(True)
-                calls = []
-                real = HF.bnpool.bn_finalize_fwd
-                HF.bnpool.bn_finalize_fwd = lambda *a, **k: (calls.append(1), real(*a, **k))[1]
-                try:
-                    y = b(x)
-                finally:
-                    HF.bnpool.bn_finalize_fwd = real
-                assert bool(calls) == fused                      # the fused path really ran (or did not)
-                y.backward(g)
-                HF.side_join()
-                res[fused] = [y.detach(), x.grad] + [p.grad for p in b.parameters()] + [b.bn1.running_mean, b.bn1.running_var,
-                                                                                        b.bn1.num_batches_tracked.float()]
-            finally:
-                HF._BN_WINO_FUSE = prev
-        for i, (a, c) in enumerate(zip(res[True], res[False])):
-            assert (a - c).abs().max() <= 2e-5 * max(1.0, float(c.abs().max())), (C, H, i, float((a - c).abs().max()))
-
-
-def test_bn_relu_winograd_fusion_emulated(emu_lib):
-    _run_bn_relu_wino_fusion("cpu", [(4, 128, 16, 2), (1, 128, 64, 4)])
-
-
-@pytest.mark.gpu
-def test_bn_relu_winograd_fusion_gpu(hip_lib):
-    _run_bn_relu_wino_fusion("cuda", [(4, 128, 64, 4), (4, 256, 32, 4), (4, 512, 16, 2), (4, 64, 128, 4)])
-
-
-# ---- one 3x3 filter over several tensors through shared Winograd arrays (functional._WinoConv3x3Levels) -------------------
-def _run_levels(dev, sizes, tile_expected, N=2, C=128, K=128, seed=3):
-    """the RPN's shared convolution over FPN levels.  (1) without ReLU against torch's conv2d on every level: outputs, input gradients
-    (level 0 has a second consumer), filter and bias gradients.  (2) with ReLU against the per-level path of the same kernels on the
-    levels that take the same transform there: a ReLU mask flips wherever an output is within rounding of zero, so only two paths with
-    the same arithmetic can be compared through it."""
-    from omni3d_amd import functional as HF
-    from omni3d_amd.kernels import wino
-    g = torch.Generator().manual_seed(seed)
-    cl = lambda t: t.contiguous(memory_format=torch.channels_last)  # noqa: E731
-    xs = [torch.randn(N, C, h, w_, generator=g) for h, w_ in sizes]
-    w = torch.randn(K, C, 3, 3, generator=g) * 0.05
-    b = torch.randn(K, generator=g) * 0.1
-    dys = [torch.randn(N, K, h, w_, generator=g) for h, w_ in sizes]
-    xr = [x.clone().requires_grad_(True) for x in xs]
-    wr, br = w.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    ref = [F.conv2d(x, wr, br, padding=1) for x in xr]
-    torch.autograd.backward(ref + [(xr[0] * 0.5).sum()], dys + [torch.ones(())])                 # a second consumer of level 0
-    xd = [cl(x).to(dev).requires_grad_(True) for x in xs]
-    wd, bd = cl(w).to(dev).requires_grad_(True), b.to(dev).requires_grad_(True)
-    assert HF.conv3x3_levels_eligible(xd, wd) and wino.levels_tile([tuple(x.shape) for x in xd]) == tile_expected
-    with HF.wino_weight_scope():
-        ys = HF.conv3x3_levels(xd, wd, bd, relu=False)
-    torch.autograd.backward(ys + [(xd[0] * 0.5).sum()], [cl(d).to(dev) for d in dys] + [torch.ones((), device=dev)])
-    tol = 2e-3 if tile_expected == 4 else 5e-4
-    for y, r in zip(ys, ref):
-        assert (y.detach().cpu() - r.detach()).abs().max() <= tol * float(r.detach().abs().max())
-    for a, r in zip(xd, xr):
-        assert (a.grad.cpu() - r.grad).abs().max() <= tol * float(r.grad.abs().max())
-    assert (wd.grad.cpu() - wr.grad).abs().max() <= tol * float(wr.grad.abs().max())
-    assert (bd.grad.cpu() - br.grad).abs().max() <= 1e-4 * float(br.grad.abs().max())
-    # (2) ReLU: the same tensors through both forms
-    import contextlib
-    xa = [cl(x).to(dev).requires_grad_(True) for x in xs]
-    xb = [cl(x).to(dev).requires_grad_(True) for x in xs]
-    with HF.wino_weight_scope():
-        ya = HF.conv3x3_levels(xa, wd, bd, relu=True)
-    with (wino.f22_only() if tile_expected == 2 else contextlib.nullcontext()), HF.wino_weight_scope():
-        same = [l for l, x in enumerate(xb) if wino.eligible(tuple(x.shape), tuple(wd.shape), 1, 1) and wino.tile_size(tuple(x.shape)) == tile_expected]
-        yb = {l: HF.conv2d(xb[l], wd, bd, 1, 1, relu=True) for l in same}
-    assert same, "no level takes the same transform on the per-level path"
-    torch.autograd.backward(ya, [cl(d).to(dev) for d in dys])
-    torch.autograd.backward([yb[l] for l in same], [cl(dys[l]).to(dev) for l in same])
-    for l in same:
-        assert torch.equal(ya[l].detach(), yb[l].detach()), l                    # same arithmetic per output row
-        assert (xa[l].grad - xb[l].grad).abs().max() <= 1e-5 * float(xb[l].grad.abs().max()), l
-
-
-def test_wino_levels_emulated(emu_lib):
-    _run_levels("cpu", [(16, 24), (8, 12), (4, 8)], 2, N=4)      # 128 tiles of 4x4 are below the 36-point transform's floor: 16-point
-    _run_levels("cpu", [(32, 32), (16, 16), (8, 8), (4, 4)], 4, N=4)
-
-
-@pytest.mark.gpu
-def test_wino_levels_gpu(hip_lib):
-    _run_levels("cuda", [(128, 128), (64, 64), (32, 32), (16, 16), (8, 8)], 4, N=4, C=256, K=256)      # the benchmark's five levels
-    _run_levels("cuda", [(64, 96), (32, 48), (16, 24), (8, 12), (4, 6)], 2, N=2, C=256, K=256)         # p6 of 4 x 6: 16-point transform
-
-
 def test_collected_weight_gradients_emulated(emu_lib):
     """what solver/graphed.py does with a backward stage's weight-gradient closures, without the graphs: in side_mode("collect") the
     backward of Winograd / direct / linear layers only QUEUES its filter- and bias-gradient launches; run afterwards inside
@@ -783,60 +675,6 @@ def test_conv1x1_multi_source_gpu(hip_lib):
     _run_multi_src("cuda", [(4, 128, 128, (64, 64), 64, 0, 0), (4, 64, 64, (128, 128), 128, 0, 0), (4, 64, 64, (128, 128, 64, 128), 128, 0, 0),
                             (4, 32, 32, (256, 256), 256, 0, 0), (4, 32, 32, (256, 256, 128, 256), 256, 0, 0), (4, 16, 16, (512, 512, 256), 512, 0, 0)]
                    + MULTI_SRC_SMALL)
-
-
-def _run_wgrad_batch(dev, big=False):
-    """round 6: the direct weight gradients of a backward stage in one launch (conv_wgrad_multi_kernel) are bit-identical to their own
-    launches -- 1 x 1, stride-2 3 x 3, the DLA Root's multi-source 1 x 1, mixed tile shapes, two problems adding into one view"""
-    from omni3d_amd.kernels import conv, wino
-    g = torch.Generator().manual_seed(21)
-    CL = torch.channels_last
-
-    def rnd(*shape):
-        return torch.randn(*shape, generator=g).contiguous(memory_format=CL).to(dev)
-    s = 4 if big else 1
-    # (N, C, H, W, K, R, stride, pad)
-    cases = [(2, 64, 16 * s, 16 * s, 128, 1, 1, 0), (2, 32, 16 * s, 16 * s, 64, 3, 2, 1), (1, 128, 8 * s, 8 * s, 256, 1, 1, 0),
-             (2, 64, 12 * s, 12 * s, 64, 3, 2, 1), (2, 16, 16 * s, 16 * s, 32, 3, 2, 1), (1, 256, 8 * s, 8 * s, 256, 1, 1, 0)]
-    probs = []
-    for N, C, H, W, K, R, st, pad in cases:
-        OH = (H + 2 * pad - R) // st + 1
-        probs.append((rnd(N, C, H, W), rnd(N, K, OH, OH), (R, R), st, pad))
-    xs = [rnd(2, 32, 8 * s, 8 * s), rnd(2, 64, 8 * s, 8 * s), rnd(2, 32, 8 * s, 8 * s)]
-    dy_ms = rnd(2, 64, 8 * s, 8 * s)
-
-    def grads():
-        return ([torch.full((dy.shape[1], x.shape[1], k[0], k[1]), 0.5).contiguous(memory_format=CL).to(dev) for x, dy, k, _, _ in probs]
-                + [torch.full((64, 128, 1, 1), 0.25).contiguous(memory_format=CL).to(dev)])
-
-    def issue(into):
-        for (x, dy, k, st, pad), gw in zip(probs, into):
-            conv.conv2d_wgrad(x, dy, k, st, pad, accum_into=gw)
-        conv.conv1x1_multi_wgrad(xs, dy_ms, accum_into=into[-1])
-        conv.conv2d_wgrad(probs[0][0], probs[0][1], probs[0][2], probs[0][3], probs[0][4], accum_into=into[0])       # the same view once more
-    one = grads()
-    issue(one)                                   # every problem its own launch
-    many = grads()
-    prev, conv.WGRAD_BATCH = conv.WGRAD_BATCH, True          # (measured neutral in the step and left off by default: kernels/conv.py)
-    with wino.batched_wgrads():                  # the weight-gradient stream's context: everything leaves when it closes
-        issue(many)
-        assert all(torch.equal(a, b) for a, b in zip(many, grads()))          # nothing launched yet
-    conv.WGRAD_BATCH = prev
-    for a, b in zip(one, many):
-        assert torch.equal(a.cpu(), b.cpu())
-    # and against the plain sum: dw of a fresh buffer
-    ref0 = conv.conv2d_wgrad(probs[1][0], probs[1][1], probs[1][2], probs[1][3], probs[1][4])
-    assert (many[1].cpu() - 0.5 - ref0.cpu()).abs().max() <= 1e-4 * float(ref0.abs().max())
-
-
-def test_wgrad_batch_emulated(emu_lib):
-    _run_wgrad_batch("cpu")
-
-
-@pytest.mark.gpu
-def test_wgrad_batch_gpu(hip_lib):
-    _run_wgrad_batch("cuda")
-    _run_wgrad_batch("cuda", big=True)
 
 
 def _run_s2_dgrad(dev, cases):

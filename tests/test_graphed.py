@@ -1,6 +1,8 @@
 """hipGraph replay of the training step (cubercnn/solver/graphed.py) must reproduce eager launches.  Regression for the
 ROCm 7.2 finding that hipMemsetAsync nodes are not replayed correctly inside captured graphs (split-K / atomic
 accumulators stayed dirty from the second replay on): every clear in the library is a fill kernel now."""
+import math
+
 import pytest
 import torch
 
@@ -97,6 +99,48 @@ def test_pipelined_graphs_match_eager_while_the_weights_move(hip_lib):
             opt.step()
     finally:
         HF.side_mode(prev_mode)
+        stepper.uninstall()
+
+
+@pytest.mark.gpu
+def test_failed_stage0_capture_ends_the_open_capture(hip_lib, monkeypatch):
+    """An error raised inside the stage-0 capture after the labels split reaches the caller, and the graph that was still capturing
+    is ended: the next eager step and the next capture of the same model both work."""
+    from omni3d_amd.cubercnn.solver import graphed
+    model, opt, batch, packed = _setup()
+    real = graphed.GraphedPipelined._stage0
+    split_calls = []
+
+    def failing(self):
+        rpn = self.model.proposal_generator
+        hook = rpn.__dict__.get("_label_split")
+        if hook is None:                    # warm-up steps
+            return real(self)
+        rpn.__dict__["_label_split"] = lambda: (split_calls.append(1), hook())[1]
+        real(self)
+        raise RuntimeError("injected failure after the labels split")
+
+    monkeypatch.setattr(graphed.GraphedPipelined, "_stage0", failing)
+    with pytest.raises(RuntimeError, match="injected failure"):
+        graphed.GraphedPipelined(model, opt, batch, packed)
+    monkeypatch.undo()
+    assert split_calls, "the capture never reached the labels split"
+    assert not torch.cuda.is_current_stream_capturing()
+    with torch.cuda.stream(graphed.lean_capture._stream):        # (the stream stage 0 is captured on)
+        assert not torch.cuda.is_current_stream_capturing()
+
+    eager = graphed.GraphedPipelined(model, opt, batch, packed, graphs=False)
+    _, total, _ = eager()
+    torch.cuda.synchronize()
+    assert math.isfinite(float(total))
+
+    stepper = graphed.GraphedPipelined(model, opt, batch, packed)
+    try:
+        assert stepper.prologue is not None            # (stage 0 captured with the labels split)
+        _, total, _ = stepper()
+        torch.cuda.synchronize()
+        assert math.isfinite(float(total))
+    finally:
         stepper.uninstall()
 
 
