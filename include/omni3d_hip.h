@@ -165,6 +165,22 @@ int omni_bn_bwd_algo(const float* x, const float* dy, long long lddy, const floa
 int omni_bn_apply(const float* x, const float* scale_shift, const float* residual, float* y, int P, int C,
                   int relu, void* stream);
 
+/* frozen BatchNorm WITH gradients: the eval-mode BatchNorm2d of a training pass after freeze_bn (tools/train_net.py:150-151, :297-298;
+ * cubercnn/solver/build.py:71-76), MODEL.USE_BN False (cubercnn/config/config.py:82).  Forward y = relu?(x * s + t (+ residual)),
+ * s = gamma * rsqrt(running_var + eps), t = beta - running_mean * s made inside the launch from the live tensors (no host cache: a
+ * captured graph reads the current parameters on every replay); the same bits as omni_bn_apply with the eval-mode (scale, shift).
+ * Backward, g = dy masked by the ReLU (relu 0: none | 1: y > 0, y = the forward output | 2: x * s + t > 0 recomputed, forward
+ * without residual, y unused): dx = g * s, dres = g + res_carry [dres, res_carry nullable; pitch ldc], dbeta = sum g,
+ * dgamma = sum g * (x - running_mean) * rsqrt(running_var + eps) -- written, or added (accumulate_param_grads) to dgamma / dbeta
+ * (both NULL: not computed).  dy with pixel pitch lddy.  One pass + a fixed-order finalize, no atomics: run-to-run identical.
+ * ws >= 2 * C * 512 floats.  Running statistics are never written. */
+int omni_bn_frozen_fwd(const float* x, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                       float eps, const float* residual, float* y, int P, int C, int relu, void* stream);
+int omni_bn_frozen_bwd(const float* x, const float* dy, long long lddy, const float* y, const float* gamma, const float* beta,
+                       const float* running_mean, const float* running_var, float eps, float* dx, float* dres, const float* res_carry,
+                       long long ldc, float* dgamma, float* dbeta, float* ws, long long ws_floats, int P, int C, int relu,
+                       int accumulate_param_grads, void* stream);
+
 /* backward of omni_bn_fwd.  dy = grad wrt y; dres [nullable] = grad wrt residual;
  * ws >= 2C*258 doubles, coef 3C floats scratch.  relu: 0 = none; 1 = mask dy by y > 0, y = the forward output;
  * 2 = layers without residual: `y` points at the forward pass's scale_shift (2C floats) and the mask is recomputed as

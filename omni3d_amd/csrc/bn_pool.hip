@@ -437,6 +437,141 @@ __global__ void __launch_bounds__(256) bn_fin_bwd_apply_kernel(const float* __re
     }
 }
 
+// ---- frozen BatchNorm with gradients (eval mode inside a training pass: MODEL.USE_BN False / freeze_bn) -----------------------
+// Per channel s = gamma * rsqrt(running_var + eps), t = beta - running_mean * s, computed INSIDE the launch from the live parameters
+// and buffers (a captured graph reads them on every replay), with the arithmetic of the eval-mode cache in layers.py: the same
+// rsqrt as torch's on this device, no FMA contraction of `beta - mean * s`, so the forward output equals the eval-mode output bit
+// for bit.  Forward y = relu?(x * s + t (+ residual)); backward with g = dy masked by the ReLU: dx = g * s, dres = g (+ carry),
+// dbeta = sum g, dgamma = sum g * (x - mean) * rsqrt(var + eps).  Running statistics are never written.
+// Work items are (channel group of GC = 16 channels, pixel chunk) in fin_item's XCD-contiguous order; a thread owns ONE channel quad
+// for its whole chunk, so the coefficients are made once per thread.  C % 16 != 0 (ShuffleNet's 58 -> 60 padded channels): the last
+// group's quads past C idle.
+__device__ __forceinline__ float frozen_rsqrt(float v) {
+#ifdef OMNI_HIPEMU
+    return 1.f / sqrtf(v);      // torch's CPU rsqrt
+#else
+    return rsqrtf(v);           // torch's GPU rsqrt (ocml)
+#endif
+}
+__device__ __forceinline__ void frozen_coef(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                            const float* __restrict__ running_mean, const float* __restrict__ running_var, float eps,
+                                            long c, float4& sc, float4& sh, float4& mu, float4& rs) {
+#pragma clang fp contract(off)
+    const float4 g = ld4(gamma + c), b = ld4(beta + c), v = ld4(running_var + c);
+    mu = ld4(running_mean + c);
+    rs = make_float4(frozen_rsqrt(v.x + eps), frozen_rsqrt(v.y + eps), frozen_rsqrt(v.z + eps), frozen_rsqrt(v.w + eps));
+    sc = make_float4(g.x * rs.x, g.y * rs.y, g.z * rs.z, g.w * rs.w);
+    const float4 ms = make_float4(mu.x * sc.x, mu.y * sc.y, mu.z * sc.z, mu.w * sc.w);
+    sh = make_float4(b.x - ms.x, b.y - ms.y, b.z - ms.z, b.w - ms.w);
+}
+
+__global__ void __launch_bounds__(256) bn_frozen_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, const float* __restrict__ running_mean,
+                                                            const float* __restrict__ running_var, float eps,
+                                                            const float* __restrict__ residual, float* __restrict__ y, int P, int C,
+                                                            int relu, int CG, int PC, int chunk) {
+    int cg, pc;
+    if (!fin_item(CG, PC, cg, pc)) return;
+    const int t = threadIdx.x, col = t & (GQ - 1), prow = t >> 2;
+    const long coff = (long)cg * GC + 4 * col;
+    if (coff >= C) return;              // (no barrier below)
+    float4 sc, sh, mu, rs;
+    frozen_coef(gamma, beta, running_mean, running_var, eps, coff, sc, sh, mu, rs);
+    const long pend = min((long)P, (long)(pc + 1) * chunk);
+    long p = (long)pc * chunk + prow;
+    // (the expression of bn_apply_body: the same bits as the eval-mode path)
+    for (; p + 192 < pend; p += 256) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = ld4(x + (p + 64 * u) * C + coff) * sc + sh;
+        if (residual != nullptr) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = v[u] + ld4(residual + (p + 64 * u) * C + coff);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) st4(y + (p + 64 * u) * C + coff, relu ? relu4(v[u]) : v[u]);
+    }
+    for (; p < pend; p += 64) {
+        float4 v = ld4(x + p * C + coff) * sc + sh;
+        if (residual != nullptr) v = v + ld4(residual + p * C + coff);
+        st4(y + p * C + coff, relu ? relu4(v) : v);
+    }
+}
+
+// relu: 0 none | 1 mask by y > 0 (y = the forward output) | 2 mask recomputed as x * s + t > 0 (forward without residual; y unused).
+// partial [nullable]: [PC][2][C] floats, this launch's per-chunk (sum g, sum g * xhat); NULL = no parameter gradients wanted.
+__global__ void __launch_bounds__(256) bn_frozen_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, long lddy,
+                                                            const float* __restrict__ y, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, const float* __restrict__ running_mean,
+                                                            const float* __restrict__ running_var, float eps, float* __restrict__ dx,
+                                                            float* __restrict__ dres, const float* __restrict__ res_carry, long ldc,
+                                                            float* __restrict__ partial, int P, int C, int relu, int CG, int PC,
+                                                            int chunk) {
+    int cg, pc;
+    if (!fin_item(CG, PC, cg, pc)) return;
+    __shared__ float4 s0[256], s1[256];
+    const int t = threadIdx.x, col = t & (GQ - 1), prow = t >> 2;
+    const long coff = (long)cg * GC + 4 * col;
+    const bool active = coff < C;
+    float4 a0 = f4(0.f), a1 = f4(0.f);
+    if (active) {
+        float4 sc, sh, mu, rs;
+        frozen_coef(gamma, beta, running_mean, running_var, eps, coff, sc, sh, mu, rs);
+        const long pend = min((long)P, (long)(pc + 1) * chunk);
+        for (long p = (long)pc * chunk + prow; p < pend; p += 128) {
+            // two pixels per trip: up to 8 independent loads in flight per lane
+            const long p1 = p + 64;
+            const bool two = p1 < pend;
+            float4 g0 = ld4(dy + p * lddy + coff), g1 = two ? ld4(dy + p1 * lddy + coff) : f4(0.f);
+            const float4 x0 = ld4(x + p * C + coff), x1 = two ? ld4(x + p1 * C + coff) : f4(0.f);
+            if (relu == 1) {
+                g0 = mask4(g0, ld4(y + p * C + coff));
+                if (two) g1 = mask4(g1, ld4(y + p1 * C + coff));
+            } else if (relu == 2) {
+                g0 = mask4(g0, x0 * sc + sh);
+                g1 = mask4(g1, x1 * sc + sh);
+            }
+            if (dres != nullptr) {
+                st4(dres + p * C + coff, res_carry != nullptr ? g0 + ld4(res_carry + p * ldc + coff) : g0);
+                if (two) st4(dres + p1 * C + coff, res_carry != nullptr ? g1 + ld4(res_carry + p1 * ldc + coff) : g1);
+            }
+            st4(dx + p * C + coff, g0 * sc);
+            if (two) st4(dx + p1 * C + coff, g1 * sc);
+            a0 = a0 + g0;
+            a1 = a1 + g0 * ((x0 - mu) * rs);
+            if (two) {
+                a0 = a0 + g1;
+                a1 = a1 + g1 * ((x1 - mu) * rs);
+            }
+        }
+    }
+    if (partial == nullptr) return;     // (uniform over the workgroup)
+    s0[t] = a0;
+    s1[t] = a1;
+    __syncthreads();
+    // fixed tree over the 64 pixel rows of the workgroup: deterministic
+    for (int half = 32; half >= 1; half >>= 1) {
+        if (prow < half) { s0[t] = s0[t] + s0[t + half * GQ]; s1[t] = s1[t] + s1[t + half * GQ]; }
+        __syncthreads();
+    }
+    if (prow == 0 && active) {
+        st4(partial + (long)pc * 2 * C + coff, s0[t]);
+        st4(partial + (long)pc * 2 * C + C + coff, s1[t]);
+    }
+}
+
+// dbeta / dgamma of the frozen backward: the PC partial rows summed in fp64 in colsum_fin's fixed order (written, or added to what the
+// buffers hold -- the parameters' views of the flat gradient bucket); one workgroup per FIN_C channels
+__global__ void __launch_bounds__(256) bn_frozen_bwd_fin_kernel(const float* __restrict__ partial, int nblk, int C, float* __restrict__ dgamma,
+                                                                float* __restrict__ dbeta, int accumulate) {
+    double db, dg;
+    colsum_fin(partial, nblk, C, blockIdx.x * FIN_C, db, dg);
+    const int c = blockIdx.x * FIN_C + threadIdx.x;
+    if (threadIdx.x >= FIN_C || c >= C) return;
+    dbeta[c] = accumulate ? dbeta[c] + (float)db : (float)db;
+    dgamma[c] = accumulate ? dgamma[c] + (float)dg : (float)dg;
+}
+
 #ifndef OMNI_HIPEMU
 // (A one-launch BatchNorm -- statistics, finalize and apply separated by grid-wide barriers built on agent-scope atomics -- was
 // built and measured in round 2: inside a hipGraph a dependent launch costs ~2.8 us on MI355X while a grid barrier across the
@@ -696,8 +831,9 @@ extern "C" {
 
 // pixel chunks of the fused finalize + apply launches: ~2 workgroups per CU over (channel groups x chunks), chunks of >= 64 pixels
 // that are multiples of 64 (one pixel per 4 lanes and trip)
+// (C % 16 != 0: the last channel group is partial -- the frozen kernels only; the fused finalize requires C % 16 == 0)
 static inline void fin_geometry(int P, int C, int& CG, int& PC, int& chunk, int& grid) {
-    CG = C / GC;
+    CG = (C + GC - 1) / GC;
     long pc = 512 / CG;
     const long maxpc = ((long)P + 63) / 64;
     if (pc > maxpc) pc = maxpc;
@@ -837,6 +973,45 @@ int omni_bn_bwd_partials(const float* x, const float* dy, const float* y, const 
     if (partial == nullptr) return OMNI_ERR_ARG;
     return omni_bn_bwd_algo(x, dy, C, y, gamma, mean_rstd, partial, nblk, dx, dres, nullptr, 0, dgamma, dbeta, nullptr, coef, P, C, relu,
                             accumulate_param_grads, BN_FUSE_ROWS_DEFAULT, stream);
+}
+
+// Frozen (eval-mode) BatchNorm inside a training pass (freeze_bn, MODEL.USE_BN False): y = relu?(x * s + t (+ residual)) with
+// s = gamma * rsqrt(running_var + eps), t = beta - running_mean * s made in the launch from the live parameters; the same bits as
+// omni_bn_apply with the eval-mode (scale, shift) of layers.py.  Nothing else is written.
+int omni_bn_frozen_fwd(const float* x, const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                       float eps, const float* residual, float* y, int P, int C, int relu, void* stream) {
+    if (P <= 0 || C <= 0 || (C & 3) || C > 4096 || !gamma || !beta || !running_mean || !running_var) return OMNI_ERR_ARG;
+    int CG, PC, chunk, grid;
+    fin_geometry(P, C, CG, PC, chunk, grid);
+    hipLaunchKernelGGL(bn_frozen_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, running_mean, running_var, eps,
+                       residual, y, P, C, relu, CG, PC, chunk);
+    return omni_launch_status();
+}
+
+// Backward of omni_bn_frozen_fwd: ONE pass writes dx = g * s and dres = g (+ res_carry) [dres nullable] and per-chunk partials of
+// (sum g, sum g * xhat) to ws; a fixed-order finalize writes dgamma / dbeta (accumulate_param_grads: adds to them).  No atomics: two
+// runs give the same bits.  g = dy masked by the ReLU -- relu 0: none | 1: y > 0 (y = the forward output) | 2: x * s + t > 0
+// recomputed (forward without residual; y unused).  dy has pixel pitch lddy, res_carry pitch ldc (as omni_bn_bwd_carry).
+// dgamma == dbeta == NULL: no parameter gradients (no partials, no finalize).  ws: >= ws_floats floats, 2 * C * 512 always suffice.
+int omni_bn_frozen_bwd(const float* x, const float* dy, long long lddy, const float* y, const float* gamma, const float* beta,
+                       const float* running_mean, const float* running_var, float eps, float* dx, float* dres, const float* res_carry,
+                       long long ldc, float* dgamma, float* dbeta, float* ws, long long ws_floats, int P, int C, int relu,
+                       int accumulate_param_grads, void* stream) {
+    if (P <= 0 || C <= 0 || (C & 3) || C > 4096 || relu < 0 || relu > 2 || (relu == 1 && y == nullptr)) return OMNI_ERR_ARG;
+    if (!gamma || !beta || !running_mean || !running_var || (dgamma == nullptr) != (dbeta == nullptr)) return OMNI_ERR_ARG;
+    if (lddy == 0) lddy = C;
+    if (bad_carry(res_carry, ldc, C) || (res_carry != nullptr && dres == nullptr) || bad_carry(dy, lddy, C)) return OMNI_ERR_ARG;
+    int CG, PC, chunk, grid;
+    fin_geometry(P, C, CG, PC, chunk, grid);
+    const bool params = dgamma != nullptr;
+    if (params && (ws == nullptr || ws_floats < 2LL * C * PC)) return OMNI_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(bn_frozen_bwd_kernel, dim3(grid), dim3(256), 0, st, x, dy, (long)lddy, y, gamma, beta, running_mean, running_var, eps,
+                       dx, dres, res_carry, (long)ldc, params ? ws : nullptr, P, C, relu, CG, PC, chunk);
+    if (params)
+        hipLaunchKernelGGL(bn_frozen_bwd_fin_kernel, dim3((C + FIN_C - 1) / FIN_C), dim3(256), 0, st, (const float*)ws, PC, C, dgamma, dbeta,
+                           accumulate_param_grads);
+    return omni_launch_status();
 }
 
 int omni_maxpool2_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream) {

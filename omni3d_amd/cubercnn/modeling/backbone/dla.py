@@ -126,7 +126,7 @@ class Root(nn.Module):
         if _ROOT_MULTI_SRC and conv.kernel_size == (1, 1) and conv.bias is None and kconv.multi_src_eligible(x, conv.weight):
             # the 1 x 1 convolution reads its reduction slabs from the children directly: torch.cat(x, 1) is never formed (six
             # copies of 7-16 us on the critical path of the 4 x 512 x 512 step, and as many in an inference pass)
-            want_stats = self.training and torch.is_grad_enabled()
+            want_stats = self.bn.training and torch.is_grad_enabled()      # (a frozen BatchNorm reads no batch statistics)
             y = HF.cat_conv1x1(x, conv.weight, want_stats)
         else:
             # (the concatenation hands each child its slice of the gradient through the child's fan-in slot, see functional.fanout)
@@ -175,8 +175,10 @@ class Tree(nn.Module):
         HF.fanout(bottom)
         if self.levels > 1 and self.project is not None:
             # a nested Tree recomputes `residual` from its own projection and drops this one (dla.py:208-213 of the reference):
-            # run it for its BatchNorm's running statistics only -- no autograd graph, no saved activations
-            if _SIDE_STATS and HF.side_mode() == "collect":
+            # run it for its BatchNorm's running statistics only -- no autograd graph, no saved activations; not at all when that
+            # BatchNorm is frozen (freeze_bn: nothing to update)
+            live = self.project[1].training
+            if live and _SIDE_STATS and HF.side_mode() == "collect":
                 # a step being captured: nothing in the step reads that BatchNorm's running statistics, so the 1 x 1 convolution + statistics
                 # leave the critical path and replay in the stage's weight-gradient graph (late round 6; OMNI_DLA_SIDE_STATS=0: inline)
                 src = bottom.detach()
@@ -185,7 +187,7 @@ class Tree(nn.Module):
                     with torch.no_grad():
                         self.project(src)
                 HF._side_run(stats_only, (src,))
-            else:
+            elif live:
                 with torch.no_grad():
                     self.project(bottom.detach())
             residual = None

@@ -21,7 +21,7 @@ from torch import nn
 
 from .... import functional as HF
 from ....kernels import bnpool
-from ..layers import BatchNorm2d, Conv2d, DepthwiseConv2d
+from ..layers import BatchNorm2d, Conv2d, DepthwiseConv2d, frozen_bn_wants_grad
 from ..registries import BACKBONE_REGISTRY
 from .fpn import FPN, Backbone
 
@@ -71,6 +71,10 @@ def _bn(x, m, relu=False):
             if not m.defer_counter:
                 m.num_batches_tracked += 1
         return y[:, :c]
+    if frozen_bn_wants_grad(x, m):
+        # frozen BatchNorm of a training pass (layers.BatchNorm2d.forward): zero gamma / beta / mean and unit variance in the pad channels
+        mean, var = _pad_vec(m.running_mean.detach(), c4).contiguous(), _pad_vec(m.running_var.detach(), c4, 1.0).contiguous()
+        return HF.batch_norm_frozen(xp, gamma.contiguous(), beta.contiguous(), mean, var, None, relu, m.eps)[:, :c]
     scale = gamma * torch.rsqrt(_pad_vec(m.running_var, c4, 1.0) + m.eps)
     scale_shift = torch.cat([scale, beta - _pad_vec(m.running_mean, c4) * scale]).detach().contiguous()
     return bnpool.bn_apply(xp.contiguous(memory_format=torch.channels_last), scale_shift, None, relu)[:, :c]

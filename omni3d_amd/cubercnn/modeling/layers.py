@@ -24,9 +24,14 @@ class Conv2d(nn.Conv2d):
 
     def forward(self, x, relu=False):
         # a bias-free convolution in training mode is the conv half of a conv -> BatchNorm pair (every one in the DLA / ResNet
-        # bottom-up): let the kernel emit the batch statistics with its output
-        want_stats = self.bias is None and self.training and not relu and torch.is_grad_enabled()
-        return HF.conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0], relu, want_stats)
+        # bottom-up): let the kernel emit the batch statistics with its output -- unless that BatchNorm is frozen (eval mode: freeze_bn)
+        # and would not read them.  The BatchNorm makes itself known through the tag on the output (BatchNorm2d._note_producer).
+        pair = self.bias is None and self.training and not relu and torch.is_grad_enabled()
+        bn = self.__dict__.get("_stats_reader") if pair else None
+        y = HF.conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0], relu, pair and (bn is None or bn.training))
+        if pair:
+            y._omni_stats_producer = self
+        return y
 
 
 class GroupedConv2d(nn.Conv2d):
@@ -113,14 +118,48 @@ class FlattenLinear(nn.Module):
 
 
 PARAM_EPOCH = [0]        # bumped by every parameter update torch's version counters do not see (solver/build.py FlatOptimizer.step)
+BN_MODE_EPOCH = [0]      # bumped whenever a BatchNorm2d's `training` or `track_running_stats` changes (freeze_bn, .train() / .eval())
+TRAIN_PASS = [0]         # > 0 inside a training-mode pass of a model (training_pass): its eval-mode BatchNorms are frozen ones with gradients
+
+
+class training_pass:
+    """Marks the forward pass of a model in training mode (RCNN3D._forward).  An eval-mode BatchNorm2d inside it -- freeze_bn,
+    MODEL.USE_BN False -- normalises with its running statistics AND passes gradients (functional.batch_norm_frozen); outside it an
+    eval-mode BatchNorm2d is an inference layer and keeps its cached (scale, shift) path, bit for bit (the frozen kernel makes its
+    coefficients with the device library's rsqrtf, which differs from torch's GPU rsqrt in the last bit for some values)."""
+
+    def __enter__(self):
+        TRAIN_PASS[0] += 1
+        return self
+
+    def __exit__(self, *exc):
+        TRAIN_PASS[0] -= 1
+
+
+def frozen_bn_wants_grad(x, bn):
+    """an eval-mode BatchNorm of a training pass whose input or affine parameters need a gradient"""
+    return TRAIN_PASS[0] > 0 and torch.is_grad_enabled() and (x.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad)
 
 
 class BatchNorm2d(nn.BatchNorm2d):
     # RCNN3D sets this and bumps every `num_batches_tracked` of the model with ONE multi-tensor add per step
     defer_counter = False
 
+    def __setattr__(self, name, value):
+        # a captured training step holds the kernels of one BatchNorm mode (batch statistics or frozen): solver/autoreplay.py watches this
+        if name in ("training", "track_running_stats") and self.__dict__.get(name, value) != value:
+            BN_MODE_EPOCH[0] += 1
+        super().__setattr__(name, value)
+
+    def _note_producer(self, x):
+        """the bias-free Conv2d that wrote x learns which BatchNorm reads its output (Conv2d.forward: no batch statistics for a frozen one)"""
+        conv = getattr(x, "_omni_stats_producer", None)
+        if conv is not None and conv.__dict__.get("_stats_reader") is not self:
+            conv.__dict__["_stats_reader"] = self          # (not a submodule: kept out of nn.Module's registry)
+
     def forward(self, x, residual=None, relu=False):
         if self.training:
+            self._note_producer(x)
             y = HF.batch_norm_train(x, self.weight, self.bias, self.running_mean if self.track_running_stats else None,
                                     self.running_var if self.track_running_stats else None, residual, relu, self.eps,
                                     self.momentum)
@@ -129,6 +168,12 @@ class BatchNorm2d(nn.BatchNorm2d):
             if self.track_running_stats:
                 PARAM_EPOCH[0] += 1          # the kernel moved the running statistics through raw pointers: eval-mode caches are stale
             return y
+        if frozen_bn_wants_grad(x, self):
+            # frozen BatchNorm of a training pass (freeze_bn, MODEL.USE_BN False): the running statistics normalise, gamma / beta and
+            # everything below get gradients.  (scale, shift) are made inside the kernel from the live tensors: nothing a captured
+            # graph could hold stale
+            self._note_producer(x)
+            return HF.batch_norm_frozen(x, self.weight, self.bias, self.running_mean, self.running_var, residual, relu, self.eps)
         from ...kernels import bnpool
         # inference: (scale, shift) of the frozen statistics, built once per set of values (six ATen launches per layer and call
         # otherwise: 234 of the 805 launches of an inference pass, profiles/r04_infer_trace_table.txt).  The key catches every write

@@ -14,6 +14,7 @@ from ....d2.structures import ImageList
 from .... import functional as HF
 from ....kernels import bnpool
 from ..proposal_generator import build_proposal_generator
+from ..layers import training_pass
 from ..registries import BACKBONE_REGISTRY, META_ARCH_REGISTRY
 from ..roi_heads import build_roi_heads
 from ..targets import pack_targets
@@ -137,7 +138,8 @@ class RCNN3D(nn.Module):
             packed = self.prepack(batched_inputs)
         images = self.preprocess_image(batched_inputs, slot_hw=packed.image_hw if getattr(packed, "slotted", False) else None,
                                        hw_dev=getattr(packed, "image_hw", None))
-        features = self.backbone(images.tensor)
+        with training_pass():       # (eval-mode BatchNorms in here are frozen ones with gradients: freeze_bn / MODEL.USE_BN False)
+            features = self.backbone(images.tensor)
         if getattr(self, "feature_cut", None) is not None:   # data-parallel two-phase backward (solver/graphed.py)
             features = self.feature_cut(features)
         self._bump_bn_counters()

@@ -165,6 +165,8 @@ class AutoReplay:
         self.pools = None                        # (M pool, W pool) shared by the captured steps of every bucket (SHARE_POOLS)
         self._eager_anchor = None
         self.busy = False                        # True while a capture drives the model itself
+        self.bn_mode = None                      # BatchNorm modes the cached steps were captured under (see _check_bn_mode)
+        self._bn_epoch = None
         optimizer._auto = self
 
     # ---- signature / state machine -----------------------------------------------------------------------------------
@@ -242,6 +244,26 @@ class AutoReplay:
             warnings.warn(f"omni3d_amd: the captured-step cache still misses {miss:.0%} of the iterations; no new size bucket is captured "
                           "any more (cached buckets replay, the rest runs eager launches).  OMNI_AUTO_REPLAY_CACHE raises the cache size")
 
+    def _check_bn_mode(self):
+        """A captured step replays the BatchNorm kernels of the mode it was captured in: batch statistics + running-statistics update, or
+        the frozen eval-mode affine of freeze_bn (MODEL.USE_BN False, tools/train_net.py:150-151, :297-298 of the reference).  When the
+        (training, track_running_stats) flags of the model's BatchNorms differ from those the cache was filled under, every captured
+        step and the shared pools are dropped; each bucket earns its warm-up iterations again.  The flags are re-read only after
+        one of them changed (layers.BN_MODE_EPOCH): an eval pass and `model.train()` in between leave the cache alone."""
+        from ..modeling.layers import BN_MODE_EPOCH
+        if self._bn_epoch == BN_MODE_EPOCH[0]:
+            return
+        self._bn_epoch = BN_MODE_EPOCH[0]
+        modules = getattr(self.model, "modules", None)
+        if modules is None:         # (stand-in models of the tests)
+            return
+        mode = tuple((m.training, m.track_running_stats) for m in modules() if isinstance(m, torch.nn.BatchNorm2d))
+        if self.bn_mode is not None and mode != self.bn_mode:
+            self.cache.clear()
+            self.pools = None
+            self.counts.clear()
+        self.bn_mode = mode
+
     # (kept for callers / tests that look at the most recently used captured step)
     @property
     def stepper(self):
@@ -252,6 +274,7 @@ class AutoReplay:
         if not ENABLED or self.failed is not None or not self.model.training:
             return None
         self._raise_if_poisoned()
+        self._check_bn_mode()
         sig = self.signature(batched_inputs)
         entry = self.cache.get(sig)
         level = self.level

@@ -693,6 +693,54 @@ def batch_norm_train(x, gamma, beta, running_mean, running_var, residual=None, r
     return _BatchNorm.apply(x, gamma, beta, running_mean, running_var, residual, relu, eps, momentum, getattr(x, "_omni_bn_partials", None))
 
 
+class _FrozenBatchNorm(Function):
+    """eval-mode BatchNorm inside a training pass (freeze_bn / MODEL.USE_BN False): normalises with the running statistics, which it
+    never writes; gamma, beta, x and the residual get their gradients.  Same protocols as _BatchNorm: the residual's gradient fan-in
+    slot, direct accumulation of dgamma / dbeta into the flat gradient bucket.  Batch statistics a producer left on x
+    (`_omni_bn_partials`) are not read."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, residual, relu, eps):
+        gg, gb = _direct_grad(gamma), _direct_grad(beta)
+        ctx.direct = (gg, gb) if (gg is not None and gb is not None) else None
+        ctx.res_slot = _slot_enter(residual, residual is not None and ctx.needs_input_grad[5])
+        x = _cl(x)
+        res = _cl(residual) if residual is not None else None
+        y = bnpool.bn_frozen_fwd(x, gamma, beta, running_mean, running_var, res, relu, eps)
+        # ReLU mask for the backward pass: the output y, or (no residual) recomputed from x and the coefficients the kernel makes anyway
+        remask = relu and residual is None and _BN_REMASK
+        ctx.save_for_backward(x, gamma, beta, running_mean, running_var, (y if relu and not remask else None))
+        ctx.cfg = (relu, residual is not None, remask, eps)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, beta, running_mean, running_var, y = ctx.saved_tensors
+        relu, has_res, remask, eps = ctx.cfg
+        want_dres = has_res and ctx.needs_input_grad[5]
+        params = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        box = []
+        # (dy that is a channel slice of the Root's concatenated gradient is read where it lies)
+        dyk = dy if (not dy.is_contiguous(memory_format=CL) and _carry_pitch(dy) is not None) else _cl(dy)
+
+        def run(carry):     # carry: what the other consumers of the residual tensor contributed, added where dres is written
+            ok = carry is not None and _carry_pitch(carry) is not None
+            dx_, dres_, dgamma_, dbeta_ = bnpool.bn_frozen_bwd(x, dyk, y, gamma, beta, running_mean, running_var, eps, relu, remask,
+                                                               want_dres=want_dres, param_grads=params,
+                                                               accum_into=ctx.direct if params else None, res_carry=carry if ok else None)
+            box.append((dx_, dgamma_, dbeta_))
+            return dres_ if (ok or carry is None) else dres_ + carry
+
+        dres = _slot_deliver(ctx.res_slot, run) if want_dres else run(None)
+        dx, dgamma, dbeta = box[0]
+        return dx, dgamma, dbeta, None, None, dres, None, None
+
+
+def batch_norm_frozen(x, gamma, beta, running_mean, running_var, residual=None, relu=False, eps=1e-5):
+    """relu?(BatchNorm_eval(x) (+ residual)) with gradients for x, gamma, beta and the residual (torch's nn.BatchNorm2d in eval mode)"""
+    return _FrozenBatchNorm.apply(x, gamma, beta, running_mean, running_var, residual, relu, eps)
+
+
 class _MaxPool2(Function):
     @staticmethod
     def forward(ctx, x):

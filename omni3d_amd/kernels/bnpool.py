@@ -63,6 +63,63 @@ def bn_apply(x, scale_shift, residual=None, relu=False):
     return y.permute(0, 3, 1, 2)
 
 
+def bn_frozen_fwd(x, gamma, beta, running_mean, running_var, residual=None, relu=False, eps=1e-5):
+    """frozen (eval-mode) BatchNorm of a training pass: relu?(x * s + t (+ residual)) with (s, t) made in the kernel from the live
+    gamma / beta / running statistics (omni_bn_frozen_fwd) -> y CL.  Same bits as bn_apply with layers.BatchNorm2d's eval-mode
+    (scale, shift); nothing but y is written."""
+    xv = _nhwc(x)
+    rv = _nhwc(residual) if residual is not None else None
+    N, H, W, C = xv.shape
+    L = _lib.check_device(xv, rv, gamma, beta, running_mean, running_var)
+    for t in (gamma, beta, running_mean, running_var):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C
+    y = _like_cl((N, H, W, C), x)
+    L.call("omni_bn_frozen_fwd", _lib.ptr(xv), _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean), _lib.ptr(running_var), float(eps),
+           _lib.ptr(rv), _lib.ptr(y), N * H * W, C, int(relu), _lib.stream_of(x))
+    return y.permute(0, 3, 1, 2)
+
+
+def bn_frozen_bwd(x, dy, y, gamma, beta, running_mean, running_var, eps=1e-5, relu=False, remask=False, want_dres=False, param_grads=True,
+                  accum_into=None, res_carry=None):
+    """backward of bn_frozen_fwd -> (dx CL, dres CL or None, dgamma, dbeta).  relu with remask: the mask is recomputed from x (forward
+    without residual; y may be None), otherwise read from y.  param_grads False: no dgamma / dbeta (None, None).  accum_into =
+    (dgamma_buf, dbeta_buf): added to those buffers instead (dgamma / dbeta returned as None).  dy may be pitched (a channel slice of
+    the Root's concatenated gradient); res_carry: gradient fan-in of the residual (functional._carry_pitch), added where dres is
+    written."""
+    xv = _nhwc(x)
+    N, H, W, C = xv.shape
+    dy_pitched = not dy.is_contiguous(memory_format=torch.channels_last)
+    if dy_pitched:
+        assert tuple(dy.shape) == tuple(x.shape) and dy.stride(1) == 1
+    dyv = None if dy_pitched else _nhwc(dy)
+    mode = 0
+    yv = None
+    if relu:
+        mode = 2 if remask else 1
+        yv = None if remask else _nhwc(y)
+    L = _lib.check_device(xv, dyv, yv, gamma, beta, running_mean, running_var)
+    dx = _like_cl((N, H, W, C), x)
+    dres = _like_cl((N, H, W, C), x) if want_dres else None
+    if res_carry is not None:
+        assert want_dres and tuple(res_carry.shape) == tuple(x.shape)
+    dgamma = dbeta = ws = None
+    if param_grads:
+        if accum_into is not None:
+            dgamma, dbeta = accum_into
+            assert dgamma.is_contiguous() and dbeta.is_contiguous() and dgamma.numel() == C and dbeta.numel() == C
+        else:
+            dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+            dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
+        ws = torch.empty(2 * C * 512, dtype=torch.float32, device=x.device)
+    L.call("omni_bn_frozen_bwd", _lib.ptr(xv), dy.data_ptr() if dy_pitched else _lib.ptr(dyv), dy.stride(3) if dy_pitched else C, _lib.ptr(yv),
+           _lib.ptr(gamma), _lib.ptr(beta), _lib.ptr(running_mean), _lib.ptr(running_var), float(eps), _lib.ptr(dx), _lib.ptr(dres),
+           _lib.ptr(res_carry), res_carry.stride(3) if res_carry is not None else 0, _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ws),
+           ws.numel() if ws is not None else 0, N * H * W, C, mode, int(accum_into is not None), _lib.stream_of(x))
+    if accum_into is not None:
+        dgamma = dbeta = None
+    return dx.permute(0, 3, 1, 2), (dres.permute(0, 3, 1, 2) if want_dres else None), dgamma, dbeta
+
+
 def bn_bwd(x, dy, y, gamma, mean_rstd, relu=False, want_dres=False, accum_into=None, scale_shift=None, partials=None, res_carry=None):
     """-> (dx CL, dres CL or None, dgamma, dbeta).  accum_into = (dgamma_buf, dbeta_buf): the parameter
     gradients are added to those buffers instead (dgamma/dbeta returned as None).  scale_shift (2C, from bn_fwd) instead of y:
