@@ -940,31 +940,44 @@ def upsample2_add(lat, top):
     return _Upsample2Add.apply(lat, top)
 
 
+# ---- ROI poolers: the fan-in protocol they share (block comment above _Conv2d) is in these two helpers; each Function below keeps its own
+# kernels/det.py forward / backward, what it saves, and whether the level gradients start zeroed (atomic scatter) or empty (written once).
+def _pool_enter(ctx, k, feats):
+    """forward prologue; feats = the Function's inputs from position k on: a fan-in slot per FPN level -> the levels' (B, H, W, C) views"""
+    ctx.slots = [_slot_enter(f, ctx.needs_input_grad[k + i]) for i, f in enumerate(feats)]
+    feats = [_cl(f) for f in feats]
+    nhwc = [f.permute(0, 2, 3, 1) for f in feats]
+    ctx.shapes = [tuple(f.shape) for f in nhwc]
+    return nhwc
+
+
+def _pool_deliver(ctx, k, dfe):
+    """backward epilogue: nothing for the k leading inputs; each level's NHWC gradient goes through the feature's fan-in slot (the RPN
+    head's data gradient, which runs later, reads it in its output transform instead of an add kernel over the whole map)"""
+    return (None,) * k + tuple(_slot_deliver(slot, lambda carry, d=d: _add_carry(d.permute(0, 3, 1, 2), carry)) for slot, d in zip(ctx.slots, dfe))
+
+
 class _ROIAlign(Function):
     """feats: logical (B,C,H,W) CL tensors of the FPN levels -> (R, C, P, P) CL (physically (R,P,P,C))."""
 
     @staticmethod
     def forward(ctx, rois, batch_idx, levels, scales, P, *feats):
-        ctx.slots = [_slot_enter(f, ctx.needs_input_grad[5 + i]) for i, f in enumerate(feats)]
-        feats = [_cl(f) for f in feats]
-        nhwc = [f.permute(0, 2, 3, 1) for f in feats]
-        out = det.roi_align_fwd(nhwc, scales, rois, batch_idx, levels, P)
+        out = det.roi_align_fwd(_pool_enter(ctx, 5, feats), scales, rois, batch_idx, levels, P)
         ctx.save_for_backward(rois, batch_idx, levels)
-        ctx.meta = (scales, P, [tuple(f.shape) for f in nhwc])
+        ctx.meta = (scales, P)
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, dout):
         rois, batch_idx, levels = ctx.saved_tensors
-        scales, P, shapes = ctx.meta
-        if det.roi_align_bwd_deterministic(P, rois.shape[0], shapes[0][3]):
-            dfe = [torch.empty(s, dtype=torch.float32, device=dout.device) for s in shapes]      # every element written exactly once
+        scales, P = ctx.meta
+        if det.roi_align_bwd_deterministic(P, rois.shape[0], ctx.shapes[0][3]):
+            dfe = [torch.empty(s, dtype=torch.float32, device=dout.device) for s in ctx.shapes]      # every element written exactly once
             det.roi_align_bwd_det(dfe, scales, rois, batch_idx, levels, P, _cl(dout).permute(0, 2, 3, 1).contiguous())
         else:
-            dfe = [torch.zeros(s, dtype=torch.float32, device=dout.device) for s in shapes]
+            dfe = [torch.zeros(s, dtype=torch.float32, device=dout.device) for s in ctx.shapes]
             det.roi_align_bwd(dfe, scales, rois, batch_idx, levels, P, _cl(dout).permute(0, 2, 3, 1))
-        return (None, None, None, None, None) + tuple(_slot_deliver(slot, lambda carry, d=d: _add_carry(d.permute(0, 3, 1, 2), carry))
-                                                      for slot, d in zip(ctx.slots, dfe))
+        return _pool_deliver(ctx, 5, dfe)
 
 
 def roi_align(feats, scales, rois, batch_idx, levels, P):
@@ -977,22 +990,18 @@ class _ROIAlignLegacy(Function):
 
     @staticmethod
     def forward(ctx, rois, batch_idx, levels, scales, P, *feats):
-        ctx.slots = [_slot_enter(f, ctx.needs_input_grad[5 + i]) for i, f in enumerate(feats)]
-        feats = [_cl(f) for f in feats]
-        nhwc = [f.permute(0, 2, 3, 1) for f in feats]
-        out = det.roi_align_fwd_mode(nhwc, scales, rois, batch_idx, levels, P, False)
+        out = det.roi_align_fwd_mode(_pool_enter(ctx, 5, feats), scales, rois, batch_idx, levels, P, False)
         ctx.save_for_backward(rois, batch_idx, levels)
-        ctx.meta = (scales, P, [tuple(f.shape) for f in nhwc])
+        ctx.meta = (scales, P)
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, dout):
         rois, batch_idx, levels = ctx.saved_tensors
-        scales, P, shapes = ctx.meta
-        dfe = [torch.zeros(s, dtype=torch.float32, device=dout.device) for s in shapes]
+        scales, P = ctx.meta
+        dfe = [torch.zeros(s, dtype=torch.float32, device=dout.device) for s in ctx.shapes]
         det.roi_align_bwd_mode(dfe, scales, rois, batch_idx, levels, P, False, _cl(dout).permute(0, 2, 3, 1).contiguous())
-        return (None, None, None, None, None) + tuple(_slot_deliver(slot, lambda carry, d=d: _add_carry(d.permute(0, 3, 1, 2), carry))
-                                                      for slot, d in zip(ctx.slots, dfe))
+        return _pool_deliver(ctx, 5, dfe)
 
 
 def roi_align_legacy(feats, scales, rois, batch_idx, levels, P):
@@ -1005,22 +1014,18 @@ class _ROIPool(Function):
 
     @staticmethod
     def forward(ctx, rois, batch_idx, levels, scales, P, *feats):
-        ctx.slots = [_slot_enter(f, ctx.needs_input_grad[5 + i]) for i, f in enumerate(feats)]
-        feats = [_cl(f) for f in feats]
-        nhwc = [f.permute(0, 2, 3, 1) for f in feats]
-        out, arg = det.roi_pool_fwd(nhwc, scales, rois, batch_idx, levels, P)
+        out, arg = det.roi_pool_fwd(_pool_enter(ctx, 5, feats), scales, rois, batch_idx, levels, P)
         ctx.save_for_backward(batch_idx, levels, arg)
-        ctx.meta = (scales, P, [tuple(f.shape) for f in nhwc])
+        ctx.meta = (scales, P)
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, dout):
         batch_idx, levels, arg = ctx.saved_tensors
-        scales, P, shapes = ctx.meta
-        dfe = [torch.zeros(s, dtype=torch.float32, device=dout.device) for s in shapes]
+        scales, P = ctx.meta
+        dfe = [torch.zeros(s, dtype=torch.float32, device=dout.device) for s in ctx.shapes]
         det.roi_pool_bwd(dfe, scales, batch_idx, levels, P, _cl(dout).permute(0, 2, 3, 1).contiguous(), arg)
-        return (None, None, None, None, None) + tuple(_slot_deliver(slot, lambda carry, d=d: _add_carry(d.permute(0, 3, 1, 2), carry))
-                                                      for slot, d in zip(ctx.slots, dfe))
+        return _pool_deliver(ctx, 5, dfe)
 
 
 def roi_pool(feats, scales, rois, batch_idx, levels, P):
@@ -1037,18 +1042,16 @@ class _ROIAlignShared(Function):
 
     @staticmethod
     def forward(ctx, rois, batch_idx, levels, scales, P, per_image, first, *feats):
-        ctx.slots = [_slot_enter(f, ctx.needs_input_grad[7 + i]) for i, f in enumerate(feats)]
-        feats = [_cl(f) for f in feats]
-        nhwc = [f.permute(0, 2, 3, 1) for f in feats]
+        nhwc = _pool_enter(ctx, 7, feats)
         out, sub = det.roi_align_fwd2(nhwc, scales, rois, batch_idx, levels, P, per_image, first)   # (R, P, P, C), (R/per_image*first, P, P, C)
         ctx.save_for_backward(rois, batch_idx, levels)
-        ctx.meta = (scales, P, per_image, first, [tuple(f.shape) for f in nhwc])
+        ctx.meta = (scales, P, per_image, first)
         return out.permute(0, 3, 1, 2), sub.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, d_all, d_first):
         rois, batch_idx, levels = ctx.saved_tensors
-        scales, P, per_image, first, shapes = ctx.meta
+        (scales, P, per_image, first), shapes = ctx.meta, ctx.shapes
         d = _cl(d_all).permute(0, 2, 3, 1) if d_all is not None else None
         df = _cl(d_first).permute(0, 2, 3, 1) if d_first is not None else None
         ref = d if d is not None else df
@@ -1076,10 +1079,7 @@ class _ROIAlignShared(Function):
                 C = d.shape[3]
                 d.view(-1, per_image, P, P, C)[:, :first] += df.reshape(-1, first, P, P, C)
             det.roi_align_bwd(dfe, scales, rois, batch_idx, levels, P, d)
-        # (each level's gradient goes through the feature's fan-in slot: the RPN head's data gradient, which runs later, reads it
-        # in its output transform instead of an add kernel over the whole map)
-        return (None,) * 7 + tuple(_slot_deliver(slot, lambda carry, t=t: _add_carry(t.permute(0, 3, 1, 2), carry))
-                                   for slot, t in zip(ctx.slots, dfe))
+        return _pool_deliver(ctx, 7, dfe)
 
 
 def roi_align_shared(feats, scales, rois, batch_idx, levels, P, per_image, first):

@@ -29,44 +29,31 @@ def to_channels_last(t):
 
 def _fwd_launch(L, x, w, bias, out, N, H, W, C, K, R, S, stride, pad, ldx, ldo, relu, tile, splits, like, stats=None, stats_rows=0, nblk_addr=None):
     """omni_conv2d_fwd_algo / _stats, or -- deterministic mode -- omni_conv2d_fwd_det with the workspace its own plan asks for"""
-    st = _lib.stream_of(like)
-    if not _det.on():
-        if stats is not None:
-            L.call("omni_conv2d_fwd_stats", x, w, out, N, H, W, C, K, R, S, stride, pad, ldx, ldo, _lib.ptr(stats), stats_rows, nblk_addr, st)
-        else:
-            L.call("omni_conv2d_fwd_algo", x, w, bias, out, N, H, W, C, K, R, S, stride, pad, ldx, ldo, int(relu), tile, splits, st)
-        return
-    plan, addr = _det.new_plan()
-    L.call("omni_conv2d_fwd_det", x, w, bias, out, N, H, W, C, K, R, S, stride, pad, ldx, ldo, int(relu), tile, splits, None, 0, None, None, 0,
-           None, 0, addr, st)
-    ws, wsf, ctr, nctr = _det.workspace(like, plan)
-    L.call("omni_conv2d_fwd_det", x, w, bias, out, N, H, W, C, K, R, S, stride, pad, ldx, ldo, int(relu), int(plan[0]), int(plan[1]),
-           _lib.ptr(stats), stats_rows, nblk_addr, _lib.ptr(ws), wsf, _lib.ptr(ctr), nctr, None, st)
+    if _det.on():
+        _det.plan_launch(L, "omni_conv2d_fwd_det", like, (x, w, bias, out, N, H, W, C, K, R, S, stride, pad, ldx, ldo, int(relu)),
+                         ask=(tile, splits), late=(_lib.ptr(stats), stats_rows, nblk_addr))
+    elif stats is not None:
+        L.call("omni_conv2d_fwd_stats", x, w, out, N, H, W, C, K, R, S, stride, pad, ldx, ldo, _lib.ptr(stats), stats_rows, nblk_addr,
+               _lib.stream_of(like))
+    else:
+        L.call("omni_conv2d_fwd_algo", x, w, bias, out, N, H, W, C, K, R, S, stride, pad, ldx, ldo, int(relu), tile, splits, _lib.stream_of(like))
 
 
 def _dgrad_launch(L, dy, w, dx, N, H, W, C, K, R, S, stride, pad, lddy, lddx, accumulate, tile, splits, like):
-    st = _lib.stream_of(like)
-    if not _det.on():
-        L.call("omni_conv2d_dgrad_algo", dy, w, dx, N, H, W, C, K, R, S, stride, pad, lddy, lddx, accumulate, tile, splits, st)
-        return
-    plan, addr = _det.new_plan()
-    L.call("omni_conv2d_dgrad_det", dy, w, dx, N, H, W, C, K, R, S, stride, pad, lddy, lddx, accumulate, tile, splits, None, 0, None, 0, addr, st)
-    ws, wsf, ctr, nctr = _det.workspace(like, plan)
-    L.call("omni_conv2d_dgrad_det", dy, w, dx, N, H, W, C, K, R, S, stride, pad, lddy, lddx, accumulate, int(plan[0]), int(plan[1]),
-           _lib.ptr(ws), wsf, _lib.ptr(ctr), nctr, None, st)
+    head = (dy, w, dx, N, H, W, C, K, R, S, stride, pad, lddy, lddx, accumulate)
+    if _det.on():
+        _det.plan_launch(L, "omni_conv2d_dgrad_det", like, head, ask=(tile, splits))
+    else:
+        L.call("omni_conv2d_dgrad_algo", *head, tile, splits, _lib.stream_of(like))
 
 
 def _wgrad_launch(L, x, dy, dw, N, H, W, C, K, R, S, stride, pad, ldx, lddy, accumulate, tile, like):
-    st = _lib.stream_of(like)
-    if not _det.on():
-        L.call("omni_conv2d_wgrad_algo", x, dy, dw, N, H, W, C, K, R, S, stride, pad, ldx, lddy, accumulate, tile, st)
-        return
-    plan, addr = _det.new_plan()
-    L.call("omni_conv2d_wgrad_det", x, dy, dw, N, H, W, C, K, R, S, stride, pad, ldx, lddy, accumulate, tile, None, 0, None, 0, addr, st)
-    ws, wsf, ctr, nctr = _det.workspace(like, plan)
-    # (the tile is passed back as the caller gave it: `tile` also carries the workgroup-order request, + 16 / + 32)
-    L.call("omni_conv2d_wgrad_det", x, dy, dw, N, H, W, C, K, R, S, stride, pad, ldx, lddy, accumulate, tile, _lib.ptr(ws), wsf, _lib.ptr(ctr),
-           nctr, None, st)
+    # (the tile is part of the head: the launch gets it back as the caller gave it, it also carries the workgroup-order request, + 16 / + 32)
+    head = (x, dy, dw, N, H, W, C, K, R, S, stride, pad, ldx, lddy, accumulate, tile)
+    if _det.on():
+        _det.plan_launch(L, "omni_conv2d_wgrad_det", like, head)
+    else:
+        L.call("omni_conv2d_wgrad_algo", *head, _lib.stream_of(like))
 
 
 def conv2d_fwd(x, w, bias=None, stride=1, pad=0, relu=False, tile=0, splits=0):
@@ -140,17 +127,12 @@ def conv1x1_multi_fwd(xs, w, bias=None, relu=False, want_stats=False, tile=0, sp
     pa, ca = ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(cs, ctypes.c_void_p)
     stats = _stats_buf(K, out.device) if want_stats and bias is None and not relu else None
     cell, addr = _nblk_cell()
-    st = _lib.stream_of(xv[0])
     head = (pa, ca, n, _lib.ptr(wv), _lib.ptr(bias), _lib.ptr(out), N, H, W, K, K, int(relu))
-    if not _det.on():
-        L.call("omni_conv2d_fwd_multi_det", *head, tile, splits, _lib.ptr(stats), STATS_ROWS if stats is not None else 0, addr, None, 0, None, 0,
-               None, st)
+    late = (_lib.ptr(stats), STATS_ROWS if stats is not None else 0, addr)
+    if _det.on():
+        _det.plan_launch(L, "omni_conv2d_fwd_multi_det", xv[0], head, ask=(tile, splits), late=late)
     else:
-        plan, paddr = _det.new_plan()
-        L.call("omni_conv2d_fwd_multi_det", *head, tile, splits, None, 0, None, None, 0, None, 0, paddr, st)
-        ws, wsf, ctr, nctr = _det.workspace(xv[0], plan)
-        L.call("omni_conv2d_fwd_multi_det", *head, int(plan[0]), int(plan[1]), _lib.ptr(stats), STATS_ROWS if stats is not None else 0, addr,
-               _lib.ptr(ws), wsf, _lib.ptr(ctr), nctr, None, st)
+        L.call("omni_conv2d_fwd_multi_det", *head, tile, splits, *late, None, 0, None, 0, None, _lib.stream_of(xv[0]))
     return out.permute(0, 3, 1, 2), (stats[:cell.value] if stats is not None and cell.value > 0 else None)
 
 
@@ -254,15 +236,11 @@ def conv1x1_multi_wgrad(xs, dy, accum_into=None, tile=0):
         dw, acc = tgt, 1
     else:
         dw, acc = torch.empty((K, 1, 1, C), dtype=torch.float32, device=dyv.device), 0
-    st = _lib.stream_of(dyv)
     head = (pa, ca, n, _lib.ptr(dyv), _lib.ptr(dw), N, H, W, K, K, acc, tile)
-    if not _det.on():
-        L.call("omni_conv2d_wgrad_multi_det", *head, None, 0, None, 0, None, st)
+    if _det.on():
+        _det.plan_launch(L, "omni_conv2d_wgrad_multi_det", dyv, head)
     else:
-        plan, paddr = _det.new_plan()
-        L.call("omni_conv2d_wgrad_multi_det", *head, None, 0, None, 0, paddr, st)
-        ws, wsf, ctr, nctr = _det.workspace(dyv, plan)
-        L.call("omni_conv2d_wgrad_multi_det", *head, _lib.ptr(ws), wsf, _lib.ptr(ctr), nctr, None, st)
+        L.call("omni_conv2d_wgrad_multi_det", *head, None, 0, None, 0, None, _lib.stream_of(dyv))
     return None if accum_into is not None else dw.permute(0, 3, 1, 2)
 
 
@@ -379,11 +357,8 @@ def stem_first_wgrad(x, dy, accum_into=None):
     dst = accum_into.permute(0, 2, 3, 1) if accum_into is not None else torch.empty((16, 7, 7, 3), dtype=torch.float32, device=x.device)
     assert dst.is_contiguous() and tuple(dst.shape) == (16, 7, 7, 3)
     acc = int(accum_into is not None)
-    plan, addr = _det.new_plan()
-    L.call("omni_stem_conv_wgrad_det_cw", _lib.ptr(xv), _lib.ptr(dv), _lib.ptr(dst), 3, N, H, W, C, 16, 7, C, 16, acc, None, 0, addr, _lib.stream_of(x))
-    ws = torch.empty(max(int(plan[3]), 1), dtype=torch.float32, device=x.device)
-    L.call("omni_stem_conv_wgrad_det_cw", _lib.ptr(xv), _lib.ptr(dv), _lib.ptr(dst), 3, N, H, W, C, 16, 7, C, 16, acc, _lib.ptr(ws), int(plan[3]), None,
-           _lib.stream_of(x))
+    _det.plan_launch(L, "omni_stem_conv_wgrad_det_cw", x, (_lib.ptr(xv), _lib.ptr(dv), _lib.ptr(dst), 3, N, H, W, C, 16, 7, C, 16, acc),
+                     counters=False)
     return None if accum_into is not None else dst.permute(0, 3, 1, 2)
 
 
@@ -434,32 +409,23 @@ def stem_conv_wgrad(x, dy, R, accum_into=None, stride=1):
     K = dv.shape[3]
     L = _lib.check_device(xv, dv)
     on = _det.on()
-
-    def call(dst, acc, ws, wsf, plan):
-        if stride == 2:
-            L.call("omni_stem_conv_s2_wgrad", _lib.ptr(xv), _lib.ptr(dv), _lib.ptr(dst), N, H, W, C, K, R, C, K, acc, int(on), ws, wsf, plan,
-                   _lib.stream_of(x))
-        elif on:
-            L.call("omni_stem_conv_wgrad_det", _lib.ptr(xv), _lib.ptr(dv), _lib.ptr(dst), N, H, W, C, K, R, C, K, acc, ws, wsf, plan, _lib.stream_of(x))
-        else:
-            L.call("omni_stem_conv_wgrad", _lib.ptr(xv), _lib.ptr(dv), _lib.ptr(dst), N, H, W, C, K, R, C, K, acc, _lib.stream_of(x))
-
-    def launch(dst, acc):
-        if not on:
-            call(dst, acc, None, 0, None)
-            return
-        plan, addr = _det.new_plan()
-        call(dst, acc, None, 0, addr)
-        ws = torch.empty(max(int(plan[3]), 1), dtype=torch.float32, device=x.device)
-        call(dst, acc, _lib.ptr(ws), int(plan[3]), None)
     if accum_into is not None:
-        gv = accum_into.permute(0, 2, 3, 1)
-        assert gv.is_contiguous() and tuple(gv.shape) == (K, R, R, C)
-        launch(gv, 1)
-        return None
-    dw = torch.empty((K, R, R, C), dtype=torch.float32, device=x.device)
-    launch(dw, 0)
-    return dw.permute(0, 3, 1, 2)
+        dst = accum_into.permute(0, 2, 3, 1)
+        assert dst.is_contiguous() and tuple(dst.shape) == (K, R, R, C)
+    else:
+        dst = torch.empty((K, R, R, C), dtype=torch.float32, device=x.device)
+    head = (_lib.ptr(xv), _lib.ptr(dv), _lib.ptr(dst), N, H, W, C, K, R, C, K, int(accum_into is not None))
+    if stride == 2:
+        name, head = "omni_stem_conv_s2_wgrad", head + (int(on),)
+    else:
+        name = "omni_stem_conv_wgrad_det" if on else "omni_stem_conv_wgrad"
+    if on:
+        _det.plan_launch(L, name, x, head, counters=False)
+    elif stride == 2:
+        L.call(name, *head, None, 0, None, _lib.stream_of(x))
+    else:
+        L.call(name, *head, _lib.stream_of(x))
+    return None if accum_into is not None else dst.permute(0, 3, 1, 2)
 
 
 # ---- depthwise convolution (csrc/depthwise.hip); weights cross as (R, R, C) tap-major ----------------------------------------------

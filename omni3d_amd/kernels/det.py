@@ -6,6 +6,7 @@ import math
 import torch
 
 from .. import lib as _lib
+from . import detmode as _det
 
 _P = ctypes.c_void_p
 
@@ -315,7 +316,6 @@ def roi_align_fwd2(feats_nhwc, scales, rois, batch_idx, levels, P, per_image, fi
 
 def roi_align_bwd_deterministic(P, R, C=256):
     """the owner-computes backward (omni_roi_align_bwd_det) serves the pooler resolution and FPN width of every Cube R-CNN config"""
-    from . import detmode as _det
     return _det.on() and P == 7 and R <= 4096 and C <= 256
 
 
@@ -325,12 +325,8 @@ def roi_align_bwd_det(dfeats_nhwc, scales, rois, batch_idx, levels, P, dout, dou
     R, C, B = rois.shape[0], dfeats_nhwc[0].shape[3], dfeats_nhwc[0].shape[0]
     keep, a = _feat_args(dfeats_nhwc, scales)
     assert (dout is None or dout.is_contiguous()) and (dout2 is None or dout2.is_contiguous())
-    from . import detmode as _det
-    args = (*a, B, _lib.ptr(rois), _lib.ptr(batch_idx), _lib.ptr(levels), R, P, C, _lib.ptr(dout), _lib.ptr(dout2), int(per_image), int(first))
-    plan, addr = _det.new_plan()
-    L.call("omni_roi_align_bwd_det", *args, None, 0, None, 0, addr, _lib.stream_of(rois))
-    ws, wsf, ctr, nctr = _det.workspace(rois, plan)
-    L.call("omni_roi_align_bwd_det", *args, _lib.ptr(ws), wsf, _lib.ptr(ctr), nctr, None, _lib.stream_of(rois))
+    _det.plan_launch(L, "omni_roi_align_bwd_det", rois, (*a, B, _lib.ptr(rois), _lib.ptr(batch_idx), _lib.ptr(levels), R, P, C, _lib.ptr(dout),
+                                                         _lib.ptr(dout2), int(per_image), int(first)))
 
 
 def roi_align_bwd(dfeats_nhwc, scales, rois, batch_idx, levels, P, dout, dout2=None, per_image=0, first=0):

@@ -17,6 +17,8 @@ import os
 
 import torch
 
+from .. import lib as _lib
+
 _ON = os.environ.get("OMNI_DETERMINISTIC", "1") != "0"
 _CTR_CAP = 1 << 16
 _domain = None
@@ -100,12 +102,7 @@ def prewarm(device, families=("M", "W")):
             _counters[key] = torch.zeros(_CTR_CAP, dtype=torch.int32, device=dev)
 
 
-def new_plan():
-    buf = (ctypes.c_longlong * 4)()
-    return buf, ctypes.addressof(buf)
-
-
-def workspace(like, plan):
+def _workspace(like, plan):
     """plan = the four values a `*_det` entry point reported -> (ws tensor or None, ws_floats, counter tensor, n_ctr)"""
     n_ctr, ws_floats = int(plan[2]), int(plan[3])
     ws = torch.empty(ws_floats, dtype=torch.float32, device=like.device) if ws_floats > 0 else None
@@ -120,3 +117,29 @@ def workspace(like, plan):
         raise RuntimeError("omni3d_amd: arrival counters of a deterministic reduction are not zero on entry (an earlier launch of this "
                            f"stream faulted or was planned with another split count): {int((ctr != 0).sum())} entries")
     return ws, ws_floats, ctr, max(n_ctr, 1)
+
+
+def plan_launch(L, name, like, head, ask=(), late=(), counters=True):
+    """The call protocol of every entry of include/omni3d_hip.h that takes `plan`, in one place: the plan call (nothing launches; the
+    launcher reports tile / splits / counters / workspace floats), the workspace that plan asks for, the launch.
+
+        name(*head, *ask,             <nulls for late>, NULL, 0[, NULL, 0],          &plan, stream)
+        name(*head, *plan[:len(ask)], *late,            ws, ws_floats[, ctr, n_ctr], NULL,  stream)
+
+    head: the leading arguments, the same in both calls by construction.  ask: the algorithm request that follows them (tile, splits /
+    algo; 0 = the launcher's choice); the launch passes the plan's answer in its place.  A request the launch must repeat unchanged
+    (the weight gradient's tile, which also carries the workgroup order) belongs to `head`.  late: arguments only the launch gets (the
+    forward's statistics buffer, its row count and block-count cell).  counters=False: the workspace-only tail of the stem weight
+    gradients (no arrival counters; at least one float is allocated).  `like` selects device, stream and counter domain."""
+    st = _lib.stream_of(like)
+    plan = (ctypes.c_longlong * 4)()
+    k = len(head) + len(ask)
+    nulls = [None if c == "p" else 0 for c in _lib.SIGNATURES[name][k:k + len(late)]]
+    if counters:
+        L.call(name, *head, *ask, *nulls, None, 0, None, 0, ctypes.addressof(plan), st)
+        ws, wsf, ctr, nctr = _workspace(like, plan)
+        L.call(name, *head, *plan[:len(ask)], *late, _lib.ptr(ws), wsf, ctr.data_ptr(), nctr, None, st)
+    else:
+        L.call(name, *head, *ask, *nulls, None, 0, ctypes.addressof(plan), st)
+        ws = torch.empty(max(int(plan[3]), 1), dtype=torch.float32, device=like.device)
+        L.call(name, *head, *plan[:len(ask)], *late, ws.data_ptr(), int(plan[3]), None, st)

@@ -3,6 +3,7 @@ forward / data-gradient / weight-gradient of a 3x3, stride-1, pad-1 convolution 
 import torch
 
 from .. import lib as _lib
+from . import detmode as _det
 
 CL = torch.channels_last
 
@@ -158,15 +159,11 @@ def gemm_batched_wgrad(V, dM, algo=0):
     K = dM.shape[2]
     L = _lib.check_device(V, dM)
     dU = torch.empty((B, K, C), dtype=torch.float32, device=V.device)
-    from . import detmode as _det
-    if not _det.on():
-        L.call("omni_gemm_batched_wgrad_algo", _lib.ptr(V), _lib.ptr(dM), _lib.ptr(dU), B, M, C, K, algo, _lib.stream_of(V))
-        return dU
-    plan, addr = _det.new_plan()
-    L.call("omni_gemm_batched_wgrad_det", _lib.ptr(V), _lib.ptr(dM), _lib.ptr(dU), B, M, C, K, algo, None, 0, None, 0, addr, _lib.stream_of(V))
-    ws, wsf, ctr, nctr = _det.workspace(V, plan)
-    L.call("omni_gemm_batched_wgrad_det", _lib.ptr(V), _lib.ptr(dM), _lib.ptr(dU), B, M, C, K, int(plan[0]), _lib.ptr(ws), wsf, _lib.ptr(ctr), nctr,
-           None, _lib.stream_of(V))
+    head = (_lib.ptr(V), _lib.ptr(dM), _lib.ptr(dU), B, M, C, K)
+    if _det.on():
+        _det.plan_launch(L, "omni_gemm_batched_wgrad_det", V, head, ask=(algo,))
+    else:
+        L.call("omni_gemm_batched_wgrad_algo", *head, algo, _lib.stream_of(V))
     return dU
 
 
@@ -179,7 +176,6 @@ def gemm_batched_wgrad_multi(problems):
     """problems: [(V (B,M,C), dM (B,M,K))], <= 16, any mix of shapes -> [dU (B,K,C)], all in ONE launch (omni_gemm_batched_wgrad_multi);
     bit-identical to gemm_batched_wgrad on each"""
     import ctypes
-    from . import detmode as _det
     n = len(problems)
     assert 0 < n <= WGRAD_MULTI_MAX
     L = _lib.check_device(*[t for pr in problems for t in pr])
@@ -195,13 +191,10 @@ def gemm_batched_wgrad_multi(problems):
         gf = sum(2.0 * V.shape[0] * V.shape[1] * V.shape[2] * dM.shape[2] for V, dM in problems) / 1e9
         print(f"gemm_tn_multi: {n} problems, {gf:.2f} GFLOP: " + " ".join(f"{V.shape[0]}x[{V.shape[1]}x{dM.shape[2]}x{V.shape[2]}]" for V, dM in problems),
               flush=True)
-    if not _det.on():
+    if _det.on():
+        _det.plan_launch(L, "omni_gemm_batched_wgrad_multi", V0, head)
+    else:
         L.call("omni_gemm_batched_wgrad_multi", *head, None, 0, None, 0, None, _lib.stream_of(V0))
-        return outs
-    plan, addr = _det.new_plan()
-    L.call("omni_gemm_batched_wgrad_multi", *head, None, 0, None, 0, addr, _lib.stream_of(V0))
-    ws, wsf, ctr, nctr = _det.workspace(V0, plan)
-    L.call("omni_gemm_batched_wgrad_multi", *head, _lib.ptr(ws), wsf, _lib.ptr(ctr), nctr, None, _lib.stream_of(V0))
     return outs
 
 

@@ -10,6 +10,7 @@ L2) on bottom-up gradient tensors (profiles/r03_grad_run_to_run_spread.txt).  Ro
     kernel family, and hand the workspace counters back zeroed;
   * GPU: two executions of the full-size training step (BASELINE configs[1]: 4 x 512 x 512, default config) give BIT-IDENTICAL
     losses and gradients for every parameter -- eager launches and staged hipGraph replays."""
+import ctypes
 import os
 
 import pytest
@@ -111,6 +112,71 @@ def test_ordered_reductions_equal_atomic_ones_emulated(emu_lib):
 @pytest.mark.gpu
 def test_ordered_reductions_equal_atomic_ones_gpu(hip_lib):
     _run_ordered_equals_atomic("cuda")
+
+
+class _PlanRecorder:
+    """stand-in for the loaded library: records every call and answers a plan call (plan address set) with `report`"""
+
+    def __init__(self, report):
+        self.report, self.calls = report, []
+
+    def call(self, name, *args):
+        self.calls.append((name, args))
+        if args[-2] is not None:
+            plan = (ctypes.c_longlong * 4).from_address(args[-2])
+            plan[0], plan[1], plan[2], plan[3] = self.report
+
+
+def test_plan_launch_protocol():
+    """detmode.plan_launch is the one implementation of the `plan` protocol of include/omni3d_hip.h: exactly two calls of the named entry --
+    the plan call (plan address set, workspace / counters / launch-only arguments null) and the launch (plan null, the workspace and the
+    counters the reported plan asks for) -- with the same leading arguments, the plan's answer in place of the request; a plan that
+    reports no split allocates nothing when the domain's counter block exists"""
+    from torch.utils._python_dispatch import TorchDispatchMode
+    from omni3d_amd.kernels import detmode
+
+    class Ops(TorchDispatchMode):
+        seen = []
+
+        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+            self.seen.append(func.__name__)
+            return func(*args, **(kwargs or {}))
+
+    like = torch.zeros(1)
+    head = tuple(range(101, 117))       # omni_conv2d_fwd_det: 16 leading arguments up to `relu`
+    with detmode.domain("plan-launch-test"):
+        try:
+            # split tail, request fed back (tile, splits), launch-only arguments (statistics buffer, rows, block-count cell)
+            L = _PlanRecorder((2, 3, 5, 640))
+            detmode.plan_launch(L, "omni_conv2d_fwd_det", like, head, ask=(0, 9), late=(7001, 64, 7002))
+            block = detmode._counters[detmode._key(like)]
+            assert [n for n, _ in L.calls] == ["omni_conv2d_fwd_det"] * 2
+            (_, a), (_, b) = L.calls
+            assert a[:16] == head and b[:16] == head
+            assert a[16:18] == (0, 9) and a[18:21] == (None, 0, None) and a[21:25] == (None, 0, None, 0) and a[25] and a[26] is None
+            assert b[16:18] == (2, 3) and b[18:21] == (7001, 64, 7002)
+            assert b[21] and b[22] == 640 and b[23] == block.data_ptr() and b[24] == 5 and b[25] is None and b[26] is None
+            assert len(a) == len(b) == 27
+            # nothing fed back (the weight gradient's tile is part of the head), and a plan without a split: the existing block serves,
+            # no tensor is created
+            L = _PlanRecorder((1, 1, 0, 0))
+            with Ops() as ops:
+                detmode.plan_launch(L, "omni_conv2d_wgrad_det", like, head)
+            assert ops.seen == []
+            (n0, a), (n1, b) = L.calls
+            assert n0 == n1 == "omni_conv2d_wgrad_det" and a[:16] == b[:16] == head
+            assert a[16:20] == (None, 0, None, 0) and a[20] and a[21] is None
+            assert b[16:] == (None, 0, block.data_ptr(), 1, None, None)
+            # workspace-only tail of the stem weight gradients: at least one float behind a non-null pointer, the reported size passed on
+            for floats in (0, 100):
+                L = _PlanRecorder((0, 0, 0, floats))
+                detmode.plan_launch(L, "omni_stem_conv_wgrad_det", like, head[:12], counters=False)
+                (n0, a), (n1, b) = L.calls
+                assert n0 == n1 == "omni_stem_conv_wgrad_det" and a[:12] == b[:12] == head[:12]
+                assert a[12:14] == (None, 0) and a[14] and a[15] is None
+                assert b[12] and b[13:] == (floats, None, None)
+        finally:
+            detmode._counters.pop(detmode._key(like), None)
 
 
 def _step_outputs(model, batch, E, gold):
