@@ -62,10 +62,8 @@ int omni_conv2d_fwd(const float* x, const float* w, const float* bias, float* ou
 int omni_conv2d_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K, int R,
                       int S, int stride, int pad, int lddy, int lddx, int accumulate, void* stream);
 
-/* grad wrt the weights: dw (K,R,S,C) overwritten, or atomically accumulated into when accumulate != 0 (weight
- * gradients land directly in the flat gradient bucket).  Split-K over output pixels, fp32 atomics. */
-int omni_conv2d_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K, int R,
-                      int S, int stride, int pad, int ldx, int lddy, int accumulate, void* stream);
+/* grad wrt the weights (omni_conv2d_wgrad_algo below): dw (K,R,S,C) overwritten, or atomically accumulated into when
+ * accumulate != 0 (weight gradients land directly in the flat gradient bucket).  Split-K over output pixels, fp32 atomics. */
 
 /* The same three operations with the ALGORITHM chosen by the caller instead of by the launcher's shape heuristics
  * (cuDNN's "algo" argument; the reference reaches it through torch.backends.cudnn.benchmark, tools/train_net.py sets
@@ -141,13 +139,11 @@ int omni_conv2d_wgrad_multi_det(const void* const* xs, const int* cs, int nsrc, 
  * dla.py:46-66 (BasicBlock), :162-172 (Root), :214 (project), :244,294 (conv levels).
  * x, y, residual [nullable]: NHWC fp32 with P = N*H*W pixels, C % 4 == 0, C <= 1024.
  * running_mean/var [nullable] updated with `momentum` (unbiased var) like F.batch_norm.
- * Outputs kept for backward: mean_rstd (2C), scale_shift (2C).  ws: >= 2C*258 doubles scratch. */
-int omni_bn_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y,
-                float* running_mean, float* running_var, float* mean_rstd, float* scale_shift, double* ws,
-                int P, int C, float eps, float momentum, int relu, void* stream);
-
-/* Round 5: the same forward / backward with every variant behind explicit arguments (the entry points above and the *_partials /
- * *_carry forms below are these with defaults).  partial [nullable] = [nblk][2][C] statistics rows already written by the producer of x
+ * Outputs kept for backward: mean_rstd (2C), scale_shift (2C).  ws: >= 2C*258 doubles scratch.
+ * Backward: dy = grad wrt y; dres [nullable] = grad wrt residual; ws >= 2C*258 doubles, coef 3C floats scratch.  relu: 0 = none;
+ * 1 = mask dy by y > 0, y = the forward output; 2 = layers without residual: `y` points at the forward pass's scale_shift (2C floats)
+ * and the mask is recomputed as x * scale + shift > 0, the output tensor is not read.
+ * Every variant sits behind explicit arguments.  partial [nullable] = [nblk][2][C] statistics rows already written by the producer of x
  * (forward) / of dy (backward); NULL = a reduction pass runs first (ws as above).  ldy / lddy / ldc: pixel pitches in floats of y, dy
  * and res_carry (0 or C = dense; a DLA Root child, dla.py:171, is written into / read from its channel slice of the concatenated
  * tensor).  fuse_rows: with <= fuse_rows partial rows and C % 16 == 0 the finalize is folded into the apply launch -- every workgroup
@@ -180,14 +176,6 @@ int omni_bn_frozen_bwd(const float* x, const float* dy, long long lddy, const fl
                        const float* running_mean, const float* running_var, float eps, float* dx, float* dres, const float* res_carry,
                        long long ldc, float* dgamma, float* dbeta, float* ws, long long ws_floats, int P, int C, int relu,
                        int accumulate_param_grads, void* stream);
-
-/* backward of omni_bn_fwd.  dy = grad wrt y; dres [nullable] = grad wrt residual;
- * ws >= 2C*258 doubles, coef 3C floats scratch.  relu: 0 = none; 1 = mask dy by y > 0, y = the forward output;
- * 2 = layers without residual: `y` points at the forward pass's scale_shift (2C floats) and the mask is recomputed as
- * x * scale + shift > 0, the output tensor is not read. */
-int omni_bn_bwd(const float* x, const float* dy, const float* y, const float* gamma, const float* mean_rstd,
-                float* dx, float* dres, float* dgamma, float* dbeta, double* ws, float* coef, int P, int C,
-                int relu, int accumulate_param_grads, void* stream);
 
 /* nn.MaxPool2d(2, stride=2) (dla.py:209) forward / backward, NHWC. */
 int omni_maxpool2_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream);
@@ -233,17 +221,14 @@ int omni_upsample2_bwd(const float* dout, float* dtop, int N, int H, int W, int 
  * later reads what the earlier ones produced (`carry`: NHWC, same extent as the output, pixel pitch ldc floats -- a whole tensor or a
  * channel slice of the Root's concatenated gradient; ldc >= channels, ldc % 4 == 0, 16-byte aligned) and writes the sum:
  *   omni_wino_out_carry      y = A^T M A + carry                 (Winograd data gradient, tile as omni_wino_out)
- *   omni_bn_bwd_carry        dres = masked dy + res_carry        (res_carry nullable: then == omni_bn_bwd)
+ *   omni_bn_bwd_algo         dres = masked dy + res_carry        (res_carry nullable)
  *   omni_maxpool2_bwd_carry  dx = routed dy + carry              (carry nullable; H, W even when given)
  *   omni_upsample2_bwd_carry dtop = 2x2 block sums + carry       (carry nullable)
  *   omni_subsample2_bwd_carry dx = carry + dy at the even pixels (the p6 = p5[::2, ::2] level; one pass instead of fill + scatter + add)
  * The implicit-GEMM data gradient takes the same role through omni_conv2d_dgrad(accumulate = 1, lddx = the carry's pitch).
- * omni_bn_bwd_carry / omni_maxpool2_bwd_carry also read their OUTPUT gradient dy with a pixel pitch lddy (same constraints): a
+ * omni_bn_bwd_algo / omni_maxpool2_bwd_carry also read their OUTPUT gradient dy with a pixel pitch lddy (same constraints): a
  * Root child with no other consumer gets its slice of the concatenated gradient without a copy. */
 int omni_wino_out_carry(const float* M, const float* carry, long long ldc, float* y, int N, int H, int W, int K, int tile, void* stream);
-int omni_bn_bwd_carry(const float* x, const float* dy, long long lddy, const float* y, const float* gamma, const float* mean_rstd, float* dx,
-                      float* dres, const float* res_carry, long long ldc, float* dgamma, float* dbeta, double* ws, float* coef,
-                      int P, int C, int relu, int accumulate_param_grads, void* stream);
 int omni_maxpool2_bwd_carry(const float* x, const float* dy, long long lddy, const float* carry, long long ldc, float* dx, int N, int H,
                             int W, int C, void* stream);
 int omni_subsample2_bwd_carry(const float* dy, const float* carry, long long ldc, float* dx, int N, int H, int W, int C, void* stream);
@@ -294,16 +279,12 @@ int omni_nms_sorted(const float* boxes, const int* counts, const int* valid, int
  * rpn.py:62,100; roi_heads/roi_heads.py:881,892.  out (N, M). */
 int omni_pairwise_iou(const float* boxes1, int N, const float* boxes2, int M, int mode, float* out, void* stream);
 
-/* RPNWithIgnore.label_and_sample_anchors, matching half (rpn.py:62-75) = pairwise_iou + detectron2
+/* RPNWithIgnore.label_and_sample_anchors, matching half (rpn.py:62-75; omni_rpn_match_draw below) = pairwise_iou + detectron2
  * Matcher(thr, labels, allow_low_quality) + per-GT best anchor, for a batch of B images.
  * anchors (A,4); gt: concatenated valid GT boxes (G,4) with gt_off (B+1); expo (B,A) Exp(1) variates.
  * Outputs (B,A): matched_val, matched_idx (GT index inside the image), match_label int8,
  * key_pos / key_neg = (iou+eps)/E for the positive / negative candidates (-inf elsewhere) whose
  * top-k is the IoU-weighted multinomial of rpn.py:318,322; gt_best_idx (G); gt_best_bits (G) scratch. */
-int omni_rpn_match(const float* anchors, int A, const float* gt, const int* gt_off, int B, int G, float thr_lo,
-                   float thr_hi, int l0, int l1, int l2, int allow_low_quality, const float* expo, float eps,
-                   float* matched_val, int* matched_idx, signed char* match_label, int* gt_best_bits,
-                   int* gt_best_idx, float* key_pos, float* key_neg, void* stream);
 
 /* Second half (rpn.py:79-105): labels (B,A) int8 in {-1,0,1} from the sampled top-k lists, forced
  * best-anchor positives and ignore regions (ign (Gi,4), ign_off (B+1)).  counts (B,2) [nullable]. */
@@ -369,15 +350,10 @@ int omni_rpn_mask_scores(const float* scores, const int* keep, long long n, floa
 int omni_rpn_collect(const float* boxes, const float* top_v, const int* top_i, int B, int N, int P, float* prop,
                      int* count, void* stream);
 
-/* ROIHeads3D.label_and_sample_proposals (roi_heads.py:862-929): append GT, Matcher(iou_thr), ignore
+/* ROIHeads3D.label_and_sample_proposals (roi_heads.py:862-929; omni_roi_sample_draw below): append GT, Matcher(iou_thr), ignore
  * regions, IoU-weighted sampling of <= nfg_max foreground + background up to batch_per_image.
  * expo (B, 2048).  Outputs (B, batch_per_image): boxes, class (num_classes = bg, -2 = padding),
  * global GT row, matched IoU; counts (B,2). */
-int omni_roi_sample(const float* prop_boxes, const int* prop_count, int B, int pmax, const float* gt,
-                    const int* gt_cls, const int* gt_off, const float* ign, const int* ign_off, const float* expo,
-                    float iou_thr, float ignore_thresh, float eps, int num_classes, int batch_per_image,
-                    int nfg_max, int append_gt, float* out_boxes, int* out_cls, int* out_gt, float* out_iou,
-                    int* out_counts, void* stream);
 /* Round 6 forms of the two subsampling steps: expo == NULL draws the Exp(1) variates INSIDE the kernel (csrc/philox.h: Philox4x32-10
  * keyed by draw_state[0] = seed, counter (element, row, draw_state[1]); the last workgroup to take its ticket advances
  * draw_state[1]; ticket: one zeroed int32) -- replaces `Tensor.exponential_()` + torch's graph-safe generator bookkeeping, six
@@ -495,27 +471,21 @@ int omni_cuboid_corners(const float* box3d, const float* R, int n, float* verts,
  * The conv -> BatchNorm pairs of the bottom-up (cubercnn/modeling/backbone/dla.py:46-66,162-172,214,244; torchvision
  * BasicBlock via resnet.py:17-27): the convolution / Winograd output transform / stem kernel also writes per-workgroup
  * partial sums and sums of squares of its output, stats [rows][2][K] floats, so training-mode BatchNorm skips its own
- * statistics pass (omni_bn_fwd_partials = finalize + apply).  *nblk_out = partial rows written; 0 means "not produced"
- * (split reduction chosen, buffer too small, unsupported channel count) and the caller uses omni_bn_fwd. */
+ * statistics pass (omni_bn_fwd_algo with `partial` = finalize + apply).  *nblk_out = partial rows written; 0 means "not produced"
+ * (split reduction chosen, buffer too small, unsupported channel count) and the caller passes partial = NULL to omni_bn_fwd_algo. */
 int omni_conv2d_fwd_stats(const float* x, const float* w, float* out, int N, int H, int W, int C, int K, int R, int S,
                           int stride, int pad, int ldx, int ldo, float* stats, int stats_rows, int* nblk_out, void* stream);
 int omni_wino_out_stats(const float* M, float* y, int N, int H, int W, int K, int tile, float* stats, int stats_rows,
                         int* nblk_out, void* stream);
 /* The same idea in the backward pass: the Winograd data-gradient transform of the convolution ABOVE a BatchNorm(+ReLU) writes that
  * BatchNorm's output gradient dy, and emits the per-workgroup partial sums (sum dz, sum dz * xhat) its backward pass starts with
- * (dz = dy masked by x * scale + shift > 0 when scale_shift != NULL); omni_bn_bwd_partials = finalize + apply on those rows
- * (arguments as omni_bn_bwd).  *nblk_out == 0: not produced, run omni_bn_bwd. */
+ * (dz = dy masked by x * scale + shift > 0 when scale_shift != NULL); omni_bn_bwd_algo with `partial` = finalize + apply on those
+ * rows.  *nblk_out == 0: not produced, omni_bn_bwd_algo runs its own reduction pass. */
 int omni_wino_out_bn_bwd_stats(const float* M, float* y, int N, int H, int W, int K, int tile, const float* bn_x,
                                const float* mean_rstd, const float* scale_shift, float* stats, int stats_rows, int* nblk_out,
                                void* stream);
-int omni_bn_bwd_partials(const float* x, const float* dy, const float* y, const float* gamma, const float* mean_rstd,
-                         const float* partial, int nblk, float* dx, float* dres, float* dgamma, float* dbeta, float* coef,
-                         int P, int C, int relu, int accumulate_param_grads, void* stream);
 int omni_stem_conv_fwd_stats(const float* x, const float* w, float* out, int N, int H, int W, int C, int K, int R, int ldx,
                              int ldo, float* stats, int stats_rows, int* nblk_out, void* stream);
-int omni_bn_fwd_partials(const float* x, const float* partial, int nblk, const float* gamma, const float* beta,
-                         const float* residual, float* y, float* running_mean, float* running_var, float* mean_rstd,
-                         float* scale_shift, int P, int C, float eps, float momentum, int relu, void* stream);
 
 /* ---------------------------------------------------------------- GEMM engine (csrc/gemm_engine.hip)
  * The cuBLAS calls behind nn.Linear (detectron2 FastRCNNConvFCHead; cubercnn/modeling/roi_heads/cube_head.py:70,108-163),
@@ -667,16 +637,14 @@ int omni_wino_dweights_multi(const void* const* dU, const void* const* dg, const
                              void* stream);
 /* `batch` independent dense GEMMs in one launch (the 16 Winograd points):
  * fwd: out[b](M,K) = x[b](M,C) * w[b](K,C)^T;  wgrad: dw[b](K,C) = dy[b](M,K)^T * x[b](M,C) (overwrites dw). */
-int omni_gemm_batched_fwd(const float* x, const float* w, float* out, int batch, int M, int C, int K, void* stream);
 /* algo: 0 = automatic | 1 = persistent workgroups walking the (problem, tile) list (`workgroups` of them, multiple of 8,
  * 0 = default; C % 32 == 0) | 2 = one 128x128 tile per workgroup | 3 = one 64x64 tile per workgroup | 4 = 64x64 tiles with
  * 2-4 slabs of buffer-load prefetch in flight (short reductions: the small-map point GEMMs; C % 64 == 0) */
 int omni_gemm_batched_fwd_algo(const float* x, const float* w, float* out, int batch, int M, int C, int K, int algo,
                                int workgroups, void* stream);
-int omni_gemm_batched_wgrad(const float* x, const float* dy, float* dw, int batch, int M, int C, int K, void* stream);
 /* algo: 0 = automatic | 1 = the implicit-GEMM weight-gradient tiles (128x128 / 64x64) | 2 = 64x64 tiles with 4 slabs of
- * buffer-load prefetch in flight (short reductions).  Same call site as omni_gemm_batched_wgrad (the Winograd-domain weight
- * gradient of torch.nn.Conv2d's backward, dla.py:43-51). */
+ * buffer-load prefetch in flight (short reductions).  The call site is the Winograd-domain weight
+ * gradient of torch.nn.Conv2d's backward (dla.py:43-51). */
 int omni_gemm_batched_wgrad_algo(const float* x, const float* dy, float* dw, int batch, int M, int C, int K, int algo,
                                  void* stream);
 /* deterministic form (see omni_conv2d_fwd_det): the row splits of the Winograd-domain weight gradient meet in `ws` in split order */

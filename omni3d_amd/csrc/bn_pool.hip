@@ -843,7 +843,6 @@ static inline void fin_geometry(int P, int C, int& CG, int& PC, int& chunk, int&
     grid = (CG * PC + 7) / 8 * 8;
 }
 static inline bool fin_fusable(int C, int nblk, int fuse_rows) { return fuse_rows > 0 && nblk <= fuse_rows && (C % GC) == 0; }
-static const int BN_FUSE_ROWS_DEFAULT = 512;
 
 // Training-mode BatchNorm forward on NHWC x (P = N*H*W pixels, C channels, C % 4 == 0, C <= 4096).
 // partial [nullable]: [nblk][2][C] per-block sums / sums of squares already made by the PRODUCER of x (conv / Winograd / stem
@@ -881,23 +880,6 @@ int omni_bn_fwd_algo(const float* x, const float* partial, int nblk, const float
     return omni_launch_status();
 }
 
-int omni_bn_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y,
-                float* running_mean, float* running_var, float* mean_rstd, float* scale_shift, double* ws, int P, int C,
-                float eps, float momentum, int relu, void* stream) {
-    return omni_bn_fwd_algo(x, nullptr, 0, gamma, beta, residual, y, C, running_mean, running_var, mean_rstd, scale_shift, ws, P, C, eps,
-                            momentum, relu, BN_FUSE_ROWS_DEFAULT, stream);
-}
-
-// The same forward with the statistics pass already done by the PRODUCER of x (conv / Winograd / stem epilogues):
-// partial [nblk][2][C] floats = per-block sums and sums of squares.
-int omni_bn_fwd_partials(const float* x, const float* partial, int nblk, const float* gamma, const float* beta, const float* residual,
-                         float* y, float* running_mean, float* running_var, float* mean_rstd, float* scale_shift, int P, int C,
-                         float eps, float momentum, int relu, void* stream) {
-    if (partial == nullptr) return OMNI_ERR_ARG;
-    return omni_bn_fwd_algo(x, partial, nblk, gamma, beta, residual, y, C, running_mean, running_var, mean_rstd, scale_shift, nullptr, P, C,
-                            eps, momentum, relu, BN_FUSE_ROWS_DEFAULT, stream);
-}
-
 // Inference / frozen BN: y = relu?(x*scale + shift (+res)) with caller-provided scale_shift (2C).
 int omni_bn_apply(const float* x, const float* scale_shift, const float* residual, float* y, int P, int C, int relu,
                   void* stream) {
@@ -914,7 +896,7 @@ static int bad_carry(const float* carry, long long ldc, int C) {
     return carry != nullptr && (ldc < C || (ldc & 3) || (((unsigned long long)carry) & 15));
 }
 
-// Backward of omni_bn_fwd(_algo) with gradient fan-in on the residual: dres = (masked dy) + res_carry, res_carry [nullable] an NHWC
+// Backward of omni_bn_fwd_algo with gradient fan-in on the residual: dres = (masked dy) + res_carry, res_carry [nullable] an NHWC
 // tensor of the same extent with pixel pitch ldc floats (what the other consumers of the residual tensor already contributed to its
 // gradient); dy with pixel pitch lddy floats (a channel slice of the DLA Root's concatenated gradient is read where it lies).
 // partial [nullable]: [nblk][2][C] reductions (sum dz, sum dz * xhat) already made by the kernel that produced dy
@@ -952,29 +934,6 @@ int omni_bn_bwd_algo(const float* x, const float* dy, long long lddy, const floa
     return omni_launch_status();
 }
 
-int omni_bn_bwd_carry(const float* x, const float* dy, long long lddy, const float* y, const float* gamma, const float* mean_rstd, float* dx,
-                      float* dres, const float* res_carry, long long ldc, float* dgamma, float* dbeta, double* ws, float* coef, int P,
-                      int C, int relu, int accumulate_param_grads, void* stream) {
-    return omni_bn_bwd_algo(x, dy, lddy, y, gamma, mean_rstd, nullptr, 0, dx, dres, res_carry, ldc, dgamma, dbeta, ws, coef, P, C, relu,
-                            accumulate_param_grads, BN_FUSE_ROWS_DEFAULT, stream);
-}
-
-int omni_bn_bwd(const float* x, const float* dy, const float* y, const float* gamma, const float* mean_rstd, float* dx,
-                float* dres, float* dgamma, float* dbeta, double* ws, float* coef, int P, int C, int relu,
-                int accumulate_param_grads, void* stream) {
-    return omni_bn_bwd_carry(x, dy, C, y, gamma, mean_rstd, dx, dres, nullptr, 0, dgamma, dbeta, ws, coef, P, C, relu,
-                             accumulate_param_grads, stream);
-}
-
-// omni_bn_bwd with the reductions already done by the kernel that produced dy (omni_wino_out_bn_bwd_stats): finalize + apply.
-int omni_bn_bwd_partials(const float* x, const float* dy, const float* y, const float* gamma, const float* mean_rstd,
-                         const float* partial, int nblk, float* dx, float* dres, float* dgamma, float* dbeta, float* coef, int P,
-                         int C, int relu, int accumulate_param_grads, void* stream) {
-    if (partial == nullptr) return OMNI_ERR_ARG;
-    return omni_bn_bwd_algo(x, dy, C, y, gamma, mean_rstd, partial, nblk, dx, dres, nullptr, 0, dgamma, dbeta, nullptr, coef, P, C, relu,
-                            accumulate_param_grads, BN_FUSE_ROWS_DEFAULT, stream);
-}
-
 // Frozen (eval-mode) BatchNorm inside a training pass (freeze_bn, MODEL.USE_BN False): y = relu?(x * s + t (+ residual)) with
 // s = gamma * rsqrt(running_var + eps), t = beta - running_mean * s made in the launch from the live parameters; the same bits as
 // omni_bn_apply with the eval-mode (scale, shift) of layers.py.  Nothing else is written.
@@ -991,7 +950,7 @@ int omni_bn_frozen_fwd(const float* x, const float* gamma, const float* beta, co
 // Backward of omni_bn_frozen_fwd: ONE pass writes dx = g * s and dres = g (+ res_carry) [dres nullable] and per-chunk partials of
 // (sum g, sum g * xhat) to ws; a fixed-order finalize writes dgamma / dbeta (accumulate_param_grads: adds to them).  No atomics: two
 // runs give the same bits.  g = dy masked by the ReLU -- relu 0: none | 1: y > 0 (y = the forward output) | 2: x * s + t > 0
-// recomputed (forward without residual; y unused).  dy has pixel pitch lddy, res_carry pitch ldc (as omni_bn_bwd_carry).
+// recomputed (forward without residual; y unused).  dy has pixel pitch lddy, res_carry pitch ldc (as omni_bn_bwd_algo).
 // dgamma == dbeta == NULL: no parameter gradients (no partials, no finalize).  ws: >= ws_floats floats, 2 * C * 512 always suffice.
 int omni_bn_frozen_bwd(const float* x, const float* dy, long long lddy, const float* y, const float* gamma, const float* beta,
                        const float* running_mean, const float* running_var, float eps, float* dx, float* dres, const float* res_carry,

@@ -49,7 +49,7 @@ struct ConvP {
     // read-modify-write (every output element has exactly one owner per launch) instead of atomics
     float* ws;
     unsigned* ctr;
-    // multi-source input (round 5, the DLA Root): nsrc > 0 asks the 1 x 1 / stride 1 forward kernel (PF == 1) to read the input
+    // multi-source input (round 5, the DLA Root): nsrc > 0 asks the 1 x 1 / stride 1 forward kernel to read the input
     // channels [coff[s], coff[s + 1]) from the dense NHWC tensor xs[s] (pitch = its own channel count) -- torch.cat(xs, 1) is never
     // formed.  Every coff[s] is a multiple of the slab depth, so a slab has one source.
     const float* xs[OMNI_MAX_SRC];
@@ -154,11 +154,12 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[WM][WN]) {
 // forward:  out[m, n] = sum_{r,s,c} x[pix(m; r, s), c] * w[n, r, s, c] (+ bias[n]) (ReLU)
 //   GEMM M = N*OH*OW, N = K, reduction Kd = R*S*C.  A and B k-contiguous in LDS.
 // =================================================================================================
-// PF = register-staged prefetch depth: the global loads of slab kt + PF are issued while slab kt is in the MFMAs.  PF = 1 is the
-// classic double buffer (one MFMA phase per load in flight).  The small-map problems of this network (Winograd point GEMMs of DLA
-// levels 3-5, reduction depth 128-512 = 4-16 slabs, 64x64 tiles so that the launch has >= 2 workgroups per CU) are bound by that
-// dependency chain -- a 64x64 tile's MFMA phase is 0.43 us per wave against ~2 us of load latency -- so they run PF = 3: three
-// slabs (48 VGPRs) in flight per thread, LDS still double buffered.
+// PF = register-staged prefetch depth.  Every instantiation has PF = 1, the classic double buffer: the global loads of slab kt + 1
+// are issued while slab kt is in the MFMAs.  A deeper ring gained nothing on the direct convolutions (profiles/r05_ab_conv64_pf.log)
+// and the small-map point GEMMs, which are bound by the load -> LDS -> MFMA chain, have their own kernel (gemm_nt_pf_kernel).  The
+// parameter stays so that the kernels keep the names the recorded traces know them by, and the PF > 1 ring below stays as
+// uninstantiated text: deleting it, although no instantiation compiles it, moved the register allocation of two live
+// instantiations (<64,64>: 93 -> 95 VGPRs, <128,64>: 109 -> 110), and this kernel's code generation is not to change here.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int BKX = 16, int PF = 1>
 __global__ void __launch_bounds__(256) conv_fwd_kernel(ConvP p) {
     constexpr int WM = BM / (32 * WAVES_M), WN = BN / (32 * WAVES_N);
@@ -880,23 +881,11 @@ __device__ __forceinline__ void conv_wgrad_body_pf(ConvP& p, int pix_per_split, 
         }
 }
 
-// xcd_splits: every tile of ONE pixel split reads the same dy rows (all (tap, c) tiles) and the same x pixels (all K tiles), but in the
-// launch order (tile fastest, workgroup ids round-robin over the 8 XCDs) the tiles of a split land on eight different L2s and each
-// fetches that range for itself (PMC, 3x3/s2 64->128: 145 MB fetched for 25 MB of operands).  With the flag the first 8 * (splits / 8)
-// splits are dealt out so that XCD q runs splits q, q + 8, ... with all their tiles; the remaining splits keep the plain order.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int BK, int PF>
-__global__ void __launch_bounds__(256) conv_wgrad_pf_kernel(ConvP p, int pix_per_split, int xcd_splits) {
+__global__ void __launch_bounds__(256) conv_wgrad_pf_kernel(ConvP p, int pix_per_split) {
     __shared__ __attribute__((aligned(16))) float smem[2 * BK * (BM + BN)];
-    int bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
     const int gx = (int)gridDim.x, gy = (int)gridDim.y;
-    if (xcd_splits) {
-        const int lin = by * gx + bx, gy8 = gy & ~7;
-        if (lin < gx * gy8) {
-            const int q = lin & 7, k = lin >> 3;
-            by = q + 8 * (k / gx);
-            bx = k - (k / gx) * gx;
-        }
-    }
     conv_wgrad_body_pf<BM, BN, WAVES_M, WAVES_N, BK, PF>(p, pix_per_split, bx, by, gx, gy, smem);
 }
 
@@ -1031,9 +1020,6 @@ struct GemmTP {
     long ab, bb, ob;       // element strides between the gridDim.z problems
     float* ws;             // deterministic split reduction (split_reduce.h); ctr == nullptr: fp32 atomics
     unsigned* ctr;
-    int batch = 0;         // number of problems (read by the persistent form only: the others take it from the grid)
-    int nt_out = 0;        // 1: `nt` stores for out (outputs far larger than the 32 MB of L2 that the consumer streams from HBM anyway:
-                           // tools/probes/probe_gemm_nt.hip -- the p2 point GEMM 176 -> 170 us; smaller outputs stay L2-resident for the consumer)
 };
 
 template <int PF>
@@ -1107,136 +1093,10 @@ __global__ void __launch_bounds__(256) gemm_nt_pf_kernel(GemmTP p) {
     }
     const int l31 = lane & 31, h = lane >> 5;
     const int n = n0 + wn * 32 + l31;
-    if (p.nt_out) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (m < p.M && n < p.N) __builtin_nontemporal_store(acc[0][0][r], out + (long)m * p.N + n);
-        }
-        return;
-    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (m < p.M && n < p.N) out[(long)m * p.N + n] = acc[0][0][r];
-    }
-}
-
-// Persistent form of gemm_nt_pf_kernel for launches of MANY tiles (the 128x128-map point GEMMs: 9216 tiles = 9 rounds of the
-// 1024 resident workgroups).  PMC on the one-tile-per-workgroup form showed 3.48 of 4 waves per SIMD resident on average and the MFMA
-// pipe idle 28 % of the time: every tile pays a workgroup launch and a prologue whose first slab comes from HBM with nothing to
-// overlap it.  Here gridDim.x workgroups (a multiple of 8) each walk their XCD's chunk of the (problem, tile) sequence with a
-// stride of gridDim.x / 8, and the slab stream runs THROUGH the tile boundaries: the load cursor (item, koff) is PF slabs ahead
-// of the MFMAs, so the first slabs of the next tile are in flight while the last ones of this tile multiply; a tile ends with its
-// 16 stores and a zeroed accumulator, nothing else.  Same tiles, same slab order, same MFMA chain per output element as
-// gemm_nt_pf_kernel: results are bit-identical.  One resource over ALL problems (offsets carry prob * stride; the launcher checks
-// batch * stride * 4 < 2 GiB), so no descriptor changes inside the loop.
-template <int PF>
-__global__ void __launch_bounds__(256) gemm_nt_pfp_kernel(GemmTP p) {
-    constexpr int BM = 64, BN = 64, BKX = 32, BKP = BKX + 4, KQ = BKX / 4, RPP = 256 / KQ, AI = BM / RPP, BI = BN / RPP;
-    __shared__ __attribute__((aligned(16))) float smem[2 * (BM + BN) * BKP];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int kq = tid % KQ, lrow = tid / KQ;
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN, per_problem = tiles_m * tiles_n;
-    const int total = per_problem * p.batch;
-    // this XCD's contiguous chunk of the item sequence (xcd_chunked's split), walked by its gridDim.x / 8 workgroups in rounds
-    const int x8 = (int)blockIdx.x & 7, stride = (int)gridDim.x >> 3;
-    const int q8 = total / 8, r8 = total % 8;
-    const int first = x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8;
-    const int last = first + q8 + (x8 < r8 ? 1 : 0);
-    int cp_item = first + ((int)blockIdx.x >> 3);
-    if (cp_item >= last) return;
-    const omni_rsrc_t ra_ = omni_make_rsrc(p.A, (unsigned)((long)p.batch * p.ab * 4));
-    const omni_rsrc_t rb_ = omni_make_rsrc(p.B, (unsigned)((long)p.batch * p.bb * 4));
-    const int k_end = p.K * 4;                      // bytes per row
-    int a_off[AI], b_off[BI];
-    int ld_item = cp_item, koff = 0;                // load cursor: the slab the NEXT load_slab() fetches
-    auto set_load_item = [&]() {
-        const bool ok = ld_item < last;
-        const int prob = ld_item / per_problem, tix = ld_item - prob * per_problem;
-        const int tile_m = tix / tiles_n, tile_n = tix - tile_m * tiles_n;
-#pragma unroll
-        for (int i = 0; i < AI; ++i) {
-            const int m = tile_m * BM + lrow + RPP * i;
-            a_off[i] = (ok && m < p.M) ? (int)(((long)prob * p.ab + (long)m * p.K + kq * 4) * 4) : OMNI_OOB;
-        }
-#pragma unroll
-        for (int j = 0; j < BI; ++j) {
-            const int n = tile_n * BN + lrow + RPP * j;
-            b_off[j] = (ok && n < p.N) ? (int)(((long)prob * p.bb + (long)n * p.K + kq * 4) * 4) : OMNI_OOB;
-        }
-    };
-    set_load_item();
-    float4 ra[PF][AI], rb[PF][BI];
-    auto load_slab = [&](const int st) {
-#pragma unroll
-        for (int i = 0; i < AI; ++i) ra[st][i] = bufld4(ra_, a_off[i] + koff);      // OMNI_OOB + koff stays out of range (koff < 2^30)
-#pragma unroll
-        for (int j = 0; j < BI; ++j) rb[st][j] = bufld4(rb_, b_off[j] + koff);
-        koff += BKX * 4;
-    };
-    // the reduction depth is a multiple of PF slabs, so a tile's last slab is always fetched at the same place of the unrolled
-    // body (u == PF - 2) and after the PF loads of the prologue: the only two places that look for the end of the row
-    auto next_tile_if_row_done = [&]() {
-        if (koff == k_end) {                        // wave-uniform: on to the first slab of this workgroup's next tile
-            koff = 0;
-            ld_item += stride;
-            set_load_item();
-        }
-    };
-    auto store_slab = [&](int buf, const int st) {
-        float* As = smem + buf * (BM + BN) * BKP;
-        float* Bs = As + BM * BKP;
-#pragma unroll
-        for (int i = 0; i < AI; ++i) *reinterpret_cast<float4*>(As + (lrow + RPP * i) * BKP + kq * 4) = ra[st][i];
-#pragma unroll
-        for (int j = 0; j < BI; ++j) *reinterpret_cast<float4*>(Bs + (lrow + RPP * j) * BKP + kq * 4) = rb[st][j];
-    };
-    f32x16 acc[1][1];
-    zero_acc<1, 1>(acc);
-#pragma unroll
-    for (int s = 0; s < PF; ++s) load_slab(s);
-    next_tile_if_row_done();
-    store_slab(0, 0);
-    load_slab(0);
-    omni_barrier_lds();
-    const int nk = p.K / BKX;                       // multiple of PF (launcher): stage and buffer parity carry over the tiles
-    const int l31 = lane & 31, h = lane >> 5;
-    for (; cp_item < last; cp_item += stride) {
-        for (int kt0 = 0; kt0 < nk; kt0 += PF) {
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int buf = u & 1;              // nk and PF even
-                store_slab(buf ^ 1, (u + 1) % PF);
-                load_slab((u + 1) % PF);
-                if (u == PF - 2) next_tile_if_row_done();
-                const float* As = smem + buf * (BM + BN) * BKP;
-                mma_slab<1, 1, true, true, 0, 0, BKX>(As, As + BM * BKP, wm * 32, wn * 32, lane, acc);
-                omni_barrier_lds();
-            }
-        }
-        const int prob = cp_item / per_problem, tix = cp_item - prob * per_problem;
-        const int tile_m = tix / tiles_n, tile_n = tix - tile_m * tiles_n;
-        float* out = p.out + (long)prob * p.ob;
-        const int n = tile_n * BN + wn * 32 + l31;
-        const int mb = tile_m * BM + wm * 32 + 4 * h;
-        if (tile_m * BM + BM <= p.M && tile_n * BN + BN <= p.N) {
-            if (p.nt_out) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) __builtin_nontemporal_store(acc[0][0][r], out + (long)(mb + (r & 3) + 8 * (r >> 2)) * p.N + n);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) out[(long)(mb + (r & 3) + 8 * (r >> 2)) * p.N + n] = acc[0][0][r];
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = mb + (r & 3) + 8 * (r >> 2);
-                if (m < p.M && n < p.N) out[(long)m * p.N + n] = acc[0][0][r];
-            }
-        }
-        zero_acc<1, 1>(acc);
     }
 }
 
@@ -1369,12 +1229,9 @@ extern "C" {
 // split over gridDim.y with an atomic epilogue into a zeroed output.  Slab depth 32 (one barrier per 64
 // MFMAs per wave) measured +23 % over 16 on the 3x3 256->256 @128x128 shape (96 -> 119 TFLOP/s).
 // `tile` / `splits` select the algorithm explicitly (0 = the launcher's own choice, which is what omni_conv2d_fwd uses):
-//   tile 1 = 128x128, 2 = 64x64, 3 = 128x64, 4 = 256x32 (BM x BN output-pixel x output-channel tile), 5 = 64x64 with three
-//   slabs of register prefetch; splits >= 1 = number of
+//   tile 1 = 128x128, 2 = 64x64, 3 = 128x64, 4 = 256x32 (BM x BN output-pixel x output-channel tile); splits >= 1 = number of
 //   reduction splits (atomic epilogue into a zeroed output when > 1; needs ldo == K).  Used by tools/bench_kernels.py for A/B
 //   measurements and by tests that want a given tile on a small problem.
-constexpr bool WGRAD_XCD_ORDER_FC = true;     // fc-class weight gradients (one split): XCD-contiguous tile order (fc1: 615 -> 562 us, profiles/r03_fc_wgrad_xcd_order.log)
-constexpr bool FWD64_DEEP_PREFETCH = true;    // batched GEMMs on 64x64 tiles: gemm_nt_pf_kernel (profiles/r03_sweep_batched_gemm.log: 17-27 % faster on every small-map shape)
 
 // Deterministic-mode plumbing shared by the launchers below (split_reduce.h).  `ctr` != nullptr asks for run-to-run identical
 // results; `plan` != nullptr makes the launcher report what it WOULD launch -- plan[0] = tile, [1] = reduction splits, [2] = arrival
@@ -1415,7 +1272,7 @@ static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, fl
     p.nsrc = 0;
     if (nblk_out) *nblk_out = 0;
     if (ms != nullptr) {      // the input is the channel concatenation of ms->xs[]: 1 x 1 / stride 1, every width a multiple of 32
-        if (ms->nsrc < 1 || ms->nsrc > OMNI_MAX_SRC || R != 1 || S != 1 || stride != 1 || pad != 0 || tile == 5) return OMNI_ERR_ARG;
+        if (ms->nsrc < 1 || ms->nsrc > OMNI_MAX_SRC || R != 1 || S != 1 || stride != 1 || pad != 0) return OMNI_ERR_ARG;
         p.coff[0] = 0;
         for (int q = 0; q < OMNI_MAX_SRC; ++q) {
             const bool live = q < ms->nsrc;
@@ -1428,7 +1285,7 @@ static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, fl
         p.nsrc = ms->nsrc;
         p.x = p.xs[0];
     }
-    if (bad_geom(p) || (ldx & 3) || ldx < C || ldo < K || tile < 0 || tile > 5 || splits_req < 0) return OMNI_ERR_ARG;
+    if (bad_geom(p) || (ldx & 3) || ldx < C || ldo < K || tile < 0 || tile > 4 || splits_req < 0) return OMNI_ERR_ARG;
     if (splits_req > 1 && ldo != K) return OMNI_ERR_ARG;
     const long M = (long)N * p.OH * p.OW;
     if (M == 0) return OMNI_OK;
@@ -1464,8 +1321,8 @@ static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, fl
     }
     if (splits_req >= 1) splits = splits_req;
     if (splits > nslab) splits = nslab;
-    const int bm = tile == 1 ? 128 : (tile == 2 || tile == 5) ? 64 : tile == 3 ? 128 : 256;
-    const int bn = tile == 1 ? 128 : (tile == 2 || tile == 5) ? 64 : tile == 3 ? 64 : 32;
+    const int bm = tile == 1 ? 128 : tile == 2 ? 64 : tile == 3 ? 128 : 256;
+    const int bn = tile == 1 ? 128 : tile == 2 ? 64 : tile == 3 ? 64 : 32;
     const long tiles = ((M + bm - 1) / bm) * ((K + bn - 1) / bn);
     if (det.plan != nullptr) {
         det_plan(det, tile, tiles, splits, (long)bm * bn);
@@ -1488,11 +1345,10 @@ static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, fl
 #define OMNI_FWD(BM_, BN_, WM_, WN_, BK_, PF_)                                                                           \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_fwd_kernel<BM_, BN_, WM_, WN_, BK_, PF_>),                                     \
                        dim3((unsigned)(((M + BM_ - 1) / BM_) * ((K + BN_ - 1) / BN_)), (unsigned)splits), dim3(256), 0, st, p)
-    // (round 5: the 64 x 64 launches of the direct convolutions gain nothing from a deeper ring -- PF 2 / 3 on every one of them:
-    // 10.97 / 10.99 ms per step against 10.97, profiles/r05_ab_conv64_pf.log; tile 5 stays an explicit choice)
+    // (round 5: the 64 x 64 launches of the direct convolutions gained nothing from a deeper ring -- PF 2 / 3 on every one of them:
+    // 10.97 / 10.99 ms per step against 10.97, profiles/r05_ab_conv64_pf.log)
     if (tile == 1) OMNI_FWD(128, 128, 2, 2, 32, 1);
     else if (tile == 2) OMNI_FWD(64, 64, 2, 2, 32, 1);
-    else if (tile == 5) OMNI_FWD(64, 64, 2, 2, 32, 3);
     else if (tile == 3) OMNI_FWD(128, 64, 2, 2, 32, 1);
     else OMNI_FWD(256, 32, 4, 1, 16, 1);   // tiny channel counts (stem, level0/1, RPN 16-wide heads): slab depth 16 measured faster
 #undef OMNI_FWD
@@ -1608,9 +1464,8 @@ static int conv2d_dgrad_impl(const float* dy, const float* w, float* dx, int N, 
         p.ctr = det.ctr;
     }
     if (splits > 1 && !accumulate && !ordered) omni_memset_async(dx, 0, sizeof(float) * (size_t)N * H * W * C, st);
-    // deep-prefetch form (PF = 2) when a 32-bit byte offset reaches both operands; OMNI_DGRAD_PF=0: the classic body (A/B knob)
-    static const int dgrad_pf = [] { const char* e = getenv("OMNI_DGRAD_PF"); return e ? atoi(e) : 2; }();
-    const bool dpf_ok = dgrad_pf >= 2 && (long)N * p.OH * p.OW * lddy * 4 < (1L << 31) - (1L << 24) && (long)K * R * S * C * 4 < (1L << 31) - (1L << 24);
+    // deep-prefetch form (PF = 2) when a 32-bit byte offset reaches both operands, else the classic body
+    const bool dpf_ok = (long)N * p.OH * p.OW * lddy * 4 < (1L << 31) - (1L << 24) && (long)K * R * S * C * 4 < (1L << 31) - (1L << 24);
 #define OMNI_DGRAD_PF(BM_, BN_, WM_, WN_, BK_)                                                                           \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_dgrad_kernel<BM_, BN_, WM_, WN_, BK_, 2>),                                     \
                        dim3((unsigned)(((M + BM_ - 1) / BM_) * ((C + BN_ - 1) / BN_)), (unsigned)splits, ncls), dim3(256), 0, st, p)
@@ -1666,11 +1521,7 @@ struct WgradGeom {
 // fc1-class weight gradients ([1024 x 2048]^T [2048 x 12544]: few "pixels", a very wide (tap, c) extent): 8 x 196 = 1568 tiles of
 // 128 x 64 are 2.04 rounds of the 768 resident workgroups -- a third round of 32 workgroups costs ~100 us; 3136 tiles of 64 x 64 at four
 // per CU end together: 589 -> 534 us (0.57 -> 0.63 of peak), the cube head's 512-ROI launch 157 -> 142 us (tools/probes/fc_wgrad_tiles.py,
-// profiles/r06_fc_wgrad_tiles.log).  Same slab order per output element.  OMNI_WGRAD_FC_TILE64=0: the 128 x 64 tile.
-static inline bool wgrad_fc_tile64() {
-    static const bool on = [] { const char* e = getenv("OMNI_WGRAD_FC_TILE64"); return e == nullptr || atoi(e) != 0; }();
-    return on;
-}
+// profiles/r06_fc_wgrad_tiles.log).  Same slab order per output element.
 static inline WgradGeom wgrad_geom(int K, int Nn, long P, int tile) {
     constexpr int WBK = 32;
     // tile: 128x128 for wide layers, 128x64 when the (tap, c) extent is only 64 wide, 64x64 for K <= 64,
@@ -1680,7 +1531,7 @@ static inline WgradGeom wgrad_geom(int K, int Nn, long P, int tile) {
     else if (tile == 2) { g.bm = 64; g.bn = 64; }
     else if (tile == 3) { g.bm = 128; g.bn = 64; }
     else if (tile == 4) { g.bm = 32; g.bn = 128; }
-    else if (K > 64 && Nn >= 4096 && P <= 4096 && wgrad_fc_tile64()) { g.bm = 64; g.bn = 64; }      // fc1-class: see wgrad_fc_tile64()
+    else if (K > 64 && Nn >= 4096 && P <= 4096) { g.bm = 64; g.bn = 64; }      // fc1-class: see above
     else if (K > 64) { g.bm = 128; g.bn = (Nn > 64 && P >= 32768) ? 128 : 64; }
     else if (K > 32) { g.bm = 64; g.bn = 64; }
     else { g.bm = 32; g.bn = 128; }
@@ -1747,25 +1598,20 @@ static int conv2d_wgrad_impl(const float* x, const float* dy, float* dw, int N, 
         p.ctr = det.ctr;
     }
     if (splits > 1 && !accumulate && !ordered) omni_memset_async(dw, 0, sizeof(float) * (size_t)K * Nn, (hipStream_t)stream);
-    if (xcd_order < 0) xcd_order = (WGRAD_XCD_ORDER_FC && R == 1 && S == 1 && H == 1 && W == 1 && splits == 1) ? 1 : 0;
+    // fc-class weight gradients (one split): XCD-contiguous tile order (fc1: 615 -> 562 us, profiles/r03_fc_wgrad_xcd_order.log)
+    if (xcd_order < 0) xcd_order = (R == 1 && S == 1 && H == 1 && W == 1 && splits == 1) ? 1 : 0;
     p.relu = xcd_order;
     // deep-prefetch form (conv_wgrad_pf_kernel): single-source problems whose operands a 32-bit buffer offset reaches
-    static const int wgrad_pf = [] { const char* e = getenv("OMNI_WGRAD_PF"); return e ? atoi(e) : 2; }();      // A/B knob: 0 = the classic body
     // (16 MiB of head-room: the byte cursors run up to PF slabs past the last pixel before their loads are masked)
-    const bool pf_ok = wgrad_pf >= 2 && ms == nullptr && (long)P * lddy * 4 < (1L << 31) - (1L << 24) && (long)N * H * W * ldx * 4 < (1L << 31) - (1L << 24);
-    // MEASURED and left OFF (profiles/r06_ab_wgrad_xcd_splits.log): 10.66-10.68 ms with, 10.66-10.68 without; the 3x3/s2 64->128 launch
-    // 52 us either way -- the re-fetched ranges come out of the memory-side cache, not HBM
-    static const int wgrad_xcd_splits = [] { const char* e = getenv("OMNI_WGRAD_XCD_SPLITS"); return e ? atoi(e) : 0; }();      // A/B knob
-    const int xcd_splits = (wgrad_xcd_splits && splits >= 8 && tiles > 1) ? 1 : 0;
+    const bool pf_ok = ms == nullptr && (long)P * lddy * 4 < (1L << 31) - (1L << 24) && (long)N * H * W * ldx * 4 < (1L << 31) - (1L << 24);
 #define OMNI_WGRAD_PF(BM_, BN_, WM_, WN_, PF_)                                                                          \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_pf_kernel<BM_, BN_, WM_, WN_, WBK, PF_>), dim3(tiles, (unsigned)splits), dim3(256), 0, \
-                       (hipStream_t)stream, p, pps, xcd_splits)
+                       (hipStream_t)stream, p, pps)
     if (pf_ok) {
-        // (wgrad_pf == 3, A/B: three slabs in flight on the tiles whose registers allow it without losing a wave per SIMD)
         if (bm == 128 && bn == 128) OMNI_WGRAD_PF(128, 128, 2, 2, 2);
         else if (bm == 128) OMNI_WGRAD_PF(128, 64, 2, 2, 2);
-        else if (bm == 64) { if (wgrad_pf >= 3) OMNI_WGRAD_PF(64, 64, 2, 2, 3); else OMNI_WGRAD_PF(64, 64, 2, 2, 2); }
-        else { if (wgrad_pf >= 3) OMNI_WGRAD_PF(32, 128, 1, 4, 3); else OMNI_WGRAD_PF(32, 128, 1, 4, 2); }
+        else if (bm == 64) OMNI_WGRAD_PF(64, 64, 2, 2, 2);
+        else OMNI_WGRAD_PF(32, 128, 1, 4, 2);
         return omni_launch_status();
     }
 #undef OMNI_WGRAD_PF
@@ -1808,57 +1654,29 @@ int omni_conv2d_wgrad_multi_det(const void* const* xs, const int* cs, int nsrc, 
                              DetArgs{ws, ws_floats, (unsigned*)ctr, n_ctr, plan}, &ms);
 }
 
-int omni_conv2d_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
-                      int stride, int pad, int ldx, int lddy, int accumulate, void* stream) {
-    return omni_conv2d_wgrad_algo(x, dy, dw, N, H, W, C, K, R, S, stride, pad, ldx, lddy, accumulate, 0, stream);
-}
-
 // ---- batched GEMMs of the Winograd path (csrc/winograd.hip): `batch` independent dense problems in one launch ----
 // out[b] (M x K) = x[b] (M x C) * w[b] (K x C)^T
 // algo: 0 auto | 1 = persistent 128x128 workgroups walking the (problem, tile) list (`workgroups` of them, 0 = 512; needs
 // C % 32 == 0) | 2 = one 128x128 tile per workgroup | 3 = one 64x64 tile per workgroup | 4 = 64x64 tiles with 2-4 slabs of
-// buffer-load prefetch in flight (gemm_nt_pf_kernel; needs C % 64 == 0) | 5 = algo 4's tiles walked by `workgroups` persistent
-// workgroups (0 = 1024, a multiple of 8) with the slab stream running through the tile boundaries (gemm_nt_pfp_kernel)
+// buffer-load prefetch in flight (gemm_nt_pf_kernel; needs C % 64 == 0)
 int omni_gemm_batched_fwd_algo(const float* x, const float* w, float* out, int batch, int M, int C, int K, int algo, int workgroups,
                                void* stream) {
-    if (batch <= 0 || M < 0 || C <= 0 || K <= 0 || (C & 3) || algo < 0 || algo > 5 || workgroups < 0) return OMNI_ERR_ARG;
-    if ((algo == 1 || algo == 5) && ((C % 32) != 0 || (workgroups & 7))) return OMNI_ERR_ARG;
+    if (batch <= 0 || M < 0 || C <= 0 || K <= 0 || (C & 3) || algo < 0 || algo > 4 || workgroups < 0) return OMNI_ERR_ARG;
+    if (algo == 1 && ((C % 32) != 0 || (workgroups & 7))) return OMNI_ERR_ARG;
     if (M == 0) return OMNI_OK;
     ConvP p{x, w, nullptr, out, M, 1, 1, C, 1, 1, K, 1, 1, 1, 0, C, K, 0, 0, 0, 1, (long)M * C, (long)K * C, (long)M * K};
     const long t128 = (((long)M + 127) / 128) * ((K + 127) / 128);
     // measured per shape (tools/sweep_batched_gemm.py, hipGraph replay): the persistent kernel from 1024 128x128 tiles up, 64x64 tiles
-    // below (36x[1024x256]x[256x256]^T: 60 us against 76 us with one 128x128 tile per workgroup)
-    const bool auto_choice = algo == 0;
-    if (algo == 0) algo = (K > 64 && (C % 32) == 0 && t128 * batch >= 1024 && !(FWD64_DEEP_PREFETCH && (C % 64) == 0)) ? 1 : 3;
+    // below (36x[1024x256]x[256x256]^T: 60 us against 76 us with one 128x128 tile per workgroup); C % 64 == 0: the deep-prefetch
+    // 64x64 kernel instead (profiles/r03_sweep_batched_gemm.log: 17-27 % faster on every small-map shape)
+    if (algo == 0) algo = (K > 64 && (C % 32) == 0 && t128 * batch >= 1024 && (C % 64) != 0) ? 1 : 3;
     if (algo == 1) {
         // >= 2 items per resident workgroup: persistent kernel with the prefetch carried across items
         GemmP g{x, w, out, batch, M, K, C, (M + 127) / 128, (K + 127) / 128};
         hipLaunchKernelGGL(gemm_nt_persistent_kernel, dim3(workgroups ? workgroups : 512), dim3(256), 0, (hipStream_t)stream, g);
         return omni_launch_status();
     }
-    if (algo == 3 && FWD64_DEEP_PREFETCH && (C % 64) == 0 && (long)M * C * 4 < (1L << 31) && (long)K * C * 4 < (1L << 31)) algo = 4;
-    // many-tile launches: the persistent form from OMNI_GEMM_PERSIST_MIN_ITEMS 64x64 tiles up (A/B knob; 0 = never)
-    static const long persist_min = [] { const char* e = getenv("OMNI_GEMM_PERSIST_MIN_ITEMS"); return e ? atol(e) : 0L; }();
-    static const int persist_wgs = [] { const char* e = getenv("OMNI_GEMM_PERSIST_WGS"); return e ? atoi(e) : 0; }();
-    // outputs of at least this many MB leave through `nt` stores (A/B knob; 0 = never)
-    static const long nt_min_mb = [] { const char* e = getenv("OMNI_GEMM_NT_OUT_MIN_MB"); return e ? atol(e) : 0L; }();
-    const int nt_out = (nt_min_mb > 0 && (long)batch * M * K * 4 >= nt_min_mb * (1L << 20)) ? 1 : 0;
-    if (algo == 4 && auto_choice && persist_min > 0 && (((long)M + 63) / 64) * ((K + 63) / 64) * batch >= persist_min &&
-        (long)batch * M * C * 4 < (1L << 31) && (long)batch * K * C * 4 < (1L << 31) && (persist_wgs & 7) == 0) {
-        algo = 5;
-        workgroups = persist_wgs;
-    }
-    if (algo == 5) {
-        const long items = (((long)M + 63) / 64) * ((K + 63) / 64) * batch;
-        if ((C % 64) != 0 || (long)batch * M * C * 4 >= (1L << 31) || (long)batch * K * C * 4 >= (1L << 31) || items > 0x7fffffff)
-            return OMNI_ERR_ARG;
-        GemmTP g{x, w, out, M, K, C, (long)M * C, (long)K * C, (long)M * K, nullptr, nullptr, batch, nt_out};
-        long wgs = workgroups ? workgroups : 1024;
-        if (wgs > items) wgs = (items + 7) / 8 * 8;
-        if ((C % 128) == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_nt_pfp_kernel<4>), dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, g);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_nt_pfp_kernel<2>), dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, g);
-        return omni_launch_status();
-    }
+    if (algo == 3 && (C % 64) == 0 && (long)M * C * 4 < (1L << 31) && (long)K * C * 4 < (1L << 31)) algo = 4;
     if (algo == 2)   // else 64x64 tiles: 4x the workgroups (measured on the 256ch @32x32 layers)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_fwd_kernel<128, 128, 2, 2, 32>), dim3((unsigned)t128, 1, (unsigned)batch), dim3(256), 0,
                            (hipStream_t)stream, p);
@@ -1868,7 +1686,7 @@ int omni_gemm_batched_fwd_algo(const float* x, const float* w, float* out, int b
                            (hipStream_t)stream, p);
     else {           // 64x64 tiles, PF slabs of buffer-load prefetch in flight (gemm_nt_pf_kernel)
         if ((C % 64) != 0 || (long)M * C * 4 >= (1L << 31) || (long)K * C * 4 >= (1L << 31)) return OMNI_ERR_ARG;
-        GemmTP g{x, w, out, M, K, C, (long)M * C, (long)K * C, (long)M * K, nullptr, nullptr, batch, nt_out};
+        GemmTP g{x, w, out, M, K, C, (long)M * C, (long)K * C, (long)M * K, nullptr, nullptr};
         const long wgs = (((long)M + 63) / 64) * ((K + 63) / 64) * batch;
         if (wgs > 0x7fffffff) return OMNI_ERR_ARG;
         const dim3 grid((unsigned)wgs);
@@ -1878,26 +1696,10 @@ int omni_gemm_batched_fwd_algo(const float* x, const float* w, float* out, int b
     return omni_launch_status();
 }
 
-int omni_gemm_batched_fwd(const float* x, const float* w, float* out, int batch, int M, int C, int K, void* stream) {
-    return omni_gemm_batched_fwd_algo(x, w, out, batch, M, C, K, 0, 0, stream);
-}
-
 // dw[b] (K x C) = dy[b] (M x K)^T * x[b] (M x C)      (overwrites dw)
 // algo: 0 auto | 1 = the tile kernels of the implicit-GEMM weight gradient (128x128 / 64x64, one slab of prefetch) | 2 = 64x64 tiles
-// with 2-4 slabs of buffer-load prefetch in flight (gemm_tn_pf_kernel)
-constexpr bool WGRAD64_DEEP_PREFETCH = true;    // gemm_tn_pf_kernel (profiles/r03_sweep_batched_gemm.log: 3-66 % faster on every Winograd weight-gradient shape)
-
-// A/B knob (OMNI_WGRAD_LDS_PAD, bytes of unused dynamic LDS per workgroup): bounds how many weight-gradient workgroups a CU hosts, so
-// that workgroups of the critical-path stream always find registers / LDS free beside them
-static inline unsigned tn_lds_pad() {
-    static const unsigned pad = [] {
-        const char* e = getenv("OMNI_WGRAD_LDS_PAD");
-        const long v = e != nullptr ? atol(e) : 0;
-        return (unsigned)(v < 0 ? 0 : v > 32768 ? 32768 : v);
-    }();
-    return pad;
-}
-
+// with 2-4 slabs of buffer-load prefetch in flight (gemm_tn_pf_kernel; profiles/r03_sweep_batched_gemm.log: 3-66 % faster on every
+// Winograd weight-gradient shape)
 // 64x64 tiles of gemm_tn_pf_kernel: row splits of >= 8 slabs, aiming at >= 512 workgroups
 static inline void tn_pf_plan(int batch, int M, int C, int K, int& tiles, long& splits, int& rps) {
     tiles = ((K + 63) / 64) * ((C + 63) / 64);
@@ -1921,7 +1723,7 @@ static int gemm_batched_wgrad_impl(const float* x, const float* dy, float* dw, i
     }
     const bool fits = (long)M * C * 4 < (1L << 31) && (long)M * K * 4 < (1L << 31);
     if (algo == 2 && !fits) return OMNI_ERR_ARG;
-    if (algo == 0) algo = (WGRAD64_DEEP_PREFETCH && fits) ? 2 : 1;
+    if (algo == 0) algo = fits ? 2 : 1;
     if (algo == 2) {
         int tiles, rps;
         long splits;
@@ -2050,12 +1852,8 @@ int omni_gemm_batched_wgrad_multi(const void* const* x, const void* const* dy, c
         if (first > 0x7fffffff) return OMNI_ERR_ARG;
     }
     t.first[live] = (int)first;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_tn_multi_kernel<4>), dim3((unsigned)first), dim3(256), tn_lds_pad(), st, t);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_tn_multi_kernel<4>), dim3((unsigned)first), dim3(256), 0, st, t);
     return omni_launch_status();
-}
-
-int omni_gemm_batched_wgrad(const float* x, const float* dy, float* dw, int batch, int M, int C, int K, void* stream) {
-    return omni_gemm_batched_wgrad_algo(x, dy, dw, batch, M, C, K, 0, stream);
 }
 
 // ---- grouped convolution: nn.Conv2d(C, K, R, stride, pad, groups=G, bias=False), the 3x3 of DLA's BottleneckX

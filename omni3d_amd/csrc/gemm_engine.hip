@@ -441,13 +441,10 @@ struct EngineDet {
     long long* plan;        // != nullptr: report {0, parts of a cut tile, counters, workspace floats} and do not launch
 };
 
-// tile rows per band (see engine_tile); OMNI_ENGINE_BAND overrides (1 = row-major, the order of rounds 2-3)
+// tile rows per band (see engine_tile; 1 would be row-major, the order of rounds 2-3)
+constexpr int ENGINE_BAND = 8;
 static inline int engine_band(int tiles_m) {
-    static const int forced = [] {
-        const char* e = getenv("OMNI_ENGINE_BAND");
-        return e != nullptr ? atoi(e) : 0;
-    }();
-    int band = forced > 0 ? forced : 8;
+    int band = ENGINE_BAND;
     if (band > tiles_m) band = tiles_m;
     return band < 1 ? 1 : band;
 }

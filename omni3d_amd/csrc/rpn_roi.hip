@@ -610,15 +610,6 @@ int omni_rpn_match_draw(const float* anchors, int A, const float* gt, const int*
     return omni_launch_status();
 }
 
-int omni_rpn_match(const float* anchors, int A, const float* gt, const int* gt_off, int B, int G, float thr_lo,
-                   float thr_hi, int l0, int l1, int l2, int allow_low_quality, const float* expo, float eps,
-                   float* matched_val, int* matched_idx, signed char* match_label, int* gt_best_bits, int* gt_best_idx,
-                   float* key_pos, float* key_neg, void* stream) {
-    if (expo == nullptr) return OMNI_ERR_ARG;
-    return omni_rpn_match_draw(anchors, A, gt, gt_off, B, G, thr_lo, thr_hi, l0, l1, l2, allow_low_quality, expo, nullptr, nullptr, eps,
-                               matched_val, matched_idx, match_label, gt_best_bits, gt_best_idx, key_pos, key_neg, stream);
-}
-
 // Final anchor labels {-1,0,1} (B, A) from the sampled candidates (sorted top-k lists of the keys).
 int omni_rpn_finalize_labels(const float* anchors, int A, int B, const int* gt_off, const float* ign, const int* ign_off,
                              const signed char* match_label, const int* gt_best_idx, const float* pos_val,
@@ -762,16 +753,6 @@ int omni_roi_sample_draw(const float* prop_boxes, const int* prop_count, int B, 
                        nfg_max, append_gt, out_boxes, out_cls, out_gt, out_iou, out_counts, draw_state, ticket, out_row, first,
                        first_boxes, first_cls, first_row);
     return omni_launch_status();
-}
-
-int omni_roi_sample(const float* prop_boxes, const int* prop_count, int B, int pmax, const float* gt, const int* gt_cls,
-                    const int* gt_off, const float* ign, const int* ign_off, const float* expo, float iou_thr,
-                    float ignore_thresh, float eps, int num_classes, int batch_per_image, int nfg_max, int append_gt,
-                    float* out_boxes, int* out_cls, int* out_gt, float* out_iou, int* out_counts, void* stream) {
-    if (expo == nullptr) return OMNI_ERR_ARG;
-    return omni_roi_sample_draw(prop_boxes, prop_count, B, pmax, gt, gt_cls, gt_off, ign, ign_off, expo, nullptr, nullptr, iou_thr,
-                                ignore_thresh, eps, num_classes, batch_per_image, nfg_max, append_gt, out_boxes, out_cls, out_gt, out_iou,
-                                out_counts, nullptr, 0, nullptr, nullptr, nullptr, stream);
 }
 
 

@@ -19,7 +19,6 @@
 // rows in 64-box chunks: intra-chunk resolution from the diagonal word, then the kept rows OR their
 // mask rows into the running `removed` words (one 64-bit word per lane).
 #include <device_rt.h>
-#include <cstdlib>
 
 namespace {
 
@@ -420,6 +419,7 @@ __global__ void __launch_bounds__(256) nms_mask_kernel(const float* __restrict__
     mask[((long)q * nmax + i) * words + cb] = bits;
 }
 
+constexpr int SCAN_WAVES = 16;      // waves per problem of the scan (4 / 8 measured slower: 250 / 230 against 189 us for mask + scan, profiles/HISTORY.md)
 template <int NMS_SCAN_WAVES>
 __global__ void __launch_bounds__(64 * NMS_SCAN_WAVES) nms_scan_kernel(const unsigned long long* __restrict__ mask,
                                                                        const int* __restrict__ counts, const int* __restrict__ valid,
@@ -553,16 +553,8 @@ int omni_nms_sorted(const float* boxes, const int* counts, const int* valid, int
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(nms_mask_kernel, dim3(words, (words + 3) / 4, Q), dim3(256), 0, st, boxes, counts, nmax, words, iou_thr,
                        mask_ws);
-    static const int scan_waves = [] { const char* e = getenv("OMNI_NMS_SCAN_WAVES"); return e ? atoi(e) : 16; }();   // A/B knob
-    if (scan_waves == 4)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(nms_scan_kernel<4>), dim3(Q), dim3(256), 0, st, (const unsigned long long*)mask_ws, counts, valid,
-                           nmax, words, keep);
-    else if (scan_waves == 8)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(nms_scan_kernel<8>), dim3(Q), dim3(512), 0, st, (const unsigned long long*)mask_ws, counts, valid,
-                           nmax, words, keep);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(nms_scan_kernel<16>), dim3(Q), dim3(1024), 0, st, (const unsigned long long*)mask_ws, counts, valid,
-                           nmax, words, keep);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(nms_scan_kernel<SCAN_WAVES>), dim3(Q), dim3(64 * SCAN_WAVES), 0, st, (const unsigned long long*)mask_ws,
+                       counts, valid, nmax, words, keep);
     return omni_launch_status();
 }
 

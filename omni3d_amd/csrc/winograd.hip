@@ -254,64 +254,10 @@ __device__ __forceinline__ void wino_w_body32(const float* __restrict__ g, float
     }
 }
 
-__device__ __forceinline__ void wino_w_body(const float* __restrict__ g, float* __restrict__ U, float* __restrict__ Uf, int K, int C,
-                                            int bid, float (*s_t)[16][17]) {
-    // one 16 (k) x 16 (c) tile per block (bid); U' goes through an LDS transpose (s_t: [16][16][17]) so that its rows (k contiguous)
-    // are written in 64-byte runs instead of 4-byte scatters
-    const long total = (long)K * C;
-    const int tiles_c = (C + 15) / 16;
-    const int k0 = (bid / tiles_c) * 16, c0 = (bid % tiles_c) * 16;
-    const int kk = threadIdx.x >> 4, cc = threadIdx.x & 15;
-    const int k = k0 + kk, c = c0 + cc;
-    const bool ok = k < K && c < C;
-    float w[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int s = 0; s < 3; ++s) w[r][s] = ok ? g[((long)k * 9 + r * 3 + s) * C + c] : 0.f;
-    float a[4][3];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {       // G g
-        a[0][s] = w[0][s];
-        a[1][s] = 0.5f * (w[0][s] + w[1][s] + w[2][s]);
-        a[2][s] = 0.5f * (w[0][s] - w[1][s] + w[2][s]);
-        a[3][s] = w[2][s];
-    }
-    float u[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {       // (.) G^T
-        u[r][0] = a[r][0];
-        u[r][1] = 0.5f * (a[r][0] + a[r][1] + a[r][2]);
-        u[r][2] = 0.5f * (a[r][0] - a[r][1] + a[r][2]);
-        u[r][3] = a[r][2];
-    }
-    if (U != nullptr && ok) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) U[(long)(4 * r + t) * total + (long)k * C + c] = u[r][t];
-    }
-    if (Uf != nullptr) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int pr = (r == 0) ? 3 : (r == 3) ? 0 : r, pt = (t == 0) ? 3 : (t == 3) ? 0 : t;
-                s_t[4 * r + t][cc][kk] = u[pr][pt];
-            }
-        __syncthreads();
-        const int oc = c0 + kk, okk = k0 + cc;       // this thread now writes (c = c0 + kk, k = k0 + cc)
-        if (oc < C && okk < K) {
-#pragma unroll
-            for (int xi = 0; xi < 16; ++xi) Uf[(long)xi * total + (long)oc * K + okk] = s_t[xi][kk][cc];
-        }
-    }
-}
 __global__ void __launch_bounds__(256) wino_w_kernel(const float* __restrict__ g, float* __restrict__ U, float* __restrict__ Uf,
-                                                     int K, int C, int tile32) {
-    __shared__ float s_t[16][16][17];           // 17.4 KB >= the 32-tile form's [4][32][33]
-    if (tile32) wino_w_body32(g, U, Uf, K, C, (int)blockIdx.x, &s_t[0][0][0]);
-    else wino_w_body(g, U, Uf, K, C, (int)blockIdx.x, s_t);
+                                                     int K, int C) {
+    __shared__ float s_t[16 * 16 * 17];         // 17.4 KB (the footprint the launch was measured with) >= the body's [4][32][33]
+    wino_w_body32(g, U, Uf, K, C, (int)blockIdx.x, s_t);
 }
 
 // v[r][s] = (G^T dU G)[r][s] of filter element i = k * C + c
@@ -565,56 +511,8 @@ __device__ __forceinline__ void gt6(const float (&u)[6], float (&e)[3]) {      /
     e[2] = (u[1] - u[2]) * (1.f / 3.f) + (u[4] - u[3]) * (4.f / 15.f) + u[5];
 }
 
-// U[36][K][C] and / or U'[36][C][K] (rotated, channel-transposed filter); 16 x 16 (k, c) tile per block, U' through an LDS
-// transpose (as wino_w_kernel)
-__device__ __forceinline__ void wino4_w_body(const float* __restrict__ g, float* __restrict__ U, float* __restrict__ Uf, int K, int C,
-                                             int bid, float (*s_t)[16][17]) {
-    const long total = (long)K * C;
-    const int tiles_c = (C + 15) / 16;
-    const int k0 = (bid / tiles_c) * 16, c0 = (bid % tiles_c) * 16;
-    const int kk = threadIdx.x >> 4, cc = threadIdx.x & 15;
-    const int k = k0 + kk, c = c0 + cc;
-    const bool ok = k < K && c < C;
-    float w[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int s = 0; s < 3; ++s) w[r][s] = ok ? g[((long)k * 9 + r * 3 + s) * C + c] : 0.f;
-#pragma unroll
-    for (int flip = 0; flip < 2; ++flip) {
-        float* dst = flip ? Uf : U;
-        if (dst == nullptr) continue;            // uniform
-        float a[6][3];
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            float col[3], o6[6];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) col[r] = flip ? w[2 - r][2 - s] : w[r][s];
-            g6(col, o6);
-#pragma unroll
-            for (int r = 0; r < 6; ++r) a[r][s] = o6[r];
-        }
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            float row[6];
-            g6(a[r], row);
-#pragma unroll
-            for (int s = 0; s < 6; ++s) {
-                if (!flip) { if (ok) dst[(long)(6 * r + s) * total + (long)k * C + c] = row[s]; }
-                else s_t[6 * r + s][cc][kk] = row[s];
-            }
-        }
-        if (flip) {
-            __syncthreads();
-            const int oc = c0 + kk, okk = k0 + cc;
-            if (oc < C && okk < K) {
-#pragma unroll
-                for (int xi = 0; xi < 36; ++xi) dst[(long)xi * total + (long)oc * K + okk] = s_t[xi][kk][cc];
-            }
-        }
-    }
-}
-// The same transform on 32 x 32 (k, c) tiles (round 4): every store instruction of a wave covers two 128-byte runs instead of four
+// U[36][K][C] and / or U'[36][C][K] (rotated, channel-transposed filter), U' through an LDS transpose (as wino_w_kernel).
+// 32 x 32 (k, c) tiles (round 4; 16 x 16 in rounds 1-3): every store instruction of a wave covers two 128-byte runs instead of four
 // 64-byte ones -- this launch writes 260 MB per training step (36 planes of U and of U' for every 3x3 filter) and ran at 2.3 TB/s.
 // A thread owns four (k, c) pairs, k = k0 + tid / 32 + 8 j; U' goes through LDS one row of six points at a time ([6][32][33] floats).
 __device__ __forceinline__ void wino4_w_body32(const float* __restrict__ g, float* __restrict__ U, float* __restrict__ Uf, int K, int C,
@@ -697,24 +595,16 @@ __device__ __forceinline__ void wino4_w_body32(const float* __restrict__ g, floa
         }
     }
 }
-// OMNI_WINO_W_TILE32=0: the 16 x 16 tiles of rounds 1-3 (A/B knob)
-static inline int wino4_w_tile32() {
-    static const int on = [] { const char* e = getenv("OMNI_WINO_W_TILE32"); return (e == nullptr || atoi(e) != 0) ? 1 : 0; }();
-    return on;
-}
-static inline int wino4_w_tiles(int K, int C) {
-    return wino4_w_tile32() ? ((K + 31) / 32) * ((C + 31) / 32) : ((K + 15) / 16) * ((C + 15) / 16);
-}
+static inline int wino4_w_tiles(int K, int C) { return ((K + 31) / 32) * ((C + 31) / 32); }
 __global__ void __launch_bounds__(256) wino4_w_kernel(const float* __restrict__ g, float* __restrict__ U, float* __restrict__ Uf,
-                                                      int K, int C, int tile32) {
-    __shared__ float s_t[36][16][17];
-    if (tile32) wino4_w_body32(g, U, Uf, K, C, (int)blockIdx.x, &s_t[0][0][0]);
-    else wino4_w_body(g, U, Uf, K, C, (int)blockIdx.x, s_t);
+                                                      int K, int C) {
+    __shared__ float s_t[36 * 16 * 17];         // 38.3 KB (the footprint the launch was measured with) >= the body's [6][32][33]
+    wino4_w_body32(g, U, Uf, K, C, (int)blockIdx.x, s_t);
 }
 
 // Every filter of a forward pass in ONE launch: the weights are fixed for the duration of a step, so the ~20 transform launches of
 // the DLA-34 + FPN + RPN forward (6 us each, latency-bound, on the un-overlapped forward path) collapse into one.  A workgroup finds
-// its (filter, 16 x 16 tile) by scanning the table's workgroup prefix.
+// its (filter, 32 x 32 tile) by scanning the table's workgroup prefix.
 constexpr int WINO_MULTI_MAX = 48;
 struct WinoWTable {
     const float* g[WINO_MULTI_MAX];
@@ -722,17 +612,15 @@ struct WinoWTable {
     float* Uf[WINO_MULTI_MAX];
     int K[WINO_MULTI_MAX], C[WINO_MULTI_MAX], tile[WINO_MULTI_MAX];
     int wg0[WINO_MULTI_MAX + 1];
-    int n, tile32;
+    int n;
 };
 __global__ void __launch_bounds__(256) wino_w_multi_kernel(WinoWTable t) {
-    __shared__ float s_t[36][16][17];
+    __shared__ float s_t[36 * 16 * 17];         // (as wino4_w_kernel)
     int e = 0;
     while (e + 1 < t.n && (int)blockIdx.x >= t.wg0[e + 1]) ++e;
     const int bid = (int)blockIdx.x - t.wg0[e];
-    if (t.tile[e] == 2 && t.tile32) wino_w_body32(t.g[e], t.U[e], t.Uf[e], t.K[e], t.C[e], bid, &s_t[0][0][0]);
-    else if (t.tile[e] == 2) wino_w_body(t.g[e], t.U[e], t.Uf[e], t.K[e], t.C[e], bid, s_t);
-    else if (t.tile32) wino4_w_body32(t.g[e], t.U[e], t.Uf[e], t.K[e], t.C[e], bid, &s_t[0][0][0]);
-    else wino4_w_body(t.g[e], t.U[e], t.Uf[e], t.K[e], t.C[e], bid, s_t);
+    if (t.tile[e] == 2) wino_w_body32(t.g[e], t.U[e], t.Uf[e], t.K[e], t.C[e], bid, s_t);
+    else wino4_w_body32(t.g[e], t.U[e], t.Uf[e], t.K[e], t.C[e], bid, s_t);
 }
 
 __device__ __forceinline__ void wino4_dw_elem(const float* __restrict__ dU, long total, long i, float (&v)[3][3]) {
@@ -991,7 +879,7 @@ int omni_wino_out_carry(const float* M, const float* carry, long long ldc, float
 
 // Data-gradient output transform that also emits the BACKWARD partial statistics of the BatchNorm whose output gradient it writes
 // (see BnBwdStats): stats [rows][2][K] = per-workgroup (sum dz, sum dz * xhat); *nblk_out = rows written, 0 = not produced (F(2x2)
-// tiles, channel count without a fixed group per thread) and the caller runs omni_bn_bwd.  scale_shift nullable (no ReLU).
+// tiles, channel count without a fixed group per thread) and the caller's omni_bn_bwd_algo runs its own reduction pass.  scale_shift nullable (no ReLU).
 int omni_wino_out_bn_bwd_stats(const float* M, float* y, int N, int H, int W, int K, int tile, const float* bn_x, const float* mean_rstd,
                                const float* scale_shift, float* stats, int stats_rows, int* nblk_out, void* stream) {
     if (bn_x == nullptr || mean_rstd == nullptr) return OMNI_ERR_ARG;
@@ -1024,9 +912,9 @@ int omni_wino_dy_in(const float* dy, float* dM, float* Vd, int N, int H, int W, 
 
 int omni_wino_weights(const float* g, float* U, float* U_flip, int K, int C, int tile, void* stream) {
     if (K <= 0 || C <= 0 || (U == nullptr && U_flip == nullptr) || (tile != 2 && tile != 4)) return OMNI_ERR_ARG;
-    const unsigned wt = (unsigned)wino4_w_tiles(K, C);       // one 32 x 32 (or, OMNI_WINO_W_TILE32=0, 16 x 16) (k, c) tile per workgroup
-    if (tile == 2) hipLaunchKernelGGL(wino_w_kernel, dim3(wt), dim3(256), 0, (hipStream_t)stream, g, U, U_flip, K, C, wino4_w_tile32());
-    else hipLaunchKernelGGL(wino4_w_kernel, dim3(wt), dim3(256), 0, (hipStream_t)stream, g, U, U_flip, K, C, wino4_w_tile32());
+    const unsigned wt = (unsigned)wino4_w_tiles(K, C);       // one 32 x 32 (k, c) tile per workgroup
+    if (tile == 2) hipLaunchKernelGGL(wino_w_kernel, dim3(wt), dim3(256), 0, (hipStream_t)stream, g, U, U_flip, K, C);
+    else hipLaunchKernelGGL(wino4_w_kernel, dim3(wt), dim3(256), 0, (hipStream_t)stream, g, U, U_flip, K, C);
     return omni_launch_status();
 }
 
@@ -1037,7 +925,6 @@ int omni_wino_weights_multi(const void* const* g, const void* const* U, const vo
     if (n <= 0 || n > WINO_MULTI_MAX || g == nullptr || U == nullptr || U_flip == nullptr) return OMNI_ERR_ARG;
     WinoWTable t;
     t.n = n;
-    t.tile32 = wino4_w_tile32();
     t.wg0[0] = 0;
     for (int i = 0; i < n; ++i) {
         if (K[i] <= 0 || C[i] <= 0 || (U[i] == nullptr && U_flip[i] == nullptr) || (tile[i] != 2 && tile[i] != 4) || g[i] == nullptr)

@@ -8,7 +8,6 @@ dla102x2 of MODEL.DLA.TYPE (the 2-channel groups of the *_c ones are zero-padded
 Every conv is the implicit-GEMM MFMA kernel, every BN(+ReLU)(+residual) one fused HBM-bound kernel pair; the image
 enters as NHWC with C padded 3 -> 4."""
 import math
-import os
 
 import torch
 from torch import nn
@@ -18,10 +17,6 @@ from ....kernels import conv as kconv
 from ..layers import BatchNorm2d, Conv2d, GroupedConv2d
 from ..registries import BACKBONE_REGISTRY
 from .fpn import FPN, Backbone
-
-_ROOT_MULTI_SRC = os.environ.get("OMNI_ROOT_MULTI_SRC", "1") != "0"     # A/B knob: 0 = Root concatenates its children (rounds 1-4)
-_SHARE_POOL = os.environ.get("OMNI_DLA_SHARE_POOL", "1") != "0"      # A/B knob: nested trees pool their common input once
-_SIDE_STATS = os.environ.get("OMNI_DLA_SIDE_STATS", "1") != "0"      # A/B knob: statistics-only projections of nested trees on the weight-gradient stream
 
 
 class ConvBNReLU(nn.Sequential):
@@ -123,7 +118,7 @@ class Root(nn.Module):
 
     def forward(self, *x):
         conv = self.conv
-        if _ROOT_MULTI_SRC and conv.kernel_size == (1, 1) and conv.bias is None and kconv.multi_src_eligible(x, conv.weight):
+        if conv.kernel_size == (1, 1) and conv.bias is None and kconv.multi_src_eligible(x, conv.weight):
             # the 1 x 1 convolution reads its reduction slabs from the children directly: torch.cat(x, 1) is never formed (six
             # copies of 7-16 us on the critical path of the 4 x 512 x 512 step, and as many in an inference pass)
             want_stats = self.bn.training and torch.is_grad_enabled()      # (a frozen BatchNorm reads no batch statistics)
@@ -178,9 +173,9 @@ class Tree(nn.Module):
             # run it for its BatchNorm's running statistics only -- no autograd graph, no saved activations; not at all when that
             # BatchNorm is frozen (freeze_bn: nothing to update)
             live = self.project[1].training
-            if live and _SIDE_STATS and HF.side_mode() == "collect":
+            if live and HF.side_mode() == "collect":
                 # a step being captured: nothing in the step reads that BatchNorm's running statistics, so the 1 x 1 convolution + statistics
-                # leave the critical path and replay in the stage's weight-gradient graph (late round 6; OMNI_DLA_SIDE_STATS=0: inline)
+                # leave the critical path and replay in the stage's weight-gradient graph (late round 6)
                 src = bottom.detach()
 
                 def stats_only(src=src):
@@ -199,7 +194,7 @@ class Tree(nn.Module):
             x1 = self.tree1(x, residual)
         else:
             t1 = self.tree1
-            shared = bottom if _SHARE_POOL and (t1.downsample is None) == (self.downsample is None) else None
+            shared = bottom if (t1.downsample is None) == (self.downsample is None) else None
             x1 = t1(x, residual, bottom=shared)
         HF.fanout(x1)
         if self.levels == 1:

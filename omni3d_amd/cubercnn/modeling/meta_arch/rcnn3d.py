@@ -20,9 +20,6 @@ from ..roi_heads import build_roi_heads
 from ..targets import pack_targets
 
 
-_EVAL_F22 = __import__("os").environ.get("OMNI_EVAL_F22", "1") != "0"       # A/B knob
-
-
 @META_ARCH_REGISTRY.register()
 class RCNN3D(nn.Module):
     @configurable
@@ -122,8 +119,6 @@ class RCNN3D(nn.Module):
 
     def _forward(self, batched_inputs, packed=None):
         if not self.training:
-            if not _EVAL_F22:
-                return self.inference(batched_inputs, packed=packed, _replay_tried=True)
             # Inference runs every Winograd layer on the 16-point F(2x2,3x3) transform: the cube head's Gram-Schmidt amplifies feature
             # noise up to ~300x for near-parallel 6D pose vectors (tools/probes/pose_diag.py), and the 36-point transform of the
             # bottom-up is what that noise is made of -- worst pose / corner error of the full-size fixture against float64 2.9e-4
@@ -209,8 +204,7 @@ class RCNN3D(nn.Module):
         def context():
             st = contextlib.ExitStack()
             st.enter_context(HF.wino_weight_scope(self))
-            if _EVAL_F22:
-                st.enter_context(_wino.f22_only())
+            st.enter_context(_wino.f22_only())
             return st
         got = rep.run(batched_inputs, context)
         if got is None:

@@ -20,8 +20,6 @@ from ..layers import Conv2d
 from ..registries import PROPOSAL_GENERATOR_REGISTRY, RPN_HEAD_REGISTRY
 
 CL = torch.channels_last
-import os as _os
-_FUSED_HEAD = _os.environ.get("OMNI_RPN_HEAD16", "1") != "0"      # A/B knob: the two 1x1 heads of all levels as one launch per direction
 
 
 @RPN_HEAD_REGISTRY.register()
@@ -57,7 +55,7 @@ class StandardRPNHead(nn.Module):
 
     def forward(self, features):
         wl, wd = self.objectness_logits.weight, self.anchor_deltas.weight
-        if _FUSED_HEAD and HF.rpn_head16_eligible(features, wl, wd):
+        if HF.rpn_head16_eligible(features, wl, wd):
             # both 1x1 heads over every level: one HBM-bound launch per direction (csrc/rpn_head.hip)
             return HF.rpn_head16(self._shared_conv(features), wl, self.objectness_logits.bias, wd, self.anchor_deltas.bias)
         w16 = torch.cat([wl, wd, wl.new_zeros(1, wl.shape[1], 1, 1)], dim=0)
@@ -207,7 +205,7 @@ class RPNWithIgnore(nn.Module):
             self.__dict__["_last_hw_list"] = hw_list
             hook = self.__dict__.get("_label_split")
             if hook is not None:
-                # a step being captured in pipelined form (solver/graphed.py, OMNI_PIPE_LABELS): anchor labelling + sampling read only
+                # a step being captured in pipelined form (solver/graphed.py _split_labels): anchor labelling + sampling read only
                 # the anchors and the ground truth, so they were captured as a graph of their own that replays on the idle
                 # weight-gradient stream beside the bottom-up; the critical-path graph is cut HERE and its second half starts behind both
                 labels, matched_idx = hook()

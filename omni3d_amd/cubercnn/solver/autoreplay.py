@@ -87,6 +87,7 @@ GUARD_MISS = float(os.environ.get("OMNI_AUTO_REPLAY_MISS", "0.25"))
 # without it the guard's only escalation is "no new captures".
 GRIDS = tuple(int(v) for v in os.environ.get("OMNI_AUTO_REPLAY_GRIDS", "").split(",") if v)
 GRID_ABOVE = int(os.environ.get("OMNI_AUTO_REPLAY_GRID_ABOVE", "256"))
+CAPTURE_WARMUP = 1       # muted warm-up passes inside a capture (round 6: 1, was 3)
 ROW_FIELDS = ("gt", "gt_cls", "gt3d", "gtpose", "ign")           # (rows, ...) arrays indexed through gt_off / ign_off
 FIXED_FIELDS = ("gt_off", "ign_off", "Ks", "v2r", "ratio", "image_hw")
 
@@ -136,10 +137,9 @@ class _Boundary(Function):
 
 
 class AutoReplay:
-    def __init__(self, model, optimizer, warm=None, graphs=None):
-        # eager iterations a size bucket runs before it is captured.  Round 6: 1 (was 2) -- with a cache that holds every bucket of the
+    def __init__(self, model, optimizer, warm=1, graphs=None):
+        # warm: eager iterations a size bucket runs before it is captured.  Round 6: 1 (was 2) -- with a cache that holds every bucket of the
         # reference's loader a capture is never wasted on a shape that will not come back, and every eager iteration saved is one replayed
-        warm = int(os.environ.get("OMNI_AUTO_REPLAY_WARM", "1")) if warm is None else warm
         self.model, self.opt, self.warm = model, optimizer, warm
         self.graphs = graphs                     # None: hipGraphs on a GPU, eager staged launches elsewhere (CPU tests)
         self.cache = OrderedDict()               # bucket -> captured step (stepper, static batch / targets, logged scalars)
@@ -356,7 +356,7 @@ class AutoReplay:
         # The graphs die by reference count when the holders let go; the collector is the safety net for a cycle through one of them.
         # Only the young generations: the holders are at most four iterations old, and a FULL collection walks the whole heap of the
         # training process (dataset dicts, loader state) -- measured 83 ms of a 210 ms capture (round 6, OMNI_AUTO_REPLAY_TIMING=1).
-        gc.collect() if os.environ.get("OMNI_AUTO_REPLAY_FULL_GC") == "1" else gc.collect(1)
+        gc.collect(1)
 
     def _drop(self):
         """forget every captured step (a failure, or a loop the protocol does not cover)"""
@@ -449,8 +449,8 @@ class AutoReplay:
         self.busy = True
         try:
             # (one muted warm-up pass inside the capture instead of three: the bucket's eager iterations have already built every
-            # lazily-made constant of this shape; OMNI_AUTO_REPLAY_CAPTURE_WARMUP restores more)
-            stepper = GraphedPipelined(model, self.opt, sb, packed, graphs=graphs, warmup=int(os.environ.get("OMNI_AUTO_REPLAY_CAPTURE_WARMUP", "1")),
+            # lazily-made constant of this shape)
+            stepper = GraphedPipelined(model, self.opt, sb, packed, graphs=graphs, warmup=CAPTURE_WARMUP,
                                        pools=self.pools if SHARE_POOLS else None)
         finally:
             self.busy = False

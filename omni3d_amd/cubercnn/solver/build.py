@@ -664,7 +664,7 @@ def grad_stage_map(model):
     the bottom-up declares them (`backward_stages()`: {name prefix: stage}); a backbone without cut points is stage 1 as a whole."""
     bu = getattr(getattr(model, "backbone", None), "bottom_up", None)
     table = bu.backward_stages() if (bu is not None and hasattr(bu, "backward_stages")) else {}
-    # the cut at the pooled ROI features (graphed.py POOL_CUT) makes the FC heads stage 0 and everything whose gradient completes
+    # the cut at the pooled ROI features (graphed.py _pool_cut) makes the FC heads stage 0 and everything whose gradient completes
     # with ROIAlign's / the RPN's backward stage 1; the backbone's stages move down by one
     shift = 1 if pool_cut_active(model) else 0
 
@@ -681,9 +681,8 @@ def grad_stage_map(model):
 
 
 def pool_cut_active(model):
-    from .graphed import POOL_CUT
     heads = getattr(model, "roi_heads", None)
-    return bool(POOL_CUT and heads is not None and hasattr(type(heads), "pool_cut") and hasattr(getattr(model, "proposal_generator", None), "forward"))
+    return bool(heads is not None and hasattr(type(heads), "pool_cut") and hasattr(getattr(model, "proposal_generator", None), "forward"))
 
 
 def build_optimizer(cfg, model):

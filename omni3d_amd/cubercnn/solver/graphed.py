@@ -70,41 +70,13 @@ class lean_capture:
 _GRAPH_DUMP = __import__("os").environ.get("OMNI_GRAPH_DUMP", "")
 
 
-def make_side_stream(device=None):
+def make_side_stream():
     """The weight-gradient stream.  The critical path runs on the main stream and is ~92 % busy (rocprofv3 trace, queue 1: 11.4 of
-    12.4 ms); whatever the side stream runs beside it competes for the same CUs, and a PERSISTENT side kernel (the fc1-class weight
-    gradient on the GEMM engine: one workgroup per CU for 0.57 ms) stops every main-stream kernel that cannot co-reside with it
-    until it ends (a 50 us data gradient measured at 557 us).  Two knobs bound that:
-      OMNI_SIDE_CUS=n       the side stream's queue is created on n of the 256 CUs (hipExtStreamCreateWithCUMask; the mask bits are
-                            spread over the XCDs), so the critical path always finds 256 - n CUs free of weight-gradient work;
-      OMNI_SIDE_PRIORITY=p  stream priority of the side stream (torch: lower value = higher priority; 0 = default).
-    Defaults are the measured optimum (profiles/r03_ab_side_stream.log)."""
-    import ctypes
-    import os
-    n = int(os.environ.get("OMNI_SIDE_CUS", str(SIDE_CUS_DEFAULT)))
-    prio = int(os.environ.get("OMNI_SIDE_PRIORITY", "0"))
-    if 0 < n < 256:
-        hip = ctypes.CDLL("libamdhip64.so")
-        dev = torch.cuda.current_device() if device is None else torch.device(device).index
-        with torch.cuda.device(dev):
-            words = (ctypes.c_uint32 * 8)()
-            for bit in range(n):                # bits 0 .. n-1: KFD deals consecutive mask bits round-robin over the XCDs
-                words[bit // 32] |= 1 << (bit % 32)
-            st = ctypes.c_void_p()
-            rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(st), 8, words)
-            if rc == 0 and st.value:
-                _MASKED_STREAMS.append(st)      # (never destroyed: lives as long as the process, like torch's pooled streams)
-                return torch.cuda.ExternalStream(st.value, device=dev)
-    if prio != 0:
-        return torch.cuda.Stream(priority=prio)
+    12.4 ms); whatever the side stream runs beside it competes for the same CUs.  A plain stream: a CU mask (128 / 192 / 96 of the
+    256 CUs) and a lower stream priority were measured and lost (profiles/r03_ab_side_stream.log)."""
     return torch.cuda.Stream()
 
 
-SIDE_CUS_DEFAULT = 0            # 0 = no mask
-# round 4: a cut at the pooled ROI features + the RPN losses deferred to that cut's stage, so stage 0 = forward + the FC heads'
-# backward and W_0 (the fc1-class weight gradients, 1.1 ms of work) runs beside ROIAlign's / the RPN's backward instead of beside
-# FPN + level 5 / 4 (A/B knob; the gradient bucket's stage layout follows it, solver/build.py)
-POOL_CUT = __import__("os").environ.get("OMNI_PIPE_POOL_CUT", "1") != "0"
 _PIPE_TIMING = __import__("os").environ.get("OMNI_PIPE_TIMING", "0") == "1"
 
 
@@ -152,7 +124,6 @@ def pipe_timing_table(graphed, last=10):
     return {"M_end_ms": [mean("m", k) for k in range(n)], "W_end_ms": [mean("w", k) for k in range(n)], "X_end_ms": [mean("x", k) for k in range(n)],
             "steps": len(recs), "note": "device timestamps after the step's first launch: end of stage k's critical-path graph (M), of its "
                                         "weight-gradient graph (W) and of the all-reduce calls issued behind it (X)"}
-_MASKED_STREAMS = []
 
 
 class FeatureCut:
@@ -374,11 +345,6 @@ class GraphedPipelined:
         self.pools = pools
         self.cuts = StageCuts()
         self._install()
-        bottom_up = getattr(getattr(model, "backbone", None), "bottom_up", None)
-        if bottom_up is not None and hasattr(type(bottom_up), "stage_cut"):
-            import os
-            if os.environ.get("OMNI_PIPE_CUTS") is not None:       # A/B knob: "" | "p2" | "p2,p3" | "p2,p3,p4" | "p2,p3,p4,p5"
-                bottom_up.stage_cut_at = tuple(x for x in os.environ["OMNI_PIPE_CUTS"].split(",") if x)
         self.stages = None
         self._timing = []
         if not graphs:
@@ -476,11 +442,10 @@ class GraphedPipelined:
     # computes.  Stage 0 is captured as THREE graphs: L (those four launches; replayed on the weight-gradient stream, which idles through
     # all of forward), M0a (zero_grad .. RPN head) and M0b (losses, proposals, ROI heads, the heads' backward), which starts behind both.
     # (A prologue of the Winograd filter transforms, captured the same way, was measured neutral: profiles/r04_ab_prologue.log.)
-    # L moves no memory to speak of: it hides completely.  OMNI_PIPE_LABELS=0 switches it off.
+    # L moves no memory to speak of: it hides completely.
     def _split_labels(self):
-        import os
         rpn = getattr(self.model, "proposal_generator", None)
-        return (os.environ.get("OMNI_PIPE_LABELS", "1") != "0" and rpn is not None and hasattr(rpn, "label_and_sample_anchors")
+        return (rpn is not None and hasattr(rpn, "label_and_sample_anchors")
                 and rpn.__dict__.get("_last_hw_list") is not None and getattr(rpn, "injected", None) is None and self.static_packed is not None)
 
     def _capture_stage0_labels(self, pool_m, pool_w):
@@ -534,9 +499,12 @@ class GraphedPipelined:
         if bottom_up is not None and hasattr(type(bottom_up), "stage_cut"):
             bottom_up.stage_cut = self.cuts
         heads = getattr(self.model, "roi_heads", None)
-        if heads is not None and hasattr(type(heads), "pool_cut") and POOL_CUT:
+        if heads is not None and hasattr(type(heads), "pool_cut"):
             heads.pool_cut = self._pool_cut
 
+    # round 4: a cut at the pooled ROI features + the RPN losses deferred to that cut's stage, so stage 0 = forward + the FC heads'
+    # backward and W_0 (the fc1-class weight gradients, 1.1 ms of work) runs beside ROIAlign's / the RPN's backward instead of beside
+    # FPN + level 5 / 4 (heads that have a `pool_cut`; the gradient bucket's stage layout follows it, solver/build.py pool_cut_active)
     def _pool_cut(self, xs):
         self._pool_cut_made = True
         return self.cuts(xs)

@@ -146,8 +146,9 @@ def _carry_pitch(c):
 #                    ROCm 7.2 replays such a graph node by node from the host, 12 ms per step instead of 0.7 ms.)
 # Inputs of queued closures are kept referenced until they have run and been joined, so the caching allocator cannot hand
 # their memory to a main-stream kernel early.
+SIDE_BATCH = 8      # closures per flush of the eager side stream
 _side = {"mode": "stream" if _os_environ_get("OMNI_WGRAD_STREAM", "1") != "0" else "inline",
-         "batch": int(_os_environ_get("OMNI_WGRAD_BATCH", "8")), "streams": {}, "pending": [], "queue": [], "main": None}
+         "batch": SIDE_BATCH, "streams": {}, "pending": [], "queue": [], "main": None}
 
 
 def side_mode(mode=None):
@@ -199,14 +200,12 @@ def _side_run(fn, keepalive):
     return None
 
 
-BIAS_GRAD_SIDE = _environ.get("OMNI_BIAS_GRAD_SIDE", "1") != "0"
-
-
 def _bias_grad(dy2d, gb):
     """column sums of dy (P, C) -> the bias gradient.  With a view of the gradient bucket to add into, the two launches (partial
     rows + fixed-order finalize) go to the weight-gradient stream like the filter gradient: nothing on the critical path reads them
-    (round 4: 44 launches, 0.27 ms per step, sat between the data-gradient kernels of the FPN / RPN / head layers)."""
-    if gb is None or not BIAS_GRAD_SIDE:
+    (round 4: 44 launches, 0.27 ms per step, sat between the data-gradient kernels of the FPN / RPN / head layers; 11.70 -> 11.46 ms,
+    profiles/r04_ab_bias_side.log)."""
+    if gb is None:
         return bnpool.bias_grad(dy2d, accum_into=gb)
     return _side_run(lambda: bnpool.bias_grad(dy2d, accum_into=gb), (dy2d,))
 
@@ -238,7 +237,7 @@ def _relu_already_masked(dy):
         return False
     if tag is not True and dy._version != tag:
         raise RuntimeError("omni3d_amd: the gradient of a convolution whose ReLU mask was applied by its consumer (fused RPN head) was "
-                           "modified in place afterwards -- a second consumer of that convolution's output; set OMNI_RPN_HEAD16=0")
+                           "modified in place afterwards -- a second consumer of that convolution's output")
     return True
 
 
@@ -479,9 +478,6 @@ def rpn_head16(ts, w_obj, b_obj, w_del, b_del):
 _wino_scope = {"cache": None, "record": []}     # (weight address, shape) -> (U, U'), only while a model forward is running
 
 
-_WINO_MULTI = _os_environ_get("OMNI_WINO_WEIGHTS_MULTI", "1") != "0"          # A/B knob
-
-
 class wino_weight_scope:
     """`with wino_weight_scope(owner):` around one forward pass.  A weight used by several convolutions of that pass (the RPN conv
     over the FPN levels) is transformed once; and the pass remembers on `owner` (the model) which filters it transformed, so the
@@ -496,7 +492,7 @@ class wino_weight_scope:
         cache = _wino_scope["cache"] = {}
         _wino_scope["record"] = []
         self.kind = "_omni_wino_plan_train" if torch.is_grad_enabled() else "_omni_wino_plan_infer"
-        plan = getattr(self.owner, self.kind, None) if (self.owner is not None and _WINO_MULTI) else None
+        plan = getattr(self.owner, self.kind, None) if self.owner is not None else None
         if plan:
             items = [(w, True, flip, tile) for w, tile, flip in plan if w.is_contiguous(memory_format=CL)]
             for k in range(0, len(items), wino.WEIGHTS_MULTI_MAX):
@@ -521,13 +517,10 @@ class wino_weight_scope:
 
 
 
-_WINOGRAD = _os_environ_get("OMNI_WINOGRAD", "1") != "0"
-
-
 def conv2d(x, w, bias=None, stride=1, pad=0, relu=False, want_stats=False):
     """want_stats: the caller is a conv -> BatchNorm pair in training mode; the result then carries `_omni_bn_partials`
     (per-workgroup sums / sums of squares written by the kernel that produced it) when the chosen kernel could emit them."""
-    if _WINOGRAD and wino.eligible(x.shape, w.shape, stride, pad):
+    if wino.eligible(x.shape, w.shape, stride, pad):
         y, parts = _WinoConv3x3.apply(x, w, bias, relu, want_stats)
     else:
         y, parts = _Conv2d.apply(x, w, bias, stride, pad, relu, want_stats)
@@ -635,7 +628,6 @@ def fused_linear(x, weights, biases, rows, relu=False):
     return _Linear.apply(x, w, b, relu, None, None)
 
 
-_BN_REMASK = _os_environ_get("OMNI_BN_REMASK", "1") != "0"     # A/B knob
 # backward reductions from the data-gradient transform above the layer (wino.transform_output_bn_bwd): the F(4x4) output transform that
 # writes a BatchNorm's output gradient also emits that layer's (sum dz, sum dz * xhat) partial rows, so its backward is ONE launch
 # (finalize folded into the apply pass, csrc/bn_pool.hip) instead of a reduction pass + apply.  Round 3 measured it neutral with the
@@ -655,7 +647,7 @@ class _BatchNorm(Function):
         y, mean_rstd, scale_shift = bnpool.bn_fwd(x, gamma, beta, running_mean, running_var, res, relu, eps, momentum, partials)
         # ReLU mask for the backward pass: the output y, or (no residual) the 2C-float (scale, shift) pair -- y > 0 is then
         # recomputed from x, which the backward kernels read anyway, and y is not read again (bnpool.bn_bwd)
-        remask = relu and residual is None and _BN_REMASK
+        remask = relu and residual is None
         ctx.save_for_backward(x, gamma, mean_rstd, (y if relu and not remask else None), (scale_shift if remask else None))
         ctx.cfg = (relu, residual is not None)
         if _BN_BWD_FUSE and residual is None and (remask or not relu):
@@ -708,7 +700,7 @@ class _FrozenBatchNorm(Function):
         res = _cl(residual) if residual is not None else None
         y = bnpool.bn_frozen_fwd(x, gamma, beta, running_mean, running_var, res, relu, eps)
         # ReLU mask for the backward pass: the output y, or (no residual) recomputed from x and the coefficients the kernel makes anyway
-        remask = relu and residual is None and _BN_REMASK
+        remask = relu and residual is None
         ctx.save_for_backward(x, gamma, beta, running_mean, running_var, (y if relu and not remask else None))
         ctx.cfg = (relu, residual is not None, remask, eps)
         return y

@@ -1,7 +1,5 @@
 """Launchers for csrc/bn_pool.hip.  All tensors are logical NCHW in channels_last memory
 (physically NHWC), fp32, C % 4 == 0."""
-import os
-
 import torch
 
 from .. import lib as _lib
@@ -13,8 +11,8 @@ def _like_cl(shape_nhwc, ref):
 
 
 # partial rows up to which the finalize is folded into the apply launch (omni_bn_fwd_algo / omni_bn_bwd_algo); 0 = the separate finalize
-# launch of rounds 1-4.  Read once: an A/B knob for bench runs, the tests and the driver leave it unset.
-FUSE_ROWS = int(os.environ.get("OMNI_BN_FUSE_ROWS", "512"))
+# launch of rounds 1-4 (profiles/r05_ab_bn_fuse.log)
+FUSE_ROWS = 512
 
 
 def _pitched_out(out, N, H, W, C):
@@ -123,7 +121,7 @@ def bn_frozen_bwd(x, dy, y, gamma, beta, running_mean, running_var, eps=1e-5, re
 def bn_bwd(x, dy, y, gamma, mean_rstd, relu=False, want_dres=False, accum_into=None, scale_shift=None, partials=None, res_carry=None):
     """-> (dx CL, dres CL or None, dgamma, dbeta).  accum_into = (dgamma_buf, dbeta_buf): the parameter
     gradients are added to those buffers instead (dgamma/dbeta returned as None).  scale_shift (2C, from bn_fwd) instead of y:
-    the ReLU mask of a layer WITHOUT residual is recomputed from x (mode 2 of omni_bn_bwd), the output tensor is not read.
+    the ReLU mask of a layer WITHOUT residual is recomputed from x (mode 2 of omni_bn_bwd_algo), the output tensor is not read.
     partials (nblk, 2C): the reductions over dy already made by the kernel that produced dy (wino.transform_output_bn_bwd).
     res_carry: gradient fan-in of the residual tensor (logical NCHW, NHWC memory, any pixel pitch: functional._carry_pitch), added
     to dres where it is written.  dy may be such a pitched tensor too (a channel slice of the Root's concatenated gradient)."""

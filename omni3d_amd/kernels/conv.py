@@ -5,7 +5,6 @@ Tensors cross this boundary in torch's channels_last memory format: logically (N
 free contiguous view.  Channel counts must be multiples of 4 (16-byte loads); callers pad the
 3-channel image and the odd-sized prediction heads.
 """
-import os
 
 import torch
 
@@ -149,21 +148,17 @@ def stem_conv_fwd_stats(x, w):
     return out.permute(0, 3, 1, 2), (stats[:cell.value] if cell.value > 0 else None)
 
 
-_S2_DGRAD = os.environ.get("OMNI_S2_DGRAD", "1") != "0"            # A/B knob: 0 = the generic kernel's four grid.z parity classes
-_S2_DGRAD_MIN_WGS = int(os.environ.get("OMNI_S2_DGRAD_MIN_WGS", "192"))
-# the 32-channel form (DLA level 2's entry, 32 -> 64 at 256 x 256): 35 us alone against the generic kernel's 56; INSIDE the step its own
+_S2_DGRAD_MIN_WGS = 192        # workgroups a layer needs for csrc/dgrad_s2.hip (swept in round 6, tools/bench_s2_dgrad.py)
+# its 32-channel form (DLA level 2's entry, 32 -> 64 at 256 x 256): 35 us alone against the generic kernel's 56; INSIDE the step its own
 # row reads 128 us against 84 (profiles/r06_trace_table_final.txt: end of backward, beside the busiest stretch of the weight-gradient
 # stream) and the STEP is still the shorter one with it: 10.753 / 10.756 ms against 10.772 / 10.766 without (profiles/r06_ab_s2_dgrad_c32.log)
-# -- what it leaves to the other stream counts too.  OMNI_S2_DGRAD_C32=0 switches this form off.
-_S2_DGRAD_C32 = os.environ.get("OMNI_S2_DGRAD_C32", "1") != "0"
+# -- what it leaves to the other stream counts too.
 
 
 def s2_dgrad_eligible(N, H, W, C, K, R, S, stride, pad):
     """3x3 / stride 2 / pad 1 with channel counts in multiples of 32, and enough 8 x 8 dy tiles (x 64-channel groups) to fill the chip:
     the small-map layers (DLA level 4 / 5 entries at 512 x 512 input: 64 and 16 tiles) stay on the split-K form of the generic kernel"""
-    if not _S2_DGRAD or (R, S, stride, pad) != (3, 3, 2, 1) or (C % 32) or (K % 32):
-        return False
-    if C % 64 and not _S2_DGRAD_C32:
+    if (R, S, stride, pad) != (3, 3, 2, 1) or (C % 32) or (K % 32):
         return False
     OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     wgs = N * ((OH + 7) // 8) * ((OW + 7) // 8) * (C // 64 if C % 64 == 0 else C // 32)
@@ -269,9 +264,6 @@ def linear_fwd(x, w, bias=None, relu=False):
     return out
 
 
-_DGRAD_NT = os.environ.get("OMNI_FC_DGRAD_NT", "1") != "0"
-_DGRAD_FORM = os.environ.get("OMNI_FC_DGRAD_FORM", "nn")            # "nn": the engine reads W as it is | "nt": transpose W first (rounds 2-3)
-_FC_BALANCED = os.environ.get("OMNI_FC_BALANCED", "1") != "0"
 # Round 5: the fc1-class WEIGHT gradient is back on the tile kernel.  It runs on the weight-gradient stream beside the critical path, and
 # the engine's balanced 128 x 128 form compiles to 256 VGPRs + 154 AGPRs = 410 registers per lane (one workgroup per CU because of its
 # 96 KB of LDS, so hipcc budgets the whole file): while its 256 persistent workgroups hold every CU, no wave that needs more than ~100
@@ -284,14 +276,12 @@ def linear_dgrad(dy, w):
     M, K = dy.shape
     C = w.shape[1]
     L = _lib.check_device(dy, w)
-    if _DGRAD_NT and M >= 512 and C >= 4096 and K >= 512 and (K % 32) == 0:
+    if M >= 512 and C >= 4096 and K >= 512 and (K % 32) == 0:
         # fc1-class data gradient dX = dY W on the LDS-DMA engine.  Round 4: its NN form reads W as it is (box head 494 us, cube head 160 us,
         # same sums bit for bit); rounds 2-3 transposed W first (51 MB, two launches per step on the critical path) for the NT main
-        # loop: 540 / 175 us including the transpose (profiles/r04_fc1_nn.log).  OMNI_FC_DGRAD_FORM=nt: the old form
+        # loop: 540 / 175 us including the transpose (profiles/r04_fc1_nn.log)
         from . import gemm as _gemm
-        if _DGRAD_FORM == "nt":
-            return _gemm.gemm(dy, _gemm.transpose2d(w), _gemm.NT, tile=2, splits=_gemm.BALANCED if _FC_BALANCED else 1)
-        return _gemm.gemm(dy, w, _gemm.NN, tile=2, splits=_gemm.BALANCED if _FC_BALANCED else 1)
+        return _gemm.gemm(dy, w, _gemm.NN, tile=2, splits=_gemm.BALANCED)
     dx = torch.empty((M, C), dtype=torch.float32, device=dy.device)
     _dgrad_launch(L, _lib.ptr(dy), _lib.ptr(w), _lib.ptr(dx), M, 1, 1, C, K, 1, 1, 1, 0, K, C, 0, 0, 0, dy)
     return dx
@@ -362,14 +352,11 @@ def stem_first_wgrad(x, dy, accum_into=None):
     return None if accum_into is not None else dst.permute(0, 3, 1, 2)
 
 
-_STEM_DGRAD = os.environ.get("OMNI_STEM_DGRAD", "1") != "0"        # A/B: 0 = the round-4 data gradients of level0 / level1
-
-
 def stem_dgrad_eligible(x_shape, w_shape, stride, pad):
     """data gradients served by csrc/stem_conv.hip (round 5): 3x3 16 -> 16 stride 1 (level0, filter rotated inside the kernel) and
     3x3 stride 2 pad 1 16 -> 32 (level1, parity classes inside one launch)"""
     K, C, R, S = w_shape
-    if not _STEM_DGRAD or R != 3 or S != 3 or pad != 1 or C != 16 or x_shape[1] != 16:
+    if R != 3 or S != 3 or pad != 1 or C != 16 or x_shape[1] != 16:
         return False
     return (stride == 1 and K == 16) or (stride == 2 and K == 32)
 
@@ -387,9 +374,6 @@ def stem_conv_dgrad(dy, w, in_hw, stride):
     return dx.permute(0, 3, 1, 2)
 
 
-_STEM_WGRAD_ALL = os.environ.get("OMNI_STEM_WGRAD_ALL", "1") != "0"       # A/B: 0 = only the 16 -> 16 stride-1 layer (rounds 2-3)
-
-
 def stem_wgrad_eligible(x_shape, w_shape, stride, pad):
     """weight gradients served by stem_conv_wgrad_kernel: the two stride-1 stem layers and (16 -> 32, 3x3, stride 2) = DLA-34 level1.
     The 4-channel 7x7 form only with the deterministic reductions on: its 3136-element filter gradient met 3072 waves' worth of
@@ -398,8 +382,8 @@ def stem_wgrad_eligible(x_shape, w_shape, stride, pad):
     if R != S or pad != R // 2 or x_shape[1] != C:
         return False
     if stride == 1:
-        return K == 16 and ((C, R) == (16, 3) or ((C, R) == (4, 7) and _det.on() and _STEM_WGRAD_ALL))
-    return _STEM_WGRAD_ALL and stride == 2 and (K, C, R) == (32, 16, 3) and x_shape[2] % 2 == 0 and x_shape[3] % 2 == 0
+        return K == 16 and ((C, R) == (16, 3) or ((C, R) == (4, 7) and _det.on()))
+    return stride == 2 and (K, C, R) == (32, 16, 3) and x_shape[2] % 2 == 0 and x_shape[3] % 2 == 0
 
 
 def stem_conv_wgrad(x, dy, R, accum_into=None, stride=1):

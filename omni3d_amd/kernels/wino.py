@@ -10,12 +10,9 @@ CL = torch.channels_last
 
 import os as _os
 
-_F43 = _os.environ.get("OMNI_WINOGRAD_F43", "1") != "0"
-_F43_MIN_TILES = int(_os.environ.get("OMNI_WINOGRAD_F43_MIN_TILES", "256"))     # measured: 1024 -> 14.18, 256 -> 14.02, 64 -> 14.05 ms / step
-
-
-_MIN_TILES = int(_os.environ.get("OMNI_WINO_MIN_TILES", "256"))                 # 2x2 tiles a map needs for the Winograd path at all
-_DGRAD_MIN_TILES = int(_os.environ.get("OMNI_WINO_DGRAD_MIN_TILES", "256"))     # ... and for the Winograd data gradient (round 3: 1024 -> 256,
+_F43_MIN_TILES = 256        # 4x4 tiles a map needs for F(4x4,3x3); measured: 1024 -> 14.18, 256 -> 14.02, 64 -> 14.05 ms / step
+_MIN_TILES = 256            # 2x2 tiles a map needs for the Winograd path at all
+_DGRAD_MIN_TILES = 256      # ... and for the Winograd data gradient (round 3: 1024 -> 256,
 #   the deep-prefetch point GEMMs made the 16x16 maps pay: 13.60 -> 13.55 ms / step, profiles/r03_ab_thresholds.log)
 
 
@@ -55,7 +52,7 @@ def tile_size(x_shape):
     N, _, H, W = x_shape
     if _f22_depth > 0:
         return 2
-    return 4 if (_F43 and H % 4 == 0 and W % 4 == 0 and N * (H // 4) * (W // 4) >= _F43_MIN_TILES) else 2
+    return 4 if (H % 4 == 0 and W % 4 == 0 and N * (H // 4) * (W // 4) >= _F43_MIN_TILES) else 2
 
 
 def dgrad_eligible(x_shape):
@@ -167,8 +164,7 @@ def gemm_batched_wgrad(V, dM, algo=0):
     return dU
 
 
-WGRAD_MULTI_MAX = max(1, min(16, int(_os.environ.get("OMNI_WGRAD_MULTI_MAX", "16"))))      # problems per launch (A/B knob; the kernel takes <= 16)
-WGRAD_MULTI = _os.environ.get("OMNI_WGRAD_MULTI", "1") != "0"
+WGRAD_MULTI_MAX = 16        # problems per launch: all the kernel takes (TN_MULTI_MAX in csrc/conv_gemm.hip)
 _deferred = None        # [(V, dM, dU, accum_into)] while a batched_wgrads() context is open
 
 
@@ -187,10 +183,6 @@ def gemm_batched_wgrad_multi(problems):
             ints([V.shape[0] for V, _ in problems]), ints([V.shape[1] for V, _ in problems]), ints([V.shape[2] for V, _ in problems]),
             ints([dM.shape[2] for _, dM in problems]), n)
     V0 = problems[0][0]
-    if _os.environ.get("OMNI_WGRAD_MULTI_LOG") == "1":       # (tools: which problems a launch holds, for the in-step roofline figures)
-        gf = sum(2.0 * V.shape[0] * V.shape[1] * V.shape[2] * dM.shape[2] for V, dM in problems) / 1e9
-        print(f"gemm_tn_multi: {n} problems, {gf:.2f} GFLOP: " + " ".join(f"{V.shape[0]}x[{V.shape[1]}x{dM.shape[2]}x{V.shape[2]}]" for V, dM in problems),
-              flush=True)
     if _det.on():
         _det.plan_launch(L, "omni_gemm_batched_wgrad_multi", V0, head)
     else:
@@ -249,7 +241,7 @@ def transform_dweights_multi(items):
 def wgrad_into(V, dM, accum_into):
     """accum_into (KRSC-contiguous gradient view) += the weight gradient of a Winograd layer: V its transformed input, dM its
     transformed output gradient.  Inside batched_wgrads() the GEMM joins the context's launch."""
-    if _deferred is None or not WGRAD_MULTI or not _multi_fits(V, dM):
+    if _deferred is None or not _multi_fits(V, dM):
         return transform_dweights(gemm_batched_wgrad(V, dM), accum_into)
     _deferred.append((V, dM, accum_into))
     return None

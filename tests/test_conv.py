@@ -17,7 +17,7 @@ CASES = [
     (1, 7, 6, 16, 24, 1, 2, 0),     # 1x1/s2 (ResNet downsample): three of the four dgrad classes have no taps -> zeros
     (1, 12, 10, 4, 16, 7, 2, 3),    # 7x7/s2 ResNet stem
     (2, 5, 6, 16, 72, 3, 1, 1),     # wgrad 128x128 tile (K > 64, R*S*C > 64), pixel cursor wrapping rows and images
-    (2, 32, 40, 64, 128, 3, 1, 1),  # wgrad: 9 tiles x 10 pixel splits (with OMNI_WGRAD_XCD_SPLITS=1: 8 of them dealt out per XCD, 2 in the plain order)
+    (2, 32, 40, 64, 128, 3, 1, 1),  # wgrad: 9 tiles x 10 pixel splits
 ]
 
 
@@ -255,20 +255,8 @@ def _run_prefetch_gemm(dev):
         ref = torch.einsum("bmc,bkc->bmk", V.cpu().double(), U.cpu().double())
         assert (out.cpu().double() - ref).abs().max() <= 1e-4 * ref.abs().max(), (B, M, K, C)
         assert torch.equal(out, wino.gemm_batched(V, U, algo=3)), (B, M, K, C)
-        # the persistent form (gemm_nt_pfp_kernel, slab stream running through the tile boundaries): 8 workgroups = one per XCD
-        # chunk walking several tiles each, 16 = two per chunk, 1024 = more workgroups than tiles (clamped); bit-identical
-        for wgs in (8, 16, 1024):
-            assert torch.equal(out, wino.gemm_batched(V, U, algo=5, workgroups=wgs)), (B, M, K, C, wgs)
-    g5 = torch.Generator().manual_seed(10)
-    V, U = torch.randn(5, 200, 128, generator=g5).to(dev), torch.randn(5, 100, 128, generator=g5).to(dev)   # 5 x 4 x 2 = 40 tiles: ragged chunks (40 % 8 == 0), K = PF slabs
-    assert torch.equal(wino.gemm_batched(V, U, algo=4), wino.gemm_batched(V, U, algo=5, workgroups=8))
-    V, U = torch.randn(3, 130, 256, generator=g5).to(dev), torch.randn(3, 64, 256, generator=g5).to(dev)    # 9 tiles over 8 chunks: one chunk holds two
-    assert torch.equal(wino.gemm_batched(V, U, algo=4), wino.gemm_batched(V, U, algo=5, workgroups=8))
-    assert torch.equal(wino.gemm_batched(V, U, algo=4), wino.gemm_batched(V, U, algo=5, workgroups=0))
     with pytest.raises(Exception):
         wino.gemm_batched(torch.randn(1, 64, 32).to(dev), torch.randn(1, 64, 32).to(dev), algo=4)     # C % 64 != 0: refused, not mangled
-    with pytest.raises(Exception):
-        wino.gemm_batched(V, U, algo=5, workgroups=12)                                                # not a multiple of 8
     # TN twin (Winograd-domain weight gradient): ragged row counts (a last slab of 6 rows, a split that gets fewer rows), ragged tiles
     for B, M, K, C in ((3, 70, 72, 64), (2, 300, 136, 68), (2, 1024, 64, 128), (1, 128, 64, 64)):
         V = torch.randn(B, M, C, generator=g).to(dev)
@@ -693,7 +681,6 @@ def _run_s2_dgrad(dev, cases):
         y.backward(dy)
         ref = x.grad
         prev, conv._S2_DGRAD_MIN_WGS = conv._S2_DGRAD_MIN_WGS, 1
-        prev32, conv._S2_DGRAD_C32 = conv._S2_DGRAD_C32, True
         try:
             dyd, wd = dy.contiguous(memory_format=CL).to(dev), w.contiguous(memory_format=CL).to(dev)
             got = conv.conv2d_dgrad(dyd, wd, (H, W), 2, 1)
@@ -702,17 +689,17 @@ def _run_s2_dgrad(dev, cases):
             base = carry.clone()
             out = conv.conv2d_dgrad(dyd, wd, (H, W), 2, 1, accum_into=carry)
         finally:
-            conv._S2_DGRAD_MIN_WGS, conv._S2_DGRAD_C32 = prev, prev32
+            conv._S2_DGRAD_MIN_WGS = prev
         tol = 2e-5 * max(float(ref.abs().max()), 1.0)
         assert (got.cpu() - ref).abs().max() <= tol, (N, C, H, W, K, float((got.cpu() - ref).abs().max()))
         assert torch.equal(got, again)
         assert out.data_ptr() == carry.data_ptr() and (out.cpu() - base.cpu() - ref).abs().max() <= tol
-        # and the generic kernel (the A/B partner) agrees
-        prev, conv._S2_DGRAD = conv._S2_DGRAD, False
+        # and the generic kernel (what a layer that s2_dgrad_eligible rejects runs) agrees
+        prev, conv.s2_dgrad_eligible = conv.s2_dgrad_eligible, lambda *a: False
         try:
             old = conv.conv2d_dgrad(dyd, wd, (H, W), 2, 1)
         finally:
-            conv._S2_DGRAD = prev
+            conv.s2_dgrad_eligible = prev
         assert (old.cpu() - got.cpu()).abs().max() <= tol
 
 

@@ -30,9 +30,13 @@ for N, C, H, K in ((4, 32, 256, 64), (4, 64, 128, 128), (4, 128, 64, 256), (4, 2
     w = (torch.randn(K, C, 3, 3, device="cuda") * 0.05).contiguous(memory_format=CL)
     fl = 2.0 * N * OH * OH * K * 9 * C
     res = {}
-    for name, flag, minw in (("fused", True, 1), ("generic", False, 1)):
-        conv._S2_DGRAD, conv._S2_DGRAD_MIN_WGS = flag, minw
-        us = timeit(lambda: conv.conv2d_dgrad(dy, w, (H, H), 2, 1))
-        res[name] = us
+    min_wgs, conv._S2_DGRAD_MIN_WGS = conv._S2_DGRAD_MIN_WGS, 1
+    eligible = conv.s2_dgrad_eligible
+    try:
+        res["fused"] = timeit(lambda: conv.conv2d_dgrad(dy, w, (H, H), 2, 1))
+        conv.s2_dgrad_eligible = lambda *a: False       # what a layer the fused form rejects runs
+        res["generic"] = timeit(lambda: conv.conv2d_dgrad(dy, w, (H, H), 2, 1))
+    finally:
+        conv._S2_DGRAD_MIN_WGS, conv.s2_dgrad_eligible = min_wgs, eligible
     print(f"3x3/s2 {C:3d}->{K:3d} dx {H}x{H}: fused {res['fused']:7.1f} us ({fl / res['fused'] / 1e6 / 157.3:.2f} of peak)   generic {res['generic']:7.1f} us "
           f"({fl / res['generic'] / 1e6 / 157.3:.2f})", flush=True)
