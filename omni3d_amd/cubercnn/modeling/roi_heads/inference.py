@@ -7,7 +7,7 @@ NMS kernels, the fused cube decode); the host reads back only the per-image dete
 import torch
 
 from ....d2.structures import Boxes, Instances
-from ....kernels import det, select
+from ....kernels import det
 
 @torch.no_grad()
 def roi_heads_inference(heads, images, feats, proposals, packed):
@@ -29,12 +29,8 @@ def roi_heads_inference_device(heads, feats, proposals, packed):
     pred = heads.box_predictor(heads.box_head(x)).contiguous()
     bp = heads.box_predictor
     topk = bp.test_topk_per_image
-    cap = min(det.DET_MAX_CANDIDATES, P * K)
-    scores, probs, boxes = det.det_scores(pred, rois, count, packed.image_hw, B, P, K, bp.box2box_weights, bp.test_score_thresh)
-    vals, idx = select.topk_rows(scores, cap)                      # stable descending order of the row-major (roi, class) list
-    nms_boxes, valid = det.det_nms_boxes(boxes, vals, idx, B, P * K, K, cap)
-    keep = select.nms_sorted(nms_boxes, bp.test_nms_thresh, None, valid)
-    dbox, dscore, dcls, droi, dcount = det.det_compact(keep, valid, vals, idx, boxes, B, P * K, K, cap, topk)
+    dbox, dscore, dcls, droi, dcount, probs = det.fast_rcnn_inference(pred, rois, count, packed.image_hw, B, P, K, bp.box2box_weights,
+                                                                      bp.test_score_thresh, bp.test_nms_thresh, topk)
     # ---- cube head on the fixed (B, topk) slots (roi_heads.py:353-357, 771-819); unused slots hold a dummy box
     dboxes, dcl = dbox.view(B * topk, 4), dcls.view(-1)
     dimg = heads._batch_index(B, topk, dboxes.device)

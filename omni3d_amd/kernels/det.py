@@ -7,6 +7,7 @@ import torch
 
 from .. import lib as _lib
 from . import detmode as _det
+from . import select as _select
 
 _P = ctypes.c_void_p
 
@@ -558,6 +559,20 @@ def det_compact(keep, valid, vals, idx, boxes, B, PK, K, cap, topk):
     L.call("omni_det_compact", _lib.ptr(keep), _lib.ptr(valid), _lib.ptr(vals), _lib.ptr(idx), _lib.ptr(boxes), B, PK, K, cap, topk,
            _lib.ptr(obox), _lib.ptr(oscore), _lib.ptr(ocls), _lib.ptr(oroi), _lib.ptr(ocount), _lib.stream_of(boxes))
     return obox, oscore, ocls, oroi, ocount
+
+
+def fast_rcnn_inference(pred, rois, count, image_hw, B, P, K, weights, score_thresh, nms_thresh, topk, cap=None):
+    """`fast_rcnn_inference` for the whole batch on fixed shapes: score / decode / clip / threshold, stable candidate sort, per-class
+    NMS as one problem per image, the `topk` best into fixed slots.  pred (B*P, ld) = [K+1 logits | 4K deltas | pad], rois (B*P, 4),
+    count (B) proposals per image, image_hw (B, 2).  cap: candidates per image that enter NMS (None: min(DET_MAX_CANDIDATES, P*K)).
+    -> (dbox (B, topk, 4), dscore, dcls, droi (B, topk), dcount (B), probs (B*P, K)); slots >= dcount hold box (0,0,1,1), 0, 0, 0."""
+    cap = min(DET_MAX_CANDIDATES, P * K) if cap is None else int(cap)
+    scores, probs, boxes = det_scores(pred, rois, count, image_hw, B, P, K, weights, score_thresh)
+    vals, idx = _select.topk_rows(scores, cap)                     # stable descending order of the row-major (roi, class) list
+    nms_boxes, valid = det_nms_boxes(boxes, vals, idx, B, P * K, K, cap)
+    keep = _select.nms_sorted(nms_boxes, nms_thresh, None, valid)
+    dbox, dscore, dcls, droi, dcount = det_compact(keep, valid, vals, idx, boxes, B, P * K, K, cap, topk)
+    return dbox, dscore, dcls, droi, dcount, probs
 
 
 def guard_pre(vec, n):
