@@ -711,6 +711,30 @@ int omni_eval_accumulate(const int* order, const int* cat_off, const int* rank, 
                          const int* max_dets, int K, int A, int M, int T, int R, int sumD, double* precision, double* recall,
                          double* scores, void* stream);
 
+/* Drawing predicted cuboids (csrc/render.hip).  The reference renders them with pytorch3d's mesh rasteriser and paints the edges
+ * with OpenCV; here every pixel casts its ray (through the pixel centre (x + 0.5, y + 0.5)) against the boxes themselves.
+ *
+ * omni_cuboid_depth -- `render_depth_map` / `estimate_visibility` (cubercnn/util/math_util.py:707-743; the rasteriser call
+ * `renderer(mesh)` at :719 and the per-box silhouette sums at :738-739).  box3d (N,6) [X,Y,Z,W,H,L] camera space, R (N,9), K (9),
+ * vertices / faces as get_cuboid_verts_faces; zplane > 0.  Per pixel: depth (H,W) camera z of the first surface point at depth >=
+ * zplane (the exit face when the entry lies in front of the plane), +inf without a hit; index (H,W) the box, -1 without a hit,
+ * equal depths go to the lower index; face (H,W) 0..5 = front, right, left, back, top, bottom (the face pairs of the triangle list).
+ * Per box: area (N) pixels whose ray hits the box at all at depth >= zplane, visible (N) pixels where it is the nearest hit (both
+ * zeroed here; integer atomics only: two runs are bit-identical). */
+int omni_cuboid_depth(const float* box3d, const float* R, const float* K, int N, int H, int W, float zplane, float* depth,
+                      int* index, int* face, int* area, int* visible, void* stream);
+/* The shaded overlay of `draw_scene_view` (cubercnn/vis/vis.py:278-282 and :382-384: `renderer(meshes_scene)` with PointLights at
+ * the origin + SoftPhongShader, math_util.py:823-826): for every pixel with index >= 0, image (3,H,W) uint8 = round(shaded * blend_weight
+ * + image * (1 - blend_weight)), shaded = 255 * color[index] (N,3 in [0,1]) * (0.5 + 0.3 * max(0, n . l)): n the outward normal of
+ * `face`, turned to the viewer when the exit face was hit, l the unit vector from the hit point to the light at the camera origin.
+ * No specular term.  Pixels without a hit are not touched.  0 <= blend_weight <= 1. */
+int omni_scene_compose(const int* index, const int* face, const float* R, const float* K, const float* color, int N, int H, int W,
+                       float blend_weight, unsigned char* image, void* stream);
+/* `cv2.line` of draw_3d_box_from_verts (vis.py:622-626) as a gather: seg (S,8) = [x0, y0, x1, y1, thickness, c0, c1, c2]; every pixel
+ * of image (3,H,W) uint8 whose centre lies within thickness / 2 of a segment takes (c0, c1, c2) (planes 0..2, rounded, clamped to
+ * 0..255) of the LAST such segment of the list; the others are not touched.  A segment of length zero draws a disc. */
+int omni_draw_segments(const float* seg, int S, unsigned char* image, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,9 +1,13 @@
 """The five geometry helpers of the reference's util/math_util.py that sit on the hot path
 (SURVEY.md 2.1 #9).  In the training / inference path they are fused into csrc/cube_head.hip; these
-entry points expose them with the reference's names and argument meaning."""
+entry points expose them with the reference's names and argument meaning.  The cuboid renderer (`mesh_cuboid`,
+`render_depth_map`, `estimate_visibility`) runs on csrc/render.hip."""
+import math
+
+import numpy as np
 import torch
 
-from ...kernels import det
+from ...kernels import det, render
 
 
 def get_cuboid_verts_faces(box3d=None, R=None):
@@ -83,3 +87,74 @@ def R_from_allocentric(K, R_view, u=None, v=None):
     M, valid = _viewing_rotation(Kt, ut, vt)
     R_view = np.asarray(R_view)
     return (M[0].numpy() @ R_view) if bool(valid[0]) else R_view
+
+
+def euler2mat(euler):
+    """math_util.py:86-105: rotation matrix R_z R_y R_x of the euler angles (x, y, z)"""
+    cx, sx, cy, sy, cz, sz = (math.cos(euler[0]), math.sin(euler[0]), math.cos(euler[1]), math.sin(euler[1]), math.cos(euler[2]),
+                              math.sin(euler[2]))
+    R_x = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    R_y = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    R_z = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return np.dot(R_z, np.dot(R_y, R_x))
+
+
+class CuboidMesh:
+    """What `mesh_cuboid` returns in place of a pytorch3d `Meshes` (which does not exist here): the cuboids themselves -- box3d (n,6)
+    [X,Y,Z,W,H,L], R (n,3,3), color (n,3) in [0,1] or None -- since csrc/render.hip casts rays against boxes, not triangles."""
+
+    def __init__(self, box3d, R, color=None):
+        self.box3d, self.R, self.color = box3d, R, color
+
+    def __len__(self):
+        return len(self.box3d)
+
+    def verts_padded(self):
+        """(n,8,3) vertices in the order of get_cuboid_verts_faces (math_util.py:116-219), on the host"""
+        b, dt = self.box3d, self.box3d.dtype
+        sx = torch.tensor([-1, 1, 1, -1, -1, 1, 1, -1], dtype=dt) * 0.5
+        sy = torch.tensor([-1, -1, 1, 1, -1, -1, 1, 1], dtype=dt) * 0.5
+        sz = torch.tensor([-1, -1, -1, -1, 1, 1, 1, 1], dtype=dt) * 0.5
+        local = torch.stack((b[:, 5:6] * sx, b[:, 4:5] * sy, b[:, 3:4] * sz), dim=1)
+        return (self.R @ local + b[:, :3, None]).transpose(1, 2)
+
+    def clone(self):
+        return CuboidMesh(self.box3d.clone(), self.R.clone(), None if self.color is None else self.color.clone())
+
+
+def mesh_cuboid(box3d=None, R=None, color=None):
+    """math_util.py:761-782.  box3d [X,Y,Z,W,H,L] or (n,6); R 3x3 or (n,3,3); color: 3 values in [0,1] or (n,3)."""
+    box3d = torch.as_tensor([0, 0, 0, 1, 1, 1] if box3d is None else box3d, dtype=torch.float32).reshape(-1, 6).cpu()
+    n = len(box3d)
+    R = torch.eye(3).repeat(n, 1, 1) if R is None else torch.as_tensor(R, dtype=torch.float32).reshape(n, 3, 3).cpu()
+    if color is not None:
+        color = torch.as_tensor(color, dtype=torch.float32).reshape(-1, 3).cpu().expand(n, 3).contiguous()
+    return CuboidMesh(box3d, R, color)
+
+
+def _cast(K, box3d, pose, width, height, device, zplane=0.05):
+    dev = render.default_device() if device is None else torch.device(device)
+    mesh = mesh_cuboid(box3d, pose)
+    K = torch.as_tensor(np.asarray(K, dtype=np.float32) if not isinstance(K, torch.Tensor) else K, dtype=torch.float32).reshape(9)
+    return mesh, dev, render.cuboid_depth(mesh.box3d.to(dev), mesh.R.to(dev), K.to(dev), height, width, zplane)
+
+
+def render_depth_map(K, box3d, pose, width, height, device=None):
+    """math_util.py:707-726 -> (silhouettes (N,H,W) bool, depth_map (H,W), depth_map_inds (H,W) int64).  Two departures from
+    pytorch3d's rasteriser, both of csrc/render.hip: a pixel is sampled at its centre (x + 0.5, y + 0.5), and depth is the true depth
+    of the ray / surface intersection (the reference sets perspective_correct=False and interpolates depth in screen space).  The
+    N silhouettes come from one single-box cast each; `estimate_visibility` does not need them.  Without a hit depth_map is +inf
+    and, since the reference takes `zbuf.min(dim=0)` of all-inf columns there, depth_map_inds is 0."""
+    mesh, dev, (depth, index, _, _, _) = _cast(K, box3d, pose, width, height, device)
+    sil = torch.zeros((len(mesh), height, width), dtype=torch.bool, device=dev)
+    Kd = torch.as_tensor(np.asarray(K, dtype=np.float32) if not isinstance(K, torch.Tensor) else K, dtype=torch.float32).reshape(9).to(dev)
+    for b in range(len(mesh)):
+        sil[b] = render.cuboid_depth(mesh.box3d[b:b + 1].to(dev), mesh.R[b:b + 1].to(dev), Kd, height, width)[1] >= 0
+    return sil, depth, index.clamp(min=0).long()
+
+
+def estimate_visibility(K, box3d, pose, width, height, device=None):
+    """math_util.py:728-743 -> [visible / area per box]: the share of a box's pixels where it is the nearest surface, read from the
+    counters of omni_cuboid_depth (no silhouette is materialised); nan where the box covers no pixel, as the reference's division."""
+    _, _, (_, _, _, area, visible) = _cast(K, box3d, pose, width, height, device)
+    return (visible / area).tolist()

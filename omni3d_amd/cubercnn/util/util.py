@@ -1,6 +1,8 @@
-"""The small host helpers tools/train_net.py reaches through `cubercnn.util` (:328-329, :363-369, :424)."""
+"""The small host helpers tools/train_net.py (:328-329, :363-369, :424) and demo/demo.py reach through `cubercnn.util`."""
 import json
 import os
+import shutil
+from glob import glob
 
 import numpy as np
 
@@ -19,6 +21,60 @@ def save_json(path, data):
 def load_json(path):
     with open(path, "r") as fp:
         return json.load(fp)
+
+
+def list_files(base_dir, file_pattern):
+    """util.py:102-109: the files of a directory that match a pattern, sorted alphabetically"""
+    return sorted(glob(os.path.join(base_dir) + file_pattern))
+
+
+def mkdir_if_missing(directory, delete_if_exist=False):
+    """util.py:121-127"""
+    if delete_if_exist and os.path.exists(directory):
+        shutil.rmtree(directory)
+    if not os.path.exists(directory):
+        os.makedirs(directory)
+
+
+def imread(path):
+    """util.py:64-65 (`cv2.imread`): HWC uint8 in BGR order, None when the file is not an image.  PIL stands in for OpenCV."""
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            rgb = np.asarray(im.convert("RGB"))
+    except (OSError, ValueError):
+        return None
+    return np.ascontiguousarray(rgb[:, :, ::-1])
+
+
+def imwrite(im, path):
+    """util.py:75-76 (`cv2.imwrite`): HWC BGR image (rounded and clipped to uint8), format from the file extension"""
+    from PIL import Image
+    im = np.asarray(im)
+    if im.dtype != np.uint8:
+        im = np.clip(np.rint(im), 0, 255).astype(np.uint8)
+    Image.fromarray(np.ascontiguousarray(im[:, :, ::-1])).save(path)
+
+
+# hues a golden-angle step apart at three lightness / saturation levels: neighbours in the table are far apart in colour
+def _make_colors(n=48):
+    import colorsys
+    table = []
+    for i in range(n):
+        h = (i * 0.61803398875) % 1.0
+        l, s = (0.50, 0.62, 0.40)[i % 3], (0.85, 0.70, 0.95)[(i // 3) % 3]
+        table.append([int(round(255 * c)) for c in colorsys.hls_to_rgb(h, l, s)])
+    return table
+
+
+_colors = _make_colors()
+
+
+def get_color(ind=None, hex=False):
+    """util.py:289-300: a colour (3 values 0..255) for index `ind` from a fixed table of this package's own; no random jitter, so
+    a drawing is reproducible (ind None: index 0)"""
+    color = list(_colors[(0 if ind is None else int(ind)) % len(_colors)])
+    return "#%02x%02x%02x" % tuple(color) if hex else color
 
 
 class CubeRCNNHandler:
