@@ -735,6 +735,28 @@ int omni_scene_compose(const int* index, const int* face, const float* R, const 
  * 0..255) of the LAST such segment of the list; the others are not touched.  A segment of length zero draws a disc. */
 int omni_draw_segments(const float* seg, int S, unsigned char* image, int H, int W, void* stream);
 
+/* The 3D error report of `visualize_from_instances` (cubercnn/vis/vis.py:95-171, csrc/vis_errors.hip) for a whole dataset in one
+ * call.  Rows are ragged by image: detections of image i are rows dt_off[i] .. dt_off[i + 1] - 1, ground truths gt_off[i] ..
+ * gt_off[i + 1] - 1 (both (I + 1) int32, non-decreasing, ending at D / G; not checked here).
+ *   detections   dt_box (D,4) XYWH, dt_cat (D) int32, dt_c2d (D,2) projected centre, dt_z (D), dt_dims (D,3) [w,h,l], dt_pose (D,9)
+ *   ground truth gt_box (G,4) XYWH, gt_cat (G) int32, gt_center (G,3) camera space, gt_dims (G,3), gt_pose (G,9)
+ *   K (I,9)      the intrinsics of every image, row-major
+ * A detection is matched to the ground truth of its image and category with the largest 2D IoU (plain XYXY intersection over union,
+ * no +1; 0 where the union is not positive; the lowest row among equal IoUs), valid at IoU >= 0.5.  Out:
+ *   match (D) int32   global ground-truth row or -1
+ *   err (D,7)         [xy, z, w, h, l, dim, ry] of the matched pair, NaN where match < 0: xy = |dt_c2d - (K gt_center / gt_center.z)[:2]|,
+ *                     z = |dt_z - gt_center.z|, w / h / l = |differences of the dimensions|, dim = their Euclidean norm, ry = pi / 2 -
+ *                     (trace(R_dt R_gt^T) - 1) / 2 (pytorch3d `so3_relative_angle(..., cos_bound=1)`), NaN and not counted when the trace
+ *                     lies outside [-1 - 1e-4, 3 + 1e-4] (pytorch3d raises there and the reference skips the pair for ry)
+ *   sums (7) double   the columns of err over the matched pairs (ry: over the pairs with a valid ry)
+ *   counts (2) int64  matched pairs, matched pairs with a valid ry
+ * workspace: I * 9 doubles (one row of partial sums per image, added in image order by a second launch: no floating-point atomics,
+ * two runs give the same bits).  I = 0 (then D = G = 0) writes zero sums and counts. */
+int omni_match_errors(const float* dt_box, const int* dt_cat, const float* dt_c2d, const float* dt_z, const float* dt_dims,
+                      const float* dt_pose, const int* dt_off, const float* gt_box, const int* gt_cat, const float* gt_center,
+                      const float* gt_dims, const float* gt_pose, const int* gt_off, const float* K, int I, int D, int G, int* match,
+                      float* err, double* sums, long long* counts, double* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,13 +47,14 @@ def imread(path):
     return np.ascontiguousarray(rgb[:, :, ::-1])
 
 
-def imwrite(im, path):
-    """util.py:75-76 (`cv2.imwrite`): HWC BGR image (rounded and clipped to uint8), format from the file extension"""
+def imwrite(im, path, **save_params):
+    """util.py:75-76 (`cv2.imwrite`): HWC BGR image (rounded and clipped to uint8), format from the file extension; `save_params`
+    go to PIL's encoder (e.g. quality=100, subsampling=0 for a JPEG that keeps thin lines)"""
     from PIL import Image
     im = np.asarray(im)
     if im.dtype != np.uint8:
         im = np.clip(np.rint(im), 0, 255).astype(np.uint8)
-    Image.fromarray(np.ascontiguousarray(im[:, :, ::-1])).save(path)
+    Image.fromarray(np.ascontiguousarray(im[:, :, ::-1])).save(path, **save_params)
 
 
 # hues a golden-angle step apart at three lightness / saturation levels: neighbours in the table are far apart in colour

@@ -2,14 +2,19 @@
 against the cuboids (`omni_cuboid_depth` + `omni_scene_compose`) instead of pytorch3d's mesh renderer, the box edges are thick
 segments painted by `omni_draw_segments` instead of `cv2.line`.  Images enter and leave as the reference's numpy HWC uint8 arrays;
 in between they live on the device as (3,H,W) tensors.  Labels are written last, on the host, with PIL's built-in bitmap font (a
-stated departure from OpenCV's Hershey font; not on the hot path)."""
+stated departure from OpenCV's Hershey font; not on the hot path).
+`visualize_from_instances` (vis.py:76-196), the last step of every evaluation: the per-dataset 3D error line from one launch of
+csrc/vis_errors.hip (`match_errors_from_instances`) and a drawing of every 50th image."""
+import os
 from copy import deepcopy
 
 import numpy as np
 import torch
 
-from ...kernels import render
+from ...d2.structures import BoxMode
+from ...kernels import render, viserr
 from ..util import math_util as MU
+from ..util import util as U
 
 # the twelve edges in the reference's drawing order (vis.py:593)
 BOX_EDGES = [[0, 1], [1, 2], [2, 3], [3, 0], [1, 5], [5, 6], [6, 2], [4, 5], [4, 7], [6, 7], [0, 4], [3, 7]]
@@ -54,10 +59,8 @@ def _paint(image, rows):
         render.draw_segments(image, torch.tensor(rows, dtype=torch.float32).to(image.device))
 
 
-def draw_3d_box_from_verts(im, K, verts3d, color=(0, 200, 200), thickness=1, zplane=0.05, eps=1e-4):
-    """vis.py:571-626: the edges of the box with vertices verts3d (8,3, camera space) onto `im`, in place.  im: numpy HWC uint8 (as in
-    the reference) or a (3,H,W) uint8 tensor already on the device.  The back / top face highlights are not drawn."""
-    rows = box_segments(K, verts3d, color, thickness, zplane, eps)
+def _draw_rows(im, rows):
+    """segment rows onto `im`, in place: numpy HWC uint8 (through the device and back) or a (3,H,W) uint8 tensor on the device"""
     if isinstance(im, torch.Tensor):
         _paint(im, rows)
         return im
@@ -65,6 +68,52 @@ def draw_3d_box_from_verts(im, K, verts3d, color=(0, 200, 200), thickness=1, zpl
     _paint(dev, rows)
     im[...] = _to_host(dev)
     return im
+
+
+def _cv_segment(v0, v1, color, thickness):
+    """one `cv2.line` call as a segment row: the end points are truncated to integers as cv2.line receives them; OpenCV's integer
+    (x, y) names a pixel, whose centre is (x + 0.5, y + 0.5) in the coordinates of omni_draw_segments"""
+    return [int(v0[0]) + 0.5, int(v0[1]) + 0.5, int(v1[0]) + 0.5, int(v1[1]) + 0.5, float(thickness), float(color[0]), float(color[1]),
+            float(color[2])]
+
+
+def draw_line(im, v0, v1, color=(0, 200, 200), thickness=1):
+    """vis.py:58-59: the line from v0 to v1 (x, y), end points truncated to integers, onto `im` in place"""
+    return _draw_rows(im, [_cv_segment(v0, v1, color, thickness)])
+
+
+def draw_2d_box(im, box, color=(0, 200, 200), thickness=1):
+    """vis.py:705-714 (`cv2.rectangle`): the outline of box [x, y, w, h] with corners (int(x), int(y)) and (int(x + w - 1),
+    int(y + h - 1)), four segments in one launch"""
+    x1, y1, x2, y2 = int(box[0]), int(box[1]), int((box[0] + box[2]) - 1), int((box[1] + box[3]) - 1)
+    corners = [(x1, y1), (x2, y1), (x2, y2), (x1, y2)]
+    return _draw_rows(im, [_cv_segment(corners[k], corners[(k + 1) % 4], color, thickness) for k in range(4)])
+
+
+def bev_corners(canvas_width, z3d, l3d, w3d, x3d, ry3d, scale=1):
+    """the four corners (4,2) of a box in the bird's-eye view of vis.py:26-50, with the reference's swap of w and l"""
+    w, l, x, z, r = l3d * scale, w3d * scale, x3d * scale, z3d * scale, ry3d * -1
+    corners1 = np.array([[-w / 2, -l / 2, 1], [+w / 2, -l / 2, 1], [+w / 2, +l / 2, 1], [-w / 2, +l / 2, 1]], dtype=np.float64)
+    ry = np.array([[+np.cos(r), -np.sin(r), 0], [+np.sin(r), np.cos(r), 0], [0, 0, 1]], dtype=np.float64)
+    corners2 = ry.dot(corners1.T).T
+    corners2[:, 0] += w / 2 + x + canvas_width / 2
+    corners2[:, 1] += l / 2 + z
+    return corners2[:, :2]
+
+
+def draw_bev(canvas_bev, z3d, l3d, w3d, x3d, ry3d, color=(0, 200, 200), scale=1, thickness=2):
+    """vis.py:26-55: the footprint of a box on a bird's-eye canvas (HWC uint8 or a device tensor), four segments in one launch.
+    -> the corners (4,2) that were joined (the reference returns nothing)"""
+    width = canvas_bev.shape[2] if isinstance(canvas_bev, torch.Tensor) else canvas_bev.shape[1]
+    c = bev_corners(width, z3d, l3d, w3d, x3d, ry3d, scale)
+    _draw_rows(canvas_bev, [_cv_segment(c[k], c[(k + 1) % 4], color, thickness) for k in range(4)])
+    return c
+
+
+def draw_3d_box_from_verts(im, K, verts3d, color=(0, 200, 200), thickness=1, zplane=0.05, eps=1e-4):
+    """vis.py:571-626: the edges of the box with vertices verts3d (8,3, camera space) onto `im`, in place.  im: numpy HWC uint8 (as in
+    the reference) or a (3,H,W) uint8 tensor already on the device.  The back / top face highlights are not drawn."""
+    return _draw_rows(im, box_segments(K, verts3d, color, thickness, zplane, eps))
 
 
 def draw_3d_box(im, K, box3d, R, color=(0, 200, 200), thickness=1, view_R=None, view_T=None):
@@ -237,3 +286,109 @@ def draw_scene_view(im, K, meshes, text=None, scale=1000, R=None, T=None, zoom_f
     if mode == "front_and_novel":
         return im_drawn_rgb, im_novel_view, canvas
     return im_novel_view, canvas
+
+
+# ---- visualize_from_instances (vis.py:76-196) -------------------------------------------------------------------------------------
+
+def _dataset_dicts(dataset):
+    """the raw dataset dicts: this package's test loader keeps them as a plain sequence, detectron2's MapDataset as `._dataset`"""
+    return getattr(dataset, "_dataset", dataset)
+
+
+def _pack_instances(detections, dicts):
+    """all prediction records and ground-truth annotations as the flat arrays of `viserr.match_errors`, ragged by image"""
+    dt_n = [len(o["instances"]) for o in detections]
+    gt_n = [len(dicts[i]["annotations"]) for i in range(len(detections))]
+    D, G, I = sum(dt_n), sum(gt_n), len(detections)
+    dt_f = np.zeros((D, 19), np.float32)                 # box 4, centre 2, z 1, dims 3, pose 9
+    gt_f = np.zeros((G, 19), np.float32)                 # box 4, centre 3, dims 3, pose 9
+    dt_cat, gt_cat = np.zeros(D, np.int32), np.zeros(G, np.int32)
+    K = np.zeros((I, 9), np.float32)
+    d = g = 0
+    for i, o in enumerate(detections):
+        K[i] = np.asarray(o["K"], np.float64).reshape(9)
+        for r in o["instances"]:
+            dt_f[d, 0:4], dt_f[d, 4:6], dt_f[d, 6] = r["bbox"], r["center_2D"], r["center_cam"][2]
+            dt_f[d, 7:10], dt_f[d, 10:19] = r["dimensions"], np.asarray(r["pose"], np.float64).reshape(9)
+            dt_cat[d] = r["category_id"]
+            d += 1
+        for a in dicts[i]["annotations"]:
+            mode = a.get("bbox_mode", BoxMode.XYWH_ABS)
+            gt_f[g, 0:4] = a["bbox"] if mode == BoxMode.XYWH_ABS else BoxMode.convert(list(a["bbox"]), mode, BoxMode.XYWH_ABS)
+            gt_f[g, 4:7], gt_f[g, 7:10], gt_f[g, 10:19] = a["center_cam"], a["dimensions"], np.asarray(a["pose"], np.float64).reshape(9)
+            gt_cat[g] = a["category_id"]
+            g += 1
+    off = lambda n: np.concatenate(([0], np.cumsum(n, dtype=np.int64))).astype(np.int32)      # noqa: E731
+    c = np.ascontiguousarray
+    return (c(dt_f[:, 0:4]), dt_cat, c(dt_f[:, 4:6]), c(dt_f[:, 6]), c(dt_f[:, 7:10]), c(dt_f[:, 10:19]), off(dt_n),
+            c(gt_f[:, 0:4]), gt_cat, c(gt_f[:, 4:7]), c(gt_f[:, 7:10]), c(gt_f[:, 10:19]), off(gt_n), K)
+
+
+def match_errors_from_instances(detections, dataset):
+    """The numbers behind the error line of `visualize_from_instances`: `detections` is the list `inference_on_dataset` returns (and
+    `instances_predictions.pth` stores), `dataset` the test loader's dataset in the same order (a sequence of dataset dicts, or an
+    object exposing them as `._dataset`).  Every record is packed once on the host, copied once, and matched in one launch of
+    csrc/vis_errors.hip (`kernels.viserr.match_errors`, which defines the match and the seven errors).
+    -> {"match" (D,) int32 global ground-truth row or -1, "err" (D,7) float32 [xy, z, w, h, l, dim, ry] (NaN where unmatched),
+    "dt_off" / "gt_off" (I+1,) int32 (rows of image i), "counts" (matched pairs, pairs with a valid ry), "means" {name: float}} --
+    host tensors; a mean over no pair is nan."""
+    dicts = _dataset_dicts(dataset)
+    packed = [torch.from_numpy(a) for a in _pack_instances(detections, dicts)]
+    dev = render.default_device()
+    match, err, sums, counts = viserr.match_errors(*[t.to(dev) for t in packed])
+    sums, counts = sums.cpu().tolist(), counts.cpu().tolist()
+    means = {n: (sums[k] / counts[1 if n == "ry" else 0] if counts[1 if n == "ry" else 0] else float("nan"))
+             for k, n in enumerate(viserr.ERR_NAMES)}
+    return {"match": match.cpu(), "err": err.cpu(), "dt_off": packed[6], "gt_off": packed[12], "counts": tuple(counts), "means": means}
+
+
+def _draw_sample(im, K, records, names, thres):
+    """the predictions above `thres` onto `im` (numpy HWC uint8, in place): the edges of all boxes in one launch, then the labels"""
+    H = im.shape[0]
+    thickness = max(1, int(np.round(3 * H / 500)))
+    K_inv = np.linalg.inv(K)
+    rows, labels = [], []
+    for r in records:
+        if not r["score"] > thres:
+            continue
+        z = r["center_cam"][2]
+        x3d, y3d, z3d = K_inv @ (z * np.array(list(r["center_2D"]) + [1.0]))
+        w3d, h3d, l3d = r["dimensions"]
+        color = U.get_color(r["category_id"])
+        verts = MU.mesh_cuboid([x3d, y3d, z3d, w3d, h3d, l3d], np.asarray(r["pose"], np.float64)).verts_padded()[0].double().numpy()
+        rows += box_segments(K, verts, color, thickness)
+        labels.append(("{}, z={:.1f}, s={:.2f}".format(names[r["category_id"]], z3d, r["score"]), r["bbox"], color))
+    _draw_rows(im, rows)
+    for text, pos, color in labels:
+        draw_text(im, text, pos, scale=0.50 * H / 500, bg_color=color)
+    return im
+
+
+def visualize_from_instances(detections, dataset, dataset_name, min_size_test, output_folder, category_names_official, iteration=""):
+    """vis.py:76-196, called once per test dataset at the end of every evaluation (tools/train_net.py:99-107).
+    1. The log line `<dataset_name>iter=<iteration>, xy(..), z(..), whl(.., .., ..), ry(..)`: the mean errors, in pixels / metres /
+       radians, of the predictions matched to a same-category ground-truth box by 2D IoU >= 0.5 (`match_errors_from_instances`).  A
+       mean over no pair prints nan, ry without a valid pair prints 1000.00, as in the reference.
+    2. Every 50th image that has ground truth is written to `<output_folder>/vis/%06d.jpg` with its predictions scoring above
+       sqrt(1 / n_categories): the 3D box (`omni_draw_segments`, colour `util.get_color(category_id)`) and the label
+       "<category>, z=.., s=..".  The image is read from `file_name`, or taken from `image_array` where the dataset carries pixels.
+    Departures: lines are at least 1 px thick (the reference's int(round(3 H / 500)) is 0 below 84 rows, which cv2.line rejects);
+    labels are written after all boxes of the image; the JPEG is written at quality 100 without chroma subsampling (the default
+    encoder settings smear a one-pixel line over its 16 x 16 block: up to 110 grey levels two pixels away, 4 with these settings);
+    `min_size_test` is accepted and, as in the reference, not used."""
+    vis_folder = os.path.join(output_folder, "vis")
+    U.mkdir_if_missing(vis_folder)
+    dicts = _dataset_dicts(dataset)
+    means = match_errors_from_instances(detections, dataset)["means"]
+    thres = np.sqrt(1 / len(category_names_official))
+    for imind in range(0, len(detections), 50):
+        o, entry = detections[imind], dicts[imind]
+        if len(entry["annotations"]) == 0:
+            continue
+        assert entry["image_id"] == o["image_id"]
+        im = np.array(entry["image_array"], dtype=np.uint8) if "image_array" in entry else U.imread(entry["file_name"])
+        _draw_sample(im, np.asarray(o["K"], np.float64).reshape(3, 3), o["instances"], category_names_official, thres)
+        U.imwrite(im, os.path.join(vis_folder, "{:06d}.jpg".format(imind)), quality=100, subsampling=0)
+    ry = means["ry"] if means["ry"] == means["ry"] else 1000.0
+    return dataset_name + "iter={}, xy({:.2f}), z({:.2f}), whl({:.2f}, {:.2f}, {:.2f}), ry({:.2f})\n".format(
+        iteration, means["xy"], means["z"], means["w"], means["h"], means["l"], ry)
