@@ -757,6 +757,37 @@ int omni_match_errors(const float* dt_box, const int* dt_cat, const float* dt_c2
                       const float* gt_dims, const float* gt_pose, const int* gt_off, const float* K, int I, int D, int G, int* match,
                       float* err, double* sums, long long* counts, double* workspace, void* stream);
 
+/* Deriving the box fields of Omni3D annotations (csrc/annotate.hip) for a whole dataset in two calls.  Rows are ragged by image as
+ * above: the boxes of image i are rows box_off[i] .. box_off[i + 1] - 1 (box_off (I + 1) int32, starting at 0, non-decreasing, ending
+ * at N; not checked here).  box3d (N,6) [X,Y,Z,W,H,L] camera space, R (N,9), K (I,9) row-major, size (I,2) int32 [W, H].
+ *
+ * omni_box_annotate -- `get_cuboid_verts` (cubercnn/util/math_util.py:221-259), `convert_3d_box_to_2d` (:498-577, the projection at
+ * :537, the behind test at :540-541, the corner substitution at :543-555, the box at :557-570) and `estimate_truncation` (:745-758)
+ * for all N boxes, one thread per box.  Out:
+ *   verts3d (N,8,3)       the vertices R v + centre in the order of get_cuboid_verts_faces (`bbox3D_cam`)
+ *   verts2d (N,8,3)       [u, v, z] = [(K p).x / (K p).z, (K p).y / (K p).z, (K p).z] of every vertex p, before any substitution
+ *   behind, fully_behind  (N) uint8: any / all of the vertices have z <= min_z (the reference's default min_z is 0.20)
+ *   proj (N,4) XYXY       min and max of the eight points, where a vertex with z <= min_z is replaced by the image corner that the
+ *                         signs of its camera-space x and y select (0 or W - 1, 0 or H - 1); the signs are compared strictly, so such a
+ *                         vertex with x or y exactly 0 keeps its own projection, as in the reference.  A NaN stays (torch.min / max).
+ *   truncation (N) double 1 when fully_behind, otherwise 1 - area(proj ^ [0, 0, W - 1, H - 1]) / area(proj), evaluated in float64 from
+ *                         the float32 proj (the reference: numpy on the .tolist() values); NaN for a proj of zero area (0 / 0)
+ *   trunc (N,4) XYXY      `bbox2D_trunc`, for which the reference has no code (only its annotation files carry the field).  Defined
+ *                         here: proj intersected with [0, W - 1] x [0, H - 1]; [-1, -1, -1, -1] when the box is fully_behind or the
+ *                         intersection has no area (x2 <= x1 or y2 <= y1, or proj holds a NaN).
+ * No LDS, no atomics: two runs give the same bits.  N = 0 launches nothing. */
+int omni_box_annotate(const float* box3d, const float* R, const int* box_off, const float* K, const int* size, int I, int N,
+                      float min_z, float* verts3d, float* verts2d, float* proj, float* trunc, double* truncation,
+                      unsigned char* behind, unsigned char* fully_behind, void* stream);
+/* omni_visibility_ragged -- the counters of `estimate_visibility` (math_util.py:728-743: `silhouettes[annidx].sum()` at :738 and the
+ * nearest-surface count at :739) for every box of every image: area (N) and visible (N) int32 are exactly the `area` / `visible` of
+ * omni_cuboid_depth called once per image on the boxes of that image (same pixel centres, same zplane rule, equal depths to the
+ * lower row; occlusion is judged among the boxes of the same image only), without any depth, index or face map.  One workgroup per
+ * 16 x 16 tile of the concatenated tile list: tile_off (I + 1) int32 is the prefix sum of ceil(W / 16) * ceil(H / 16) over the
+ * images (W, H > 0), tiles = tile_off[I].  Both outputs are zeroed here; integer atomics only: two runs give the same bits. */
+int omni_visibility_ragged(const float* box3d, const float* R, const int* box_off, const float* K, const int* size,
+                           const int* tile_off, int I, int N, int tiles, float zplane, int* area, int* visible, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,73 +13,14 @@
 // camera-space z of the true ray / surface intersection (the reference interpolates z in screen space, perspective_correct =
 // False); segment end points are kept at sub-pixel precision.
 #include <device_rt.h>
+#include "cuboid_cast.h"      // TILE, CHUNK, REC, pixel_ray, clamp_to_int, slab, stage_box, cast_box
 
 namespace {
-
-constexpr int TILE = 16;       // pixels per tile edge: 256 threads = 4 waves of 4 rows x 16 columns
-constexpr int CHUNK = 64;      // boxes / segments staged in LDS at a time
-constexpr int REC = 16;        // floats per box record: R^T (9), ray origin in the box frame (3), half extents (3), pad
-
-// direction (dx, dy, 1) of the ray through the centre of pixel (x, y): K (dx, dy, 1)^T = (x + 0.5, y + 0.5, 1)^T
-__device__ __forceinline__ void pixel_ray(const float* __restrict__ K, int x, int y, float& dx, float& dy) {
-    dy = ((float)y + 0.5f - K[5]) / K[4];
-    dx = ((float)x + 0.5f - K[2] - K[1] * dy) / K[0];
-}
-
-// clamps before the conversion: a projection may be anything, +-inf included
-__device__ __forceinline__ int clamp_to_int(float v, int lo, int hi) {
-    return (int)fminf(fmaxf(v, (float)lo), (float)hi);
-}
-
-// one slab of the ray / box test: the ray o + t * l against |coordinate| <= h.  Narrows [tn, tf] and remembers which axis
-// bounds it; a ray parallel to the slab either misses the box or leaves the interval as it is.
-__device__ __forceinline__ bool slab(float o, float l, float h, int axis, float& tn, float& tf, int& an, int& af) {
-    if (l == 0.0f) return fabsf(o) <= h;
-    const float inv = 1.0f / l;
-    const float ta = (-h - o) * inv, tb = (h - o) * inv;
-    const float lo = fminf(ta, tb), hi = fmaxf(ta, tb);
-    if (lo > tn) { tn = lo; an = axis; }
-    if (hi < tf) { tf = hi; af = axis; }
-    return true;
-}
 
 // face number (get_cuboid_verts_faces: 0 front -w/2, 1 right +l/2, 2 left -l/2, 3 back +w/2, 4 top -h/2, 5 bottom +h/2) of
 // the side of box-frame axis `axis` (0: length, 1: height, 2: width) at the negative / positive end
 __device__ __forceinline__ int face_of(int axis, bool positive) {
     return axis == 0 ? (positive ? 1 : 2) : (axis == 1 ? (positive ? 5 : 4) : (positive ? 3 : 0));
-}
-
-// box record `rec` + whether the box can touch the tile [tx0, tx1] x [ty0, ty1] (rectangle of the projected corners, one pixel
-// of slack; the whole view when a corner is in front of the near plane; nothing when all of them are)
-__device__ __forceinline__ int stage_box(const float* __restrict__ b, const float* __restrict__ r, const float* __restrict__ K,
-                                         float zplane, int W, int H, int tx0, int ty0, int tx1, int ty1, float* rec) {
-    const float cx = b[0], cy = b[1], cz = b[2];
-    const float hx = 0.5f * b[5], hy = 0.5f * b[4], hz = 0.5f * b[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float r0 = r[a], r1 = r[3 + a], r2 = r[6 + a];            // column a of R = box axis a in camera space
-        rec[3 * a] = r0; rec[3 * a + 1] = r1; rec[3 * a + 2] = r2;
-        rec[9 + a] = -(r0 * cx + r1 * cy + r2 * cz);                    // the camera centre in the box frame
-    }
-    rec[12] = hx; rec[13] = hy; rec[14] = hz; rec[15] = 0.0f;
-    float zmin = __int_as_float(0x7f800000), zmax = -zmin, umin = zmin, umax = -zmin, vmin = zmin, vmax = -zmin;
-    const float znear = fmaxf(zplane, 1e-4f);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float sx = (k & 1) ? hx : -hx, sy = (k & 2) ? hy : -hy, sz = (k & 4) ? hz : -hz;
-        const float px = cx + r[0] * sx + r[1] * sy + r[2] * sz;
-        const float py = cy + r[3] * sx + r[4] * sy + r[5] * sz;
-        const float pz = cz + r[6] * sx + r[7] * sy + r[8] * sz;
-        zmin = fminf(zmin, pz); zmax = fmaxf(zmax, pz);
-        const float iz = 1.0f / fmaxf(pz, znear);
-        const float u = (K[0] * px + K[1] * py) * iz + K[2], v = K[4] * py * iz + K[5];
-        umin = fminf(umin, u); umax = fmaxf(umax, u); vmin = fminf(vmin, v); vmax = fmaxf(vmax, v);
-    }
-    if (!(zmax >= zplane)) return 0;                 // wholly in front of the near plane (or not a number): covers nothing
-    if (zmin < znear) return 1;                      // straddles the near plane / holds the camera: any pixel may see it
-    const int x0 = clamp_to_int(floorf(umin) - 1.0f, -1, W), x1 = clamp_to_int(ceilf(umax) + 1.0f, -1, W);
-    const int y0 = clamp_to_int(floorf(vmin) - 1.0f, -1, H), y1 = clamp_to_int(ceilf(vmax) + 1.0f, -1, H);
-    return x0 <= tx1 && x1 >= tx0 && y0 <= ty1 && y1 >= ty0;
 }
 
 __global__ void __launch_bounds__(256) cuboid_depth_kernel(const float* __restrict__ box3d, const float* __restrict__ R,
@@ -108,20 +49,11 @@ __global__ void __launch_bounds__(256) cuboid_depth_kernel(const float* __restri
         __syncthreads();
         for (int j = 0; j < n; ++j) {
             if (!s_on[j]) continue;                  // the same decision in every thread of the workgroup
-            const float* r = s_rec + j * REC;
-            const float lx = r[0] * dx + r[1] * dy + r[2], ly = r[3] * dx + r[4] * dy + r[5], lz = r[6] * dx + r[7] * dy + r[8];
-            float tn = -inf, tf = inf;
-            int an = 0, af = 0;
-            bool ok = slab(r[9], lx, r[12], 0, tn, tf, an, af);
-            ok = slab(r[10], ly, r[13], 1, tn, tf, an, af) && ok;
-            ok = slab(r[11], lz, r[14], 2, tn, tf, an, af) && ok;
-            // d_z = 1: the ray parameter IS the camera depth.  First surface point at or behind the near plane: the entry, or the
-            // exit when the entry lies in front of the plane (camera inside the box, box across the plane)
-            const bool entry = tn >= zplane;
-            const bool hit = inside && ok && tn <= tf && tf >= zplane;
-            const float th = entry ? tn : tf;
-            const int ax = entry ? an : af;
-            const float la = ax == 0 ? lx : (ax == 1 ? ly : lz);
+            // first surface point at or behind the near plane: the entry, or the exit when the entry lies in front of the plane
+            float th, la;
+            int ax;
+            bool entry;
+            const bool hit = cast_box(s_rec + j * REC, dx, dy, zplane, th, ax, la, entry) && inside;
             const unsigned long long m = __ballot(hit);
             if (lane == 0 && m) atomicAdd(&s_cnt[j], (int)__popcll(m));
             if (hit && th < best) {                  // boxes come in index order: equal depths stay with the lower index
