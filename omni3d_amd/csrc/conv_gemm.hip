@@ -13,17 +13,22 @@
 //     1x1 case with H=W=1.
 //   * v_mfma_f32_32x32x2_f32 (exact fp32 = fmaf chain, 157 TFLOP/s peak): the parity bar is fp32
 //     1e-4 against the reference's fp32 CPU path, so no reduced-precision operands.
-//   * 256-thread workgroup = 4 waves; block tile BM x BN x 16, each wave owns WM x WN 32x32
-//     accumulators (<= 64 VGPRs); operands staged through double-buffered LDS with the next
-//     tile's global loads (16 B / lane, coalesced along C) in flight during the MFMA phase;
-//     one barrier per k-step.
+//   * 256-thread workgroup = 4 waves; block tile BM x BN x BK with slab depth BK = 32 (16 for the
+//     256x32 tile of the few-channel layers), each wave owns WM x WN 32x32 accumulators
+//     (<= 64 VGPRs); operands staged through double-buffered LDS with the next slab's global loads
+//     (16 B / lane, coalesced along C) in flight during the MFMA phase -- two slabs ahead in the
+//     deep-prefetch gradient kernels, up to four in the batched GEMMs; one barrier per slab.
 //   * each lane fetches FOUR consecutive k values with one ds_read_b128 and feeds them to four
 //     MFMAs: lane half h supplies k = 8*kc + 4*h + t to MFMA t, identically for A and B, which
-//     keeps both fragments a single 16-byte LDS read (row pitch 20 floats = conflict-free).
-//   * blockIdx -> tile mapping walks M fastest inside an XCD-sized chunk so the 8 private L2s
-//     each see a contiguous band of output rows (weights are tiny and shared).
-//   * weight gradient: reduction over output pixels split across grid.z, partial tiles are
-//     accumulated with fp32 atomics into a zero-initialised dW.
+//     keeps both fragments a single 16-byte LDS read (row pitch BK + 4 floats = conflict-free).
+//   * blockIdx -> tile mapping walks one contiguous chunk of the tile sequence per XCD, so the 8
+//     private L2s each see a band of output rows (weights are tiny and shared).
+//   * a deep reduction over few tiles is split over gridDim.y (forward / data gradient: over
+//     (r,s,c) slabs; weight gradient: over output pixels).  Default: the partial tiles meet in a
+//     workspace and the tile's last-arriving workgroup adds them in split order (split_reduce.h:
+//     run-to-run identical bits); fp32 atomics into a zero-filled output only in the
+//     non-deterministic entry points (no counters given).
+//   * the host section at the end of the file holds every launch decision: tile, split, workspace plan.
 #include <device_rt.h>
 #include "split_reduce.h"
 
@@ -1222,16 +1227,7 @@ inline bool bad_geom(const ConvP& p) {
 
 extern "C" {
 
-// out[N,OH,OW,K] = conv(x[N,H,W,C], w[K,R,S,C]) + bias, optional ReLU.  Pitches in floats.
-//
-// Tile choice: 128x128 when that already fills the 256 CUs, otherwise 64x64 (4x the workgroups); when even
-// that leaves CUs idle and the reduction is deep (DLA level 4/5, FC heads with few rows) the reduction is
-// split over gridDim.y with an atomic epilogue into a zeroed output.  Slab depth 32 (one barrier per 64
-// MFMAs per wave) measured +23 % over 16 on the 3x3 256->256 @128x128 shape (96 -> 119 TFLOP/s).
-// `tile` / `splits` select the algorithm explicitly (0 = the launcher's own choice, which is what omni_conv2d_fwd uses):
-//   tile 1 = 128x128, 2 = 64x64, 3 = 128x64, 4 = 256x32 (BM x BN output-pixel x output-channel tile); splits >= 1 = number of
-//   reduction splits (atomic epilogue into a zeroed output when > 1; needs ldo == K).  Used by tools/bench_kernels.py for A/B
-//   measurements and by tests that want a given tile on a small problem.
+// ---- host side: every launcher below is  check -> fill ConvP -> choose {tile, splits} -> det_prologue -> dispatch ----
 
 // Deterministic-mode plumbing shared by the launchers below (split_reduce.h).  `ctr` != nullptr asks for run-to-run identical
 // results; `plan` != nullptr makes the launcher report what it WOULD launch -- plan[0] = tile, [1] = reduction splits, [2] = arrival
@@ -1244,6 +1240,7 @@ struct DetArgs {
     int n_ctr;
     long long* plan;
 };
+constexpr DetArgs NO_DET{};      // the non-deterministic entry points: no workspace, no counters, no plan
 static inline bool det_fits(const DetArgs& d, long tiles, long splits, long tile_elems) {
     return d.ctr != nullptr && d.ws != nullptr && d.n_ctr >= omni_split_counters(tiles, splits) &&
            d.ws_floats >= omni_split_ws_floats(tiles, splits, tile_elems);
@@ -1253,48 +1250,148 @@ static inline void det_plan(const DetArgs& d, long tile, long tiles, long splits
     d.plan[2] = splits > 1 ? omni_split_counters(tiles, splits) : 0;
     d.plan[3] = splits > 1 ? omni_split_ws_floats(tiles, splits, tile_elems) : 0;
 }
+// What stands between a launcher's {tile, splits} decision and its launch.  step: DET_PLANNED = the plan is reported, DET_REFUSED =
+// an ordered split without the workspace / counters its plan asks for (both are the status to return), DET_LAUNCH = go on with
+// ws / ctr (null unless attached) in the kernel's parameters.  `ordered`: the split partials meet in the workspace and are summed
+// in split order; a split that is neither ordered nor accumulating meets through atomics in `out`, zero-filled here.
+// attach_unsplit (the weight gradient): ctr != nullptr is attached even to a launch that is not split, where it selects the plain
+// read-modify-write epilogue of an accumulating launch.
+enum { DET_LAUNCH = -1, DET_PLANNED = OMNI_OK, DET_REFUSED = OMNI_ERR_ARG };
+struct DetLaunch { int step; bool ordered; float* ws; unsigned* ctr; };
+static DetLaunch det_prologue(const DetArgs& d, long tile_id, long tiles, long splits, long tile_elems, void* out, size_t out_bytes,
+                              bool accumulating, hipStream_t st, bool attach_unsplit = false) {
+    if (d.plan != nullptr) {
+        det_plan(d, tile_id, tiles, splits, tile_elems);
+        return {DET_PLANNED, false, nullptr, nullptr};
+    }
+    const bool ordered = d.ctr != nullptr && splits > 1;
+    if (ordered && !det_fits(d, tiles, splits, tile_elems)) return {DET_REFUSED, false, nullptr, nullptr};
+    const bool attach = ordered || (attach_unsplit && d.ctr != nullptr);
+    if (splits > 1 && !accumulating && !ordered) omni_memset_async(out, 0, out_bytes, st);
+    return {DET_LAUNCH, ordered, attach ? d.ws : nullptr, attach ? d.ctr : nullptr};
+}
 
+// The kernels address their operands through buffer resources with 32-bit BYTE offsets (OMNI_OOB = 0x80000000 marks a lane as out of
+// range): an fp32 operand of `elems` elements is within reach below 2 GiB; one that is not would wrap into the resource and read
+// wrong data silently, so it is refused or sent to a kernel with 64-bit addressing.  headroom: the byte cursors of the
+// deep-prefetch gradients run up to PF slabs past the last pixel before their loads are masked -- they keep PF_HEADROOM free.
+constexpr long PF_HEADROOM = 1L << 24;
+static inline bool fits_i32(long elems, long headroom = 0) { return elems * 4 < (1L << 31) - headroom; }
+
+// tile id of the forward and data-gradient launchers -> BM x BN (output pixels x output channels): 1 = 128x128, 2 = 64x64,
+// 3 = 128x64, 4 = 256x32
+static inline void tile_dims(int tile, int& bm, int& bn) {
+    bm = tile == 1 ? 128 : tile == 2 ? 64 : tile == 3 ? 128 : 256;
+    bn = tile == 1 ? 128 : tile == 2 ? 64 : tile == 3 ? 64 : 32;
+}
+
+// Row split of a reduction over `rows` (output pixels, GEMM rows): aim at `target` workgroups from `work` (tiles x batch) of them
+// per split, at least `min_rows` per split; the rows per split are rounded up to `unit` (a whole number of slabs) and the split count follows
+struct RowSplit { long splits; int rows; };
+static inline RowSplit split_rows(long target, long work, long rows, long min_rows, int unit) {
+    long splits = (target + work - 1) / work;
+    const long max_splits = (rows + min_rows - 1) / min_rows;
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    int per = (int)((rows + splits - 1) / splits);
+    per = (per + unit - 1) / unit * unit;
+    return {(rows + per - 1) / per, per};
+}
+
+// ConvP is filled here and nowhere else: value-initialised (stats / ws / ctr null, no sources and xs / coff zeroed, batch strides 0),
+// then every field a role uses assigned by name.  `splits` stays 1: the kernels take the split count from gridDim.y.
+static ConvP convp_geom(const float* x, const float* w, float* out, int N, int H, int W, int C, int K, int R, int S, int stride, int pad) {
+    ConvP p{};
+    p.x = x; p.w = w; p.out = out;
+    p.N = N; p.H = H; p.W = W; p.C = C;
+    p.OH = (H + 2 * pad - R) / stride + 1; p.OW = (W + 2 * pad - S) / stride + 1; p.K = K;
+    p.R = R; p.S = S; p.stride = stride; p.pad = pad;
+    p.splits = 1;
+    return p;
+}
+static ConvP convp_fwd(const float* x, const float* w, const float* bias, float* out, int N, int H, int W, int C, int K, int R, int S,
+                       int stride, int pad, int ldx, int ldo, int relu) {
+    ConvP p = convp_geom(x, w, out, N, H, W, C, K, R, S, stride, pad);
+    p.bias = bias; p.ldx = ldx; p.ldo = ldo; p.relu = relu;
+    return p;
+}
+static ConvP convp_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
+                         int lddy, int lddx, int accumulate) {
+    ConvP p = convp_geom(dy, w, dx, N, H, W, C, K, R, S, stride, pad);
+    p.ldx = lddy; p.ldo = lddx; p.accumulate = accumulate;
+    return p;
+}
+static ConvP convp_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
+                         int ldx, int lddy, int accumulate) {
+    ConvP p = convp_geom(x, dy, dw, N, H, W, C, K, R, S, stride, pad);
+    p.ldx = ldx; p.accumulate = accumulate;
+    p.ldw = lddy;      // the weight-gradient kernels read dY's pitch from `ldw`, and their XCD-order flag from `relu` (set once the split is known)
+    return p;
+}
+// one dense problem per gridDim.z: forward out[b] (M x K) = x[b] (M x C) w[b] (K x C)^T, or weight gradient out[b] (K x C) = w[b] (M x K)^T x[b]
+static ConvP convp_batched(const float* x, const float* w, float* out, int M, int C, int K, bool wgrad) {
+    ConvP p = convp_geom(x, w, out, M, 1, 1, C, K, 1, 1, 1, 0);
+    p.ldx = C; p.xb = (long)M * C;
+    if (wgrad) { p.ldw = K; p.wb = (long)M * K; p.ob = (long)K * C; }
+    else { p.ldo = K; p.wb = (long)K * C; p.ob = (long)M * K; }
+    return p;
+}
+
+// Multi-source input (the DLA Root): x is the channel concatenation of the dense NHWC tensors ms.xs[], 1 x 1 / stride 1; every
+// width a multiple of `width_unit` (32 = the forward kernel's slab depth, so a slab has one source; 4 = the weight gradient's
+// 16-byte loads); check_reach: every source within 32-bit byte offsets (the forward kernel's buffer resources)
 struct MultiSrc {
     const void* const* xs;    // nsrc dense NHWC tensors (N, H, W, cs[s])
     const int* cs;
     int nsrc;
 };
+static int attach_sources(ConvP& p, const MultiSrc& ms, int width_unit, bool check_reach) {
+    if (ms.nsrc < 1 || ms.nsrc > OMNI_MAX_SRC || p.R != 1 || p.S != 1 || p.stride != 1 || p.pad != 0) return OMNI_ERR_ARG;
+    p.coff[0] = 0;
+    for (int q = 0; q < OMNI_MAX_SRC; ++q) {
+        const bool live = q < ms.nsrc;
+        if (live && (ms.xs[q] == nullptr || ms.cs[q] <= 0 || (ms.cs[q] % width_unit) != 0)) return OMNI_ERR_ARG;
+        p.xs[q] = live ? (const float*)ms.xs[q] : nullptr;
+        p.coff[q + 1] = p.coff[q] + (live ? ms.cs[q] : 0);
+        if (live && check_reach && !fits_i32((long)p.N * p.H * p.W * ms.cs[q])) return OMNI_ERR_ARG;
+    }
+    if (p.coff[ms.nsrc] != p.C || p.ldx != p.C) return OMNI_ERR_ARG;
+    p.nsrc = ms.nsrc;
+    p.x = p.xs[0];
+    return OMNI_OK;
+}
+// the entry points' side of it: null / count checks and the summed width
+static int sources_width(const void* const* xs, const int* cs, int nsrc) {
+    if (xs == nullptr || cs == nullptr || nsrc < 1 || nsrc > OMNI_MAX_SRC) return 0;
+    long C = 0;
+    for (int q = 0; q < nsrc; ++q) C += cs[q] > 0 ? cs[q] : 0;
+    return (C <= 0 || C > (1 << 20)) ? 0 : (int)C;
+}
 
+// out[N,OH,OW,K] = conv(x[N,H,W,C], w[K,R,S,C]) + bias, optional ReLU.  Pitches in floats.
+//
+// Tile choice: 128x128 when that already fills the 256 CUs, otherwise 64x64 (4x the workgroups); when even
+// that leaves CUs idle and the reduction is deep (DLA level 4/5, FC heads with few rows) the reduction is
+// split over gridDim.y with an atomic epilogue into a zeroed output.  Slab depth 32 (one barrier per 64
+// MFMAs per wave) measured +23 % over 16 on the 3x3 256->256 @128x128 shape (96 -> 119 TFLOP/s).
+// `tile` / `splits` select the algorithm explicitly (0 = the launcher's own choice, which is what omni_conv2d_fwd uses):
+//   tile 1 = 128x128, 2 = 64x64, 3 = 128x64, 4 = 256x32 (BM x BN output-pixel x output-channel tile); splits >= 1 = number of
+//   reduction splits (atomic epilogue into a zeroed output when > 1; needs ldo == K).  Used by tools/bench_kernels.py for A/B
+//   measurements and by tests that want a given tile on a small problem.
 static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, float* out, int N, int H, int W, int C, int K,
                            int R, int S, int stride, int pad, int ldx, int ldo, int relu, int tile, int splits_req, float* stats,
-                           int stats_rows, int* nblk_out, void* stream, const DetArgs& det = DetArgs{nullptr, 0, nullptr, 0, nullptr},
-                           const MultiSrc* ms = nullptr) {
-    ConvP p{x, w, bias, out, N, H, W, C, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K,
-            R, S, stride, pad, ldx, ldo, 0, relu, 0, 1};
-    p.stats = nullptr;
-    p.ws = nullptr;
-    p.ctr = nullptr;
-    p.nsrc = 0;
+                           int stats_rows, int* nblk_out, void* stream, const DetArgs& det = NO_DET, const MultiSrc* ms = nullptr) {
+    ConvP p = convp_fwd(x, w, bias, out, N, H, W, C, K, R, S, stride, pad, ldx, ldo, relu);
     if (nblk_out) *nblk_out = 0;
-    if (ms != nullptr) {      // the input is the channel concatenation of ms->xs[]: 1 x 1 / stride 1, every width a multiple of 32
-        if (ms->nsrc < 1 || ms->nsrc > OMNI_MAX_SRC || R != 1 || S != 1 || stride != 1 || pad != 0) return OMNI_ERR_ARG;
-        p.coff[0] = 0;
-        for (int q = 0; q < OMNI_MAX_SRC; ++q) {
-            const bool live = q < ms->nsrc;
-            if (live && (ms->xs[q] == nullptr || ms->cs[q] <= 0 || (ms->cs[q] % 32) != 0)) return OMNI_ERR_ARG;
-            p.xs[q] = live ? (const float*)ms->xs[q] : nullptr;
-            p.coff[q + 1] = p.coff[q] + (live ? ms->cs[q] : 0);
-            if (live && (long)N * H * W * ms->cs[q] * 4 >= (1L << 31)) return OMNI_ERR_ARG;
-        }
-        if (p.coff[ms->nsrc] != C || ldx != C) return OMNI_ERR_ARG;
-        p.nsrc = ms->nsrc;
-        p.x = p.xs[0];
-    }
+    if (ms != nullptr && attach_sources(p, *ms, 32, true) != OMNI_OK) return OMNI_ERR_ARG;
     if (bad_geom(p) || (ldx & 3) || ldx < C || ldo < K || tile < 0 || tile > 4 || splits_req < 0) return OMNI_ERR_ARG;
     if (splits_req > 1 && ldo != K) return OMNI_ERR_ARG;
     const long M = (long)N * p.OH * p.OW;
     if (M == 0) return OMNI_OK;
     hipStream_t st = (hipStream_t)stream;
     const long Kd = (long)R * S * C;
-    // conv_fwd_kernel addresses x and w through buffer resources with 32-bit BYTE offsets (OMNI_OOB = 0x80000000 marks a lane as
-    // out of range): an operand of 2 GiB or more would wrap into the resource and read wrong data silently -- refuse it
-    if (ms == nullptr && (((long)N * H * W - 1) * ldx + C) * 4 >= (1L << 31)) return OMNI_ERR_ARG;
-    if ((long)K * Kd * 4 >= (1L << 31)) return OMNI_ERR_ARG;
+    if (ms == nullptr && !fits_i32(((long)N * H * W - 1) * ldx + C)) return OMNI_ERR_ARG;
+    if (!fits_i32((long)K * Kd)) return OMNI_ERR_ARG;
     const long nslab = (Kd + 31) / 32;
     const long t128 = ((M + 127) / 128) * ((K + 127) / 128);
     const long t64 = ((M + 63) / 64) * ((K + 63) / 64);
@@ -1321,21 +1418,13 @@ static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, fl
     }
     if (splits_req >= 1) splits = splits_req;
     if (splits > nslab) splits = nslab;
-    const int bm = tile == 1 ? 128 : tile == 2 ? 64 : tile == 3 ? 128 : 256;
-    const int bn = tile == 1 ? 128 : tile == 2 ? 64 : tile == 3 ? 64 : 32;
+    int bm, bn;
+    tile_dims(tile, bm, bn);
     const long tiles = ((M + bm - 1) / bm) * ((K + bn - 1) / bn);
-    if (det.plan != nullptr) {
-        det_plan(det, tile, tiles, splits, (long)bm * bn);
-        return OMNI_OK;
-    }
-    const bool ordered = det.ctr != nullptr && splits > 1;      // split partials meet in the workspace, summed in split order
-    if (ordered) {
-        if (!det_fits(det, tiles, splits, (long)bm * bn)) return OMNI_ERR_ARG;
-        p.ws = det.ws;
-        p.ctr = det.ctr;
-    }
-    if (splits > 1 && !ordered) omni_memset_async(out, 0, sizeof(float) * (size_t)M * K, st);
-    if (stats != nullptr && (splits == 1 || ordered) && bias == nullptr && !relu) {      // statistics only from complete, raw outputs
+    const DetLaunch dl = det_prologue(det, tile, tiles, splits, (long)bm * bn, out, sizeof(float) * (size_t)M * K, false, st);
+    if (dl.step != DET_LAUNCH) return dl.step;
+    p.ws = dl.ws; p.ctr = dl.ctr;
+    if (stats != nullptr && (splits == 1 || dl.ordered) && bias == nullptr && !relu) {      // statistics only from complete, raw outputs
         const long rows = (M + bm - 1) / bm;
         if (rows <= stats_rows) {
             p.stats = stats;
@@ -1343,8 +1432,7 @@ static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, fl
         }
     }
 #define OMNI_FWD(BM_, BN_, WM_, WN_, BK_, PF_)                                                                           \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_fwd_kernel<BM_, BN_, WM_, WN_, BK_, PF_>),                                     \
-                       dim3((unsigned)(((M + BM_ - 1) / BM_) * ((K + BN_ - 1) / BN_)), (unsigned)splits), dim3(256), 0, st, p)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_fwd_kernel<BM_, BN_, WM_, WN_, BK_, PF_>), dim3((unsigned)tiles, (unsigned)splits), dim3(256), 0, st, p)
     // (round 5: the 64 x 64 launches of the direct convolutions gained nothing from a deeper ring -- PF 2 / 3 on every one of them:
     // 10.97 / 10.99 ms per step against 10.97, profiles/r05_ab_conv64_pf.log)
     if (tile == 1) OMNI_FWD(128, 128, 2, 2, 32, 1);
@@ -1352,7 +1440,7 @@ static int conv2d_fwd_impl(const float* x, const float* w, const float* bias, fl
     else if (tile == 3) OMNI_FWD(128, 64, 2, 2, 32, 1);
     else OMNI_FWD(256, 32, 4, 1, 16, 1);   // tiny channel counts (stem, level0/1, RPN 16-wide heads): slab depth 16 measured faster
 #undef OMNI_FWD
-    if (splits > 1 && relu && !ordered) {     // (an ordered split applies the ReLU in its last-arriving workgroup)
+    if (splits > 1 && relu && !dl.ordered) {     // (an ordered split applies the ReLU in its last-arriving workgroup)
         const long n4 = M * K / 4;
         long g = (n4 + 255) / 256;
         if (g > 2048) g = 2048;
@@ -1393,19 +1481,13 @@ int omni_conv2d_fwd_det(const float* x, const float* w, const float* bias, float
 int omni_conv2d_fwd_multi_det(const void* const* xs, const int* cs, int nsrc, const float* w, const float* bias, float* out, int N, int H,
                               int W, int K, int ldo, int relu, int tile, int splits_req, float* stats, int stats_rows, int* nblk_out,
                               float* ws, long long ws_floats, int* ctr, int n_ctr, long long* plan, void* stream) {
-    if (xs == nullptr || cs == nullptr || nsrc < 1 || nsrc > OMNI_MAX_SRC) return OMNI_ERR_ARG;
-    long C = 0;
-    for (int q = 0; q < nsrc; ++q) C += cs[q] > 0 ? cs[q] : 0;
-    if (C <= 0 || C > (1 << 20)) return OMNI_ERR_ARG;
+    const int C = sources_width(xs, cs, nsrc);
+    if (C == 0) return OMNI_ERR_ARG;
     const MultiSrc ms{xs, cs, nsrc};
-    return conv2d_fwd_impl((const float*)xs[0], w, bias, out, N, H, W, (int)C, K, 1, 1, 1, 0, (int)C, ldo, relu, tile, splits_req, stats, stats_rows,
+    return conv2d_fwd_impl((const float*)xs[0], w, bias, out, N, H, W, C, K, 1, 1, 1, 0, C, ldo, relu, tile, splits_req, stats, stats_rows,
                            nblk_out, stream, DetArgs{ws, ws_floats, (unsigned*)ctr, n_ctr, plan}, &ms);
 }
 
-// Tile choice: 128x128 when that already fills the 256 CUs, otherwise 64x64 (4x the workgroups); when even
-// that leaves CUs idle and the reduction is deep (DLA level 4/5, FC heads with few rows) the reduction is
-// split over gridDim.y with an atomic epilogue into a zeroed output.  Slab depth 32 (one barrier per 64
-// MFMAs per wave) measured +23 % over 16 on the 3x3 256->256 @128x128 shape (96 -> 119 TFLOP/s).
 int omni_conv2d_fwd(const float* x, const float* w, const float* bias, float* out, int N, int H, int W, int C, int K,
                     int R, int S, int stride, int pad, int ldx, int ldo, int relu, void* stream) {
     return omni_conv2d_fwd_algo(x, w, bias, out, N, H, W, C, K, R, S, stride, pad, ldx, ldo, relu, 0, 0, stream);
@@ -1417,11 +1499,7 @@ int omni_conv2d_fwd(const float* x, const float* w, const float* bias, float* ou
 static int conv2d_dgrad_impl(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K, int R, int S,
                              int stride, int pad, int lddy, int lddx, int accumulate, int tile, int splits_req, void* stream,
                              const DetArgs& det) {
-    ConvP p{dy, w, nullptr, dx, N, H, W, C, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K,
-            R, S, stride, pad, lddy, lddx, 0, 0, accumulate, 1};
-    p.stats = nullptr;
-    p.ws = nullptr;
-    p.ctr = nullptr;
+    ConvP p = convp_dgrad(dy, w, dx, N, H, W, C, K, R, S, stride, pad, lddy, lddx, accumulate);
     if (bad_geom(p) || (K & 3) || (lddy & 3) || lddy < K || lddx < C || tile < 0 || tile > 4 || splits_req < 0) return OMNI_ERR_ARG;
     if (splits_req > 1 && lddx != C && !accumulate) return OMNI_ERR_ARG;
     if ((long)N * H * W == 0) return OMNI_OK;
@@ -1451,46 +1529,31 @@ static int conv2d_dgrad_impl(const float* dy, const float* w, float* dx, int N, 
     }
     if (splits_req >= 1) splits = splits_req;
     if (splits > nslab) splits = nslab;
-    const int bm = tile == 1 ? 128 : tile == 2 ? 64 : tile == 3 ? 128 : 256, bn = tile == 1 ? 128 : tile == 2 ? 64 : tile == 3 ? 64 : 32;
-    const long tiles = ((M + bm - 1) / bm) * ((C + bn - 1) / bn) * ncls;      // counter index: blockIdx.z * gridDim.x + blockIdx.x
-    if (det.plan != nullptr) {
-        det_plan(det, tile, tiles, splits, (long)bm * bn);
-        return OMNI_OK;
-    }
-    const bool ordered = det.ctr != nullptr && splits > 1;
-    if (ordered) {
-        if (!det_fits(det, tiles, splits, (long)bm * bn)) return OMNI_ERR_ARG;
-        p.ws = det.ws;
-        p.ctr = det.ctr;
-    }
-    if (splits > 1 && !accumulate && !ordered) omni_memset_async(dx, 0, sizeof(float) * (size_t)N * H * W * C, st);
+    int bm, bn;
+    tile_dims(tile, bm, bn);
+    const long class_tiles = ((M + bm - 1) / bm) * ((C + bn - 1) / bn);
+    const long tiles = class_tiles * ncls;      // counter index: blockIdx.z * gridDim.x + blockIdx.x
+    const DetLaunch dl = det_prologue(det, tile, tiles, splits, (long)bm * bn, dx, sizeof(float) * (size_t)N * H * W * C, accumulate != 0, st);
+    if (dl.step != DET_LAUNCH) return dl.step;
+    p.ws = dl.ws; p.ctr = dl.ctr;
     // deep-prefetch form (PF = 2) when a 32-bit byte offset reaches both operands, else the classic body
-    const bool dpf_ok = (long)N * p.OH * p.OW * lddy * 4 < (1L << 31) - (1L << 24) && (long)K * R * S * C * 4 < (1L << 31) - (1L << 24);
-#define OMNI_DGRAD_PF(BM_, BN_, WM_, WN_, BK_)                                                                           \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_dgrad_kernel<BM_, BN_, WM_, WN_, BK_, 2>),                                     \
-                       dim3((unsigned)(((M + BM_ - 1) / BM_) * ((C + BN_ - 1) / BN_)), (unsigned)splits, ncls), dim3(256), 0, st, p)
-    if (dpf_ok && tile >= 1 && tile <= 3) {
-        if (tile == 1) OMNI_DGRAD_PF(128, 128, 2, 2, 32);
-        else if (tile == 2) OMNI_DGRAD_PF(64, 64, 2, 2, 32);
-        else OMNI_DGRAD_PF(128, 64, 2, 2, 32);
-        return omni_launch_status();
-    }
-#undef OMNI_DGRAD_PF
-#define OMNI_DGRAD(BM_, BN_, WM_, WN_, BK_)                                                                              \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_dgrad_kernel<BM_, BN_, WM_, WN_, BK_>),                                        \
-                       dim3((unsigned)(((M + BM_ - 1) / BM_) * ((C + BN_ - 1) / BN_)), (unsigned)splits, ncls), dim3(256), 0, st, p)
-    if (tile == 1) OMNI_DGRAD(128, 128, 2, 2, 32);
-    else if (tile == 2) OMNI_DGRAD(64, 64, 2, 2, 32);
-    else if (tile == 3) OMNI_DGRAD(128, 64, 2, 2, 32);
-    else OMNI_DGRAD(256, 32, 4, 1, 16);
+    const bool dpf = fits_i32((long)N * p.OH * p.OW * lddy, PF_HEADROOM) && fits_i32((long)K * R * S * C, PF_HEADROOM);
+#define OMNI_DGRAD(BM_, BN_, WM_, WN_, BK_, PF_)                                                                         \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_dgrad_kernel<BM_, BN_, WM_, WN_, BK_, PF_>), dim3((unsigned)class_tiles, (unsigned)splits, ncls), dim3(256), 0, st, p)
+    if (dpf && tile == 1) OMNI_DGRAD(128, 128, 2, 2, 32, 2);
+    else if (dpf && tile == 2) OMNI_DGRAD(64, 64, 2, 2, 32, 2);
+    else if (dpf && tile == 3) OMNI_DGRAD(128, 64, 2, 2, 32, 2);
+    else if (tile == 1) OMNI_DGRAD(128, 128, 2, 2, 32, 1);
+    else if (tile == 2) OMNI_DGRAD(64, 64, 2, 2, 32, 1);
+    else if (tile == 3) OMNI_DGRAD(128, 64, 2, 2, 32, 1);
+    else OMNI_DGRAD(256, 32, 4, 1, 16, 1);
 #undef OMNI_DGRAD
     return omni_launch_status();
 }
 
 int omni_conv2d_dgrad_algo(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K, int R, int S,
                            int stride, int pad, int lddy, int lddx, int accumulate, int tile, int splits_req, void* stream) {
-    return conv2d_dgrad_impl(dy, w, dx, N, H, W, C, K, R, S, stride, pad, lddy, lddx, accumulate, tile, splits_req, stream,
-                             DetArgs{nullptr, 0, nullptr, 0, nullptr});
+    return conv2d_dgrad_impl(dy, w, dx, N, H, W, C, K, R, S, stride, pad, lddy, lddx, accumulate, tile, splits_req, stream, NO_DET);
 }
 
 // deterministic form (see omni_conv2d_fwd_det): an ordered split writes dx (or dx + the carry when accumulate != 0) once, from the
@@ -1522,8 +1585,8 @@ struct WgradGeom {
 // 128 x 64 are 2.04 rounds of the 768 resident workgroups -- a third round of 32 workgroups costs ~100 us; 3136 tiles of 64 x 64 at four
 // per CU end together: 589 -> 534 us (0.57 -> 0.63 of peak), the cube head's 512-ROI launch 157 -> 142 us (tools/probes/fc_wgrad_tiles.py,
 // profiles/r06_fc_wgrad_tiles.log).  Same slab order per output element.
+constexpr int WBK = 32;      // slab depth of the weight-gradient kernels
 static inline WgradGeom wgrad_geom(int K, int Nn, long P, int tile) {
-    constexpr int WBK = 32;
     // tile: 128x128 for wide layers, 128x64 when the (tap, c) extent is only 64 wide, 64x64 for K <= 64,
     // 32x128 for the <= 32-channel stem layers (a 64-row tile would spend >= half its MFMAs on padding)
     WgradGeom g;
@@ -1536,15 +1599,9 @@ static inline WgradGeom wgrad_geom(int K, int Nn, long P, int tile) {
     else if (K > 32) { g.bm = 64; g.bn = 64; }
     else { g.bm = 32; g.bn = 128; }
     g.tiles = ((K + g.bm - 1) / g.bm) * ((Nn + g.bn - 1) / g.bn);
-    // aim at ~1024 workgroups, at least 256 pixels (8 slabs) per split
-    long splits = (1024 + g.tiles - 1) / g.tiles;
-    const long max_splits = (P + 255) / 256;
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    int pps = (int)((P + splits - 1) / splits);
-    pps = (pps + WBK - 1) / WBK * WBK;
-    g.pps = pps;
-    g.splits = (P + pps - 1) / pps;
+    const RowSplit s = split_rows(1024, g.tiles, P, 256, WBK);      // ~1024 workgroups, at least 256 pixels (8 slabs) per split
+    g.pps = s.rows;
+    g.splits = s.splits;
     return g;
 }
 
@@ -1556,79 +1613,47 @@ static int conv2d_wgrad_impl(const float* x, const float* dy, float* dw, int N, 
     if (tile >= 32) { xcd_order = 0; tile -= 32; }
     else if (tile >= 16) { xcd_order = 1; tile -= 16; }
     if (tile < 0 || tile > 4) return OMNI_ERR_ARG;
-    ConvP p{x, dy, nullptr, dw, N, H, W, C, (H + 2 * pad - R) / stride + 1, (W + 2 * pad - S) / stride + 1, K,
-            R, S, stride, pad, ldx, 0, lddy, 0, accumulate, 1};
-    p.stats = nullptr;
-    p.ws = nullptr;
-    p.ctr = nullptr;
-    p.nsrc = 0;
-    if (ms != nullptr) {      // x is the channel concatenation of ms->xs[]: 1 x 1 / stride 1
-        if (ms->nsrc < 1 || ms->nsrc > OMNI_MAX_SRC || R != 1 || S != 1 || stride != 1 || pad != 0) return OMNI_ERR_ARG;
-        p.coff[0] = 0;
-        for (int q = 0; q < OMNI_MAX_SRC; ++q) {
-            const bool live = q < ms->nsrc;
-            if (live && (ms->xs[q] == nullptr || ms->cs[q] <= 0 || (ms->cs[q] & 3))) return OMNI_ERR_ARG;
-            p.xs[q] = live ? (const float*)ms->xs[q] : nullptr;
-            p.coff[q + 1] = p.coff[q] + (live ? ms->cs[q] : 0);
-        }
-        if (p.coff[ms->nsrc] != C || ldx != C) return OMNI_ERR_ARG;
-        p.nsrc = ms->nsrc;
-        p.x = p.xs[0];
-    }
+    hipStream_t st = (hipStream_t)stream;
+    ConvP p = convp_wgrad(x, dy, dw, N, H, W, C, K, R, S, stride, pad, ldx, lddy, accumulate);
+    if (ms != nullptr && attach_sources(p, *ms, 4, false) != OMNI_OK) return OMNI_ERR_ARG;
     if (bad_geom(p) || (K & 3) || (ldx & 3) || (lddy & 3) || ldx < C || lddy < K) return OMNI_ERR_ARG;
     const long P = (long)N * p.OH * p.OW;
     const int Nn = R * S * C;
-    if (P == 0 && det.plan != nullptr) { det.plan[0] = tile; det.plan[1] = 1; det.plan[2] = det.plan[3] = 0; return OMNI_OK; }
-    if (P == 0) {
-        if (!accumulate) omni_memset_async(dw, 0, sizeof(float) * (size_t)K * Nn, (hipStream_t)stream);
+    const size_t dw_bytes = sizeof(float) * (size_t)K * Nn;
+    if (P == 0) {      // nothing to sum: dw = 0 (or untouched)
+        if (det.plan != nullptr) det_plan(det, tile, 0, 1, 0);
+        else if (!accumulate) omni_memset_async(dw, 0, dw_bytes, st);
         return OMNI_OK;
     }
-    constexpr int WBK = 32;
     const WgradGeom geo = wgrad_geom(K, Nn, P, tile);
     const int bm = geo.bm, bn = geo.bn, tiles = geo.tiles, pps = geo.pps;
     const long splits = geo.splits;
-    if (det.plan != nullptr) {
-        det_plan(det, tile, tiles, splits, (long)bm * bn);
-        return OMNI_OK;
-    }
-    const bool ordered = det.ctr != nullptr && splits > 1;
-    if (ordered && !det_fits(det, tiles, splits, (long)bm * bn)) return OMNI_ERR_ARG;
-    if (det.ctr != nullptr) {             // deterministic: ordered split sums, plain read-modify-write for accumulate
-        p.ws = det.ws;
-        p.ctr = det.ctr;
-    }
-    if (splits > 1 && !accumulate && !ordered) omni_memset_async(dw, 0, sizeof(float) * (size_t)K * Nn, (hipStream_t)stream);
+    // deterministic: ordered split sums, plain read-modify-write for accumulate (ctr attached to unsplit launches too)
+    const DetLaunch dl = det_prologue(det, tile, tiles, splits, (long)bm * bn, dw, dw_bytes, accumulate != 0, st, true);
+    if (dl.step != DET_LAUNCH) return dl.step;
+    p.ws = dl.ws; p.ctr = dl.ctr;
     // fc-class weight gradients (one split): XCD-contiguous tile order (fc1: 615 -> 562 us, profiles/r03_fc_wgrad_xcd_order.log)
     if (xcd_order < 0) xcd_order = (R == 1 && S == 1 && H == 1 && W == 1 && splits == 1) ? 1 : 0;
     p.relu = xcd_order;
     // deep-prefetch form (conv_wgrad_pf_kernel): single-source problems whose operands a 32-bit buffer offset reaches
-    // (16 MiB of head-room: the byte cursors run up to PF slabs past the last pixel before their loads are masked)
-    const bool pf_ok = ms == nullptr && (long)P * lddy * 4 < (1L << 31) - (1L << 24) && (long)N * H * W * ldx * 4 < (1L << 31) - (1L << 24);
-#define OMNI_WGRAD_PF(BM_, BN_, WM_, WN_, PF_)                                                                          \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_pf_kernel<BM_, BN_, WM_, WN_, WBK, PF_>), dim3(tiles, (unsigned)splits), dim3(256), 0, \
-                       (hipStream_t)stream, p, pps)
-    if (pf_ok) {
-        if (bm == 128 && bn == 128) OMNI_WGRAD_PF(128, 128, 2, 2, 2);
-        else if (bm == 128) OMNI_WGRAD_PF(128, 64, 2, 2, 2);
-        else if (bm == 64) OMNI_WGRAD_PF(64, 64, 2, 2, 2);
-        else OMNI_WGRAD_PF(32, 128, 1, 4, 2);
-        return omni_launch_status();
-    }
-#undef OMNI_WGRAD_PF
-#define OMNI_WGRAD(BM_, BN_, WM_, WN_)                                                                                  \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_kernel<BM_, BN_, WM_, WN_, WBK>), dim3(tiles, (unsigned)splits), dim3(256), 0, \
-                       (hipStream_t)stream, p, pps)
-    if (bm == 128 && bn == 128) OMNI_WGRAD(128, 128, 2, 2);
-    else if (bm == 128) OMNI_WGRAD(128, 64, 2, 2);
-    else if (bm == 64) OMNI_WGRAD(64, 64, 2, 2);
-    else OMNI_WGRAD(32, 128, 1, 4);
+    const bool pf = ms == nullptr && fits_i32((long)P * lddy, PF_HEADROOM) && fits_i32((long)N * H * W * ldx, PF_HEADROOM);
+#define OMNI_WGRAD(KERNEL_, ...) \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL_<__VA_ARGS__>), dim3(tiles, (unsigned)splits), dim3(256), 0, st, p, pps)
+    if (pf && bm == 128 && bn == 128) OMNI_WGRAD(conv_wgrad_pf_kernel, 128, 128, 2, 2, WBK, 2);
+    else if (pf && bm == 128) OMNI_WGRAD(conv_wgrad_pf_kernel, 128, 64, 2, 2, WBK, 2);
+    else if (pf && bm == 64) OMNI_WGRAD(conv_wgrad_pf_kernel, 64, 64, 2, 2, WBK, 2);
+    else if (pf) OMNI_WGRAD(conv_wgrad_pf_kernel, 32, 128, 1, 4, WBK, 2);
+    else if (bm == 128 && bn == 128) OMNI_WGRAD(conv_wgrad_kernel, 128, 128, 2, 2, WBK);
+    else if (bm == 128) OMNI_WGRAD(conv_wgrad_kernel, 128, 64, 2, 2, WBK);
+    else if (bm == 64) OMNI_WGRAD(conv_wgrad_kernel, 64, 64, 2, 2, WBK);
+    else OMNI_WGRAD(conv_wgrad_kernel, 32, 128, 1, 4, WBK);
 #undef OMNI_WGRAD
     return omni_launch_status();
 }
 
 int omni_conv2d_wgrad_algo(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K, int R, int S,
                            int stride, int pad, int ldx, int lddy, int accumulate, int tile, void* stream) {
-    return conv2d_wgrad_impl(x, dy, dw, N, H, W, C, K, R, S, stride, pad, ldx, lddy, accumulate, tile, stream, DetArgs{nullptr, 0, nullptr, 0, nullptr});
+    return conv2d_wgrad_impl(x, dy, dw, N, H, W, C, K, R, S, stride, pad, ldx, lddy, accumulate, tile, stream, NO_DET);
 }
 
 // deterministic form: ctr must be non-null even for a launch that is not split (it selects the plain read-modify-write epilogue of an
@@ -1645,12 +1670,10 @@ int omni_conv2d_wgrad_det(const float* x, const float* dy, float* dw, int N, int
 int omni_conv2d_wgrad_multi_det(const void* const* xs, const int* cs, int nsrc, const float* dy, float* dw, int N, int H, int W, int K,
                                 int lddy, int accumulate, int tile, float* ws, long long ws_floats, int* ctr, int n_ctr, long long* plan,
                                 void* stream) {
-    if (xs == nullptr || cs == nullptr || nsrc < 1 || nsrc > OMNI_MAX_SRC) return OMNI_ERR_ARG;
-    long C = 0;
-    for (int q = 0; q < nsrc; ++q) C += cs[q] > 0 ? cs[q] : 0;
-    if (C <= 0 || C > (1 << 20)) return OMNI_ERR_ARG;
+    const int C = sources_width(xs, cs, nsrc);
+    if (C == 0) return OMNI_ERR_ARG;
     const MultiSrc ms{xs, cs, nsrc};
-    return conv2d_wgrad_impl((const float*)xs[0], dy, dw, N, H, W, (int)C, K, 1, 1, 1, 0, (int)C, lddy, accumulate, tile, stream,
+    return conv2d_wgrad_impl((const float*)xs[0], dy, dw, N, H, W, C, K, 1, 1, 1, 0, C, lddy, accumulate, tile, stream,
                              DetArgs{ws, ws_floats, (unsigned*)ctr, n_ctr, plan}, &ms);
 }
 
@@ -1664,8 +1687,10 @@ int omni_gemm_batched_fwd_algo(const float* x, const float* w, float* out, int b
     if (batch <= 0 || M < 0 || C <= 0 || K <= 0 || (C & 3) || algo < 0 || algo > 4 || workgroups < 0) return OMNI_ERR_ARG;
     if (algo == 1 && ((C % 32) != 0 || (workgroups & 7))) return OMNI_ERR_ARG;
     if (M == 0) return OMNI_OK;
-    ConvP p{x, w, nullptr, out, M, 1, 1, C, 1, 1, K, 1, 1, 1, 0, C, K, 0, 0, 0, 1, (long)M * C, (long)K * C, (long)M * K};
+    hipStream_t st = (hipStream_t)stream;
+    const ConvP p = convp_batched(x, w, out, M, C, K, false);
     const long t128 = (((long)M + 127) / 128) * ((K + 127) / 128);
+    const long t64 = (((long)M + 63) / 64) * ((K + 63) / 64);
     // measured per shape (tools/sweep_batched_gemm.py, hipGraph replay): the persistent kernel from 1024 128x128 tiles up, 64x64 tiles
     // below (36x[1024x256]x[256x256]^T: 60 us against 76 us with one 128x128 tile per workgroup); C % 64 == 0: the deep-prefetch
     // 64x64 kernel instead (profiles/r03_sweep_batched_gemm.log: 17-27 % faster on every small-map shape)
@@ -1673,25 +1698,21 @@ int omni_gemm_batched_fwd_algo(const float* x, const float* w, float* out, int b
     if (algo == 1) {
         // >= 2 items per resident workgroup: persistent kernel with the prefetch carried across items
         GemmP g{x, w, out, batch, M, K, C, (M + 127) / 128, (K + 127) / 128};
-        hipLaunchKernelGGL(gemm_nt_persistent_kernel, dim3(workgroups ? workgroups : 512), dim3(256), 0, (hipStream_t)stream, g);
+        hipLaunchKernelGGL(gemm_nt_persistent_kernel, dim3(workgroups ? workgroups : 512), dim3(256), 0, st, g);
         return omni_launch_status();
     }
-    if (algo == 3 && (C % 64) == 0 && (long)M * C * 4 < (1L << 31) && (long)K * C * 4 < (1L << 31)) algo = 4;
+    const bool pf_ok = (C % 64) == 0 && fits_i32((long)M * C) && fits_i32((long)K * C);
+    if (algo == 3 && pf_ok) algo = 4;
     if (algo == 2)   // else 64x64 tiles: 4x the workgroups (measured on the 256ch @32x32 layers)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_fwd_kernel<128, 128, 2, 2, 32>), dim3((unsigned)t128, 1, (unsigned)batch), dim3(256), 0,
-                           (hipStream_t)stream, p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_fwd_kernel<128, 128, 2, 2, 32>), dim3((unsigned)t128, 1, (unsigned)batch), dim3(256), 0, st, p);
     else if (algo == 3)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_fwd_kernel<64, 64, 2, 2, 32>),
-                           dim3((unsigned)((((long)M + 63) / 64) * ((K + 63) / 64)), 1, (unsigned)batch), dim3(256), 0,
-                           (hipStream_t)stream, p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_fwd_kernel<64, 64, 2, 2, 32>), dim3((unsigned)t64, 1, (unsigned)batch), dim3(256), 0, st, p);
     else {           // 64x64 tiles, PF slabs of buffer-load prefetch in flight (gemm_nt_pf_kernel)
-        if ((C % 64) != 0 || (long)M * C * 4 >= (1L << 31) || (long)K * C * 4 >= (1L << 31)) return OMNI_ERR_ARG;
+        if (!pf_ok || t64 * batch > 0x7fffffff) return OMNI_ERR_ARG;
         GemmTP g{x, w, out, M, K, C, (long)M * C, (long)K * C, (long)M * K, nullptr, nullptr};
-        const long wgs = (((long)M + 63) / 64) * ((K + 63) / 64) * batch;
-        if (wgs > 0x7fffffff) return OMNI_ERR_ARG;
-        const dim3 grid((unsigned)wgs);
-        if ((C % 128) == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_nt_pf_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, g);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_nt_pf_kernel<2>), grid, dim3(256), 0, (hipStream_t)stream, g);
+        const dim3 grid((unsigned)(t64 * batch));
+        if ((C % 128) == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_nt_pf_kernel<4>), grid, dim3(256), 0, st, g);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_nt_pf_kernel<2>), grid, dim3(256), 0, st, g);
     }
     return omni_launch_status();
 }
@@ -1701,83 +1722,49 @@ int omni_gemm_batched_fwd_algo(const float* x, const float* w, float* out, int b
 // with 2-4 slabs of buffer-load prefetch in flight (gemm_tn_pf_kernel; profiles/r03_sweep_batched_gemm.log: 3-66 % faster on every
 // Winograd weight-gradient shape)
 // 64x64 tiles of gemm_tn_pf_kernel: row splits of >= 8 slabs, aiming at >= 512 workgroups
-static inline void tn_pf_plan(int batch, int M, int C, int K, int& tiles, long& splits, int& rps) {
+static inline RowSplit tn_pf_plan(int batch, int M, int C, int K, int& tiles) {
     tiles = ((K + 63) / 64) * ((C + 63) / 64);
-    splits = (512 + (long)tiles * batch - 1) / ((long)tiles * batch);
-    const long max_splits = ((long)M + 255) / 256;
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    rps = (int)(((long)M + splits - 1) / splits);
-    rps = (rps + 127) / 128 * 128;                                   // multiple of 32 * PF for PF = 4
-    splits = ((long)M + rps - 1) / rps;
+    return split_rows(512, (long)tiles * batch, M, 256, 128);      // unit: a multiple of 32 * PF for PF = 4
 }
 
 static int gemm_batched_wgrad_impl(const float* x, const float* dy, float* dw, int batch, int M, int C, int K, int algo, void* stream,
                                    const DetArgs& det) {
     if (batch <= 0 || M < 0 || C <= 0 || K <= 0 || (C & 3) || (K & 3) || algo < 0 || algo > 2) return OMNI_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
+    const size_t dw_bytes = sizeof(float) * (size_t)batch * K * C;
     if (M == 0) {
-        if (det.plan != nullptr) { det.plan[0] = algo; det.plan[1] = 1; det.plan[2] = det.plan[3] = 0; return OMNI_OK; }
-        omni_memset_async(dw, 0, sizeof(float) * (size_t)batch * K * C, st);
+        if (det.plan != nullptr) det_plan(det, algo, 0, 1, 0);
+        else omni_memset_async(dw, 0, dw_bytes, st);
         return OMNI_OK;
     }
-    const bool fits = (long)M * C * 4 < (1L << 31) && (long)M * K * 4 < (1L << 31);
+    const bool fits = fits_i32((long)M * C) && fits_i32((long)M * K);
     if (algo == 2 && !fits) return OMNI_ERR_ARG;
     if (algo == 0) algo = fits ? 2 : 1;
+    // algo 2: 64x64 tiles of gemm_tn_pf_kernel; algo 1: 128x128 tiles of conv_wgrad_kernel when both extents are wide, else 64x64,
+    // aiming at ~1024 workgroups
+    const bool wide = algo == 1 && K > 64 && C > 64;
+    const int bt = wide ? 128 : 64;
+    int tiles = ((K + bt - 1) / bt) * ((C + bt - 1) / bt);
+    const RowSplit s = algo == 2 ? tn_pf_plan(batch, M, C, K, tiles) : split_rows(1024, (long)tiles * batch, M, 256, WBK);
+    const DetLaunch dl = det_prologue(det, algo, (long)tiles * batch, s.splits, (long)bt * bt, dw, dw_bytes, false, st);
+    if (dl.step != DET_LAUNCH) return dl.step;
     if (algo == 2) {
-        int tiles, rps;
-        long splits;
-        tn_pf_plan(batch, M, C, K, tiles, splits, rps);
-        if (det.plan != nullptr) {
-            det_plan(det, algo, (long)tiles * batch, splits, 64 * 64);
-            return OMNI_OK;
-        }
-        const bool ordered = det.ctr != nullptr && splits > 1;
-        if (ordered && !det_fits(det, (long)tiles * batch, splits, 64 * 64)) return OMNI_ERR_ARG;
-        if (splits > 1 && !ordered) omni_memset_async(dw, 0, sizeof(float) * (size_t)batch * K * C, st);
-        GemmTP g{dy, x, dw, M, K, C, (long)M * K, (long)M * C, (long)K * C, ordered ? det.ws : nullptr, ordered ? det.ctr : nullptr};
-        const long wgs = (long)tiles * splits * batch;
+        GemmTP g{dy, x, dw, M, K, C, (long)M * K, (long)M * C, (long)K * C, dl.ws, dl.ctr};
+        const long wgs = (long)tiles * s.splits * batch;
         if (wgs > 0x7fffffff) return OMNI_ERR_ARG;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_tn_pf_kernel<4>), dim3((unsigned)wgs), dim3(256), 0, st, g, rps, (int)splits);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gemm_tn_pf_kernel<4>), dim3((unsigned)wgs), dim3(256), 0, st, g, s.rows, (int)s.splits);
         return omni_launch_status();
     }
-    ConvP p{x, dy, nullptr, dw, M, 1, 1, C, 1, 1, K, 1, 1, 1, 0, C, 0, K, 0, 0, 1, (long)M * C, (long)M * K, (long)K * C};
-    constexpr int WBK = 32;
-    const bool wide = K > 64 && C > 64;
-    const int bm = wide ? 128 : 64, bn = wide ? 128 : 64;
-    const int tiles = ((K + bm - 1) / bm) * ((C + bn - 1) / bn);
-    long splits = (1024 + (long)tiles * batch - 1) / ((long)tiles * batch);
-    const long max_splits = ((long)M + 255) / 256;
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    int pps = (int)(((long)M + splits - 1) / splits);
-    pps = (pps + WBK - 1) / WBK * WBK;
-    splits = ((long)M + pps - 1) / pps;
-    p.stats = nullptr;
-    p.ws = nullptr;
-    p.ctr = nullptr;
-    if (det.plan != nullptr) {
-        det_plan(det, algo, (long)tiles * batch, splits, (long)bm * bn);
-        return OMNI_OK;
-    }
-    const bool ordered = det.ctr != nullptr && splits > 1;
-    if (ordered) {
-        if (!det_fits(det, (long)tiles * batch, splits, (long)bm * bn)) return OMNI_ERR_ARG;
-        p.ws = det.ws;
-        p.ctr = det.ctr;
-    }
-    if (splits > 1 && !ordered) omni_memset_async(dw, 0, sizeof(float) * (size_t)batch * K * C, st);
-    if (wide)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_kernel<128, 128, 2, 2, WBK>), dim3(tiles, (unsigned)splits, (unsigned)batch),
-                           dim3(256), 0, st, p, pps);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_kernel<64, 64, 2, 2, WBK>), dim3(tiles, (unsigned)splits, (unsigned)batch),
-                           dim3(256), 0, st, p, pps);
+    ConvP p = convp_batched(x, dy, dw, M, C, K, true);
+    p.ws = dl.ws; p.ctr = dl.ctr;
+    const dim3 grid(tiles, (unsigned)s.splits, (unsigned)batch);
+    if (wide) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_kernel<128, 128, 2, 2, WBK>), grid, dim3(256), 0, st, p, s.rows);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_kernel<64, 64, 2, 2, WBK>), grid, dim3(256), 0, st, p, s.rows);
     return omni_launch_status();
 }
 
 int omni_gemm_batched_wgrad_algo(const float* x, const float* dy, float* dw, int batch, int M, int C, int K, int algo, void* stream) {
-    return gemm_batched_wgrad_impl(x, dy, dw, batch, M, C, K, algo, stream, DetArgs{nullptr, 0, nullptr, 0, nullptr});
+    return gemm_batched_wgrad_impl(x, dy, dw, batch, M, C, K, algo, stream, NO_DET);
 }
 
 int omni_gemm_batched_wgrad_det(const float* x, const float* dy, float* dw, int batch, int M, int C, int K, int algo, float* ws,
@@ -1795,7 +1782,7 @@ int omni_gemm_batched_wgrad_multi(const void* const* x, const void* const* dy, c
                                   long long* plan, void* stream) {
     if (n <= 0 || n > TN_MULTI_MAX || x == nullptr || dy == nullptr || dw == nullptr) return OMNI_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    struct One { int i, tiles, rps; long splits, ws_off, ctr_off; };
+    struct One { int i, tiles; RowSplit s; long ws_off, ctr_off; };
     One one[TN_MULTI_MAX];
     long ws_need = 0, ctr_need = 0;
     int live = 0;
@@ -1803,19 +1790,19 @@ int omni_gemm_batched_wgrad_multi(const void* const* x, const void* const* dy, c
         if (batch[i] <= 0 || M[i] < 0 || C[i] <= 0 || K[i] <= 0 || (C[i] & 3) || (K[i] & 3) || dw[i] == nullptr ||
             (M[i] > 0 && (x[i] == nullptr || dy[i] == nullptr)))
             return OMNI_ERR_ARG;
-        if ((long)M[i] * C[i] * 4 >= (1L << 31) || (long)M[i] * K[i] * 4 >= (1L << 31)) return OMNI_ERR_ARG;
+        if (!fits_i32((long)M[i] * C[i]) || !fits_i32((long)M[i] * K[i])) return OMNI_ERR_ARG;
         if (M[i] == 0) {
             if (plan == nullptr) omni_memset_async((void*)dw[i], 0, sizeof(float) * (size_t)batch[i] * K[i] * C[i], st);
             continue;
         }
         One& o = one[live++];
         o.i = i;
-        tn_pf_plan(batch[i], M[i], C[i], K[i], o.tiles, o.splits, o.rps);
+        o.s = tn_pf_plan(batch[i], M[i], C[i], K[i], o.tiles);
         o.ws_off = ws_need;
         o.ctr_off = ctr_need;
-        if (o.splits > 1) {
-            ws_need += omni_split_ws_floats((long)o.tiles * batch[i], o.splits, 64 * 64);
-            ctr_need += omni_split_counters((long)o.tiles * batch[i], o.splits);
+        if (o.s.splits > 1) {
+            ws_need += omni_split_ws_floats((long)o.tiles * batch[i], o.s.splits, 64 * 64);
+            ctr_need += omni_split_counters((long)o.tiles * batch[i], o.s.splits);
         }
     }
     if (plan != nullptr) {
@@ -1829,7 +1816,7 @@ int omni_gemm_batched_wgrad_multi(const void* const* x, const void* const* dy, c
     for (int a = 1; a < live; ++a) {
         const One v = one[a];
         int b = a;
-        for (; b > 0 && one[b - 1].rps < v.rps; --b) one[b] = one[b - 1];
+        for (; b > 0 && one[b - 1].s.rows < v.s.rows; --b) one[b] = one[b - 1];
         one[b] = v;
     }
     GemmTnMulti t;
@@ -1838,13 +1825,13 @@ int omni_gemm_batched_wgrad_multi(const void* const* x, const void* const* dy, c
     for (int j = 0; j < live; ++j) {
         const One& o = one[j];
         const int i = o.i;
-        const bool split = o.splits > 1;
+        const bool split = o.s.splits > 1;
         if (split && !ordered) omni_memset_async((void*)dw[i], 0, sizeof(float) * (size_t)batch[i] * K[i] * C[i], st);
         t.p[j] = GemmTP{(const float*)dy[i], (const float*)x[i], (float*)dw[i], M[i], K[i], C[i], (long)M[i] * K[i], (long)M[i] * C[i],
                         (long)K[i] * C[i], (split && ordered) ? ws + o.ws_off : nullptr, (split && ordered) ? (unsigned*)ctr + o.ctr_off : nullptr};
-        t.rps[j] = o.rps;
-        t.splits[j] = (int)o.splits;
-        const long items = (long)o.tiles * o.splits * batch[i];
+        t.rps[j] = o.s.rows;
+        t.splits[j] = (int)o.s.splits;
+        const long items = (long)o.tiles * o.s.splits * batch[i];
         if (items > 0x3fffffff) return OMNI_ERR_ARG;
         t.items[j] = (int)items;
         t.first[j] = (int)first;
@@ -1860,9 +1847,13 @@ int omni_gemm_batched_wgrad_multi(const void* const* x, const void* const* dy, c
 // (cubercnn/modeling/backbone/dla.py:112-153; 32 or 64 groups of 4..32 channels).  The G independent convolutions read / write
 // channel slices of the same NHWC tensors: the implicit-GEMM kernels already take the pixel pitch (ldx / ldo) separately from
 // the channel count, so every group is one launch of them on offset pointers; w (K, R, S, C/G) keeps a group's filters contiguous.
+static inline bool bad_groups(int C, int K, int groups) {
+    return groups <= 0 || C % groups || K % groups || ((C / groups) & 3) || ((K / groups) & 3);
+}
+
 int omni_grouped_conv2d_fwd(const float* x, const float* w, float* out, int N, int H, int W, int C, int K, int R, int S, int stride,
                             int pad, int groups, void* stream) {
-    if (groups <= 0 || C % groups || K % groups || ((C / groups) & 3) || ((K / groups) & 3)) return OMNI_ERR_ARG;
+    if (bad_groups(C, K, groups)) return OMNI_ERR_ARG;
     const int Cg = C / groups, Kg = K / groups;
     for (int g = 0; g < groups; ++g) {
         const int rc = conv2d_fwd_impl(x + g * Cg, w + (size_t)g * Kg * R * S * Cg, nullptr, out + g * Kg, N, H, W, Cg, Kg, R, S, stride,
@@ -1874,7 +1865,7 @@ int omni_grouped_conv2d_fwd(const float* x, const float* w, float* out, int N, i
 
 int omni_grouped_conv2d_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, int K, int R, int S, int stride,
                               int pad, int groups, void* stream) {
-    if (groups <= 0 || C % groups || K % groups || ((C / groups) & 3) || ((K / groups) & 3)) return OMNI_ERR_ARG;
+    if (bad_groups(C, K, groups)) return OMNI_ERR_ARG;
     const int Cg = C / groups, Kg = K / groups;
     for (int g = 0; g < groups; ++g) {
         const int rc = omni_conv2d_dgrad_algo(dy + g * Kg, w + (size_t)g * Kg * R * S * Cg, dx + g * Cg, N, H, W, Cg, Kg, R, S, stride, pad,
@@ -1887,7 +1878,7 @@ int omni_grouped_conv2d_dgrad(const float* dy, const float* w, float* dx, int N,
 // dw (K, R, S, C/G) overwritten
 int omni_grouped_conv2d_wgrad(const float* x, const float* dy, float* dw, int N, int H, int W, int C, int K, int R, int S, int stride,
                               int pad, int groups, void* stream) {
-    if (groups <= 0 || C % groups || K % groups || ((C / groups) & 3) || ((K / groups) & 3)) return OMNI_ERR_ARG;
+    if (bad_groups(C, K, groups)) return OMNI_ERR_ARG;
     const int Cg = C / groups, Kg = K / groups;
     for (int g = 0; g < groups; ++g) {
         const int rc = omni_conv2d_wgrad_algo(x + g * Cg, dy + g * Kg, dw + (size_t)g * Kg * R * S * Cg, N, H, W, Cg, Kg, R, S, stride, pad,
