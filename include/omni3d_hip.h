@@ -757,6 +757,26 @@ int omni_match_errors(const float* dt_box, const int* dt_cat, const float* dt_c2
                       const float* gt_dims, const float* gt_pose, const int* gt_off, const float* K, int I, int D, int G, int* match,
                       float* err, double* sums, long long* counts, double* workspace, void* stream);
 
+/* The selection behind the training-time drawings of `RCNN3D.visualize_training` (csrc/train_vis.hip), for the training-mode rows of a
+ * whole batch in one launch.  It stands for predict_boxes_for_gt_classes (cubercnn/modeling/roi_heads/roi_heads.py:276-281),
+ * scores = exp(-uncertainty of the GT class) (:782-805) and `batched_nms(pred_boxes, scores, zeros, test_nms_thresh)[:20]`
+ * (cubercnn/modeling/meta_arch/rcnn3d.py:207-214).
+ *   pred (B*S, ldp)   box-head output [K+1 logits | 4K deltas]; head (B*Fc, ldh) cube-head output, uncert_off = column of its
+ *                     uncertainty block ((5 + bins + Pn) * K), or -1 when USE_CONFIDENCE is 0: every score is then 1 and the rows keep
+ *                     their order (the reference's score is, by accident of `cube_3D_i[:, -1]`, the v coordinate there)
+ *   rois (B,Fc,4), cls (B,Fc) int32, nfg (B) int32: the cube prefix and the foreground count the sampler writes.  Image b uses pred
+ *                     rows b*S + j and head rows b*Fc + j for j < nfg[b] (clamped to [0, min(Fc, S)])
+ *   wx..wh, scale_clamp  Box2BoxTransform weights and clamp, as omni_box_decode_gt_class (the same device function, unclipped)
+ * Per image: rows in descending score (ties to the lower row), greedy NMS -- j is suppressed after a kept i when
+ * inter / (area_i + area_j - inter) > iou_thr in float32 (torchvision box_iou) -- until max_keep rows are kept.  A row whose box or
+ * score is not finite, or whose class lies outside [0, K), is never kept and never suppresses.  Out:
+ *   keep_row (B,max_keep) int32 the kept rows j in that order, -1 beyond keep_count (B) int32; keep_box (B,max_keep,4) and keep_score
+ *   (B,max_keep), zero beyond the count.
+ * One 256-thread workgroup per image, no atomics, two runs give the same bits.  Fc > 1024 (the LDS capacity) returns OMNI_ERR_ARG. */
+int omni_train_vis_pick(const float* pred, int ldp, const float* head, int ldh, int uncert_off, const float* rois, const int* cls,
+                        const int* nfg, int B, int S, int Fc, int K, float wx, float wy, float ww, float wh, float scale_clamp,
+                        float iou_thr, int max_keep, int* keep_row, int* keep_count, float* keep_box, float* keep_score, void* stream);
+
 /* Deriving the box fields of Omni3D annotations (csrc/annotate.hip) for a whole dataset in two calls.  Rows are ragged by image as
  * above: the boxes of image i are rows box_off[i] .. box_off[i + 1] - 1 (box_off (I + 1) int32, starting at 0, non-decreasing, ending
  * at N; not checked here).  box3d (N,6) [X,Y,Z,W,H,L] camera space, R (N,9), K (I,9) row-major, size (I,2) int32 [W, H].

@@ -13,6 +13,7 @@
 // registers, the workgroup combines them in LDS and issues at most 7 fp64 atomics (round 3: 2-7 atomics per ROW on the same
 // 7 doubles -- ~6000 serialised atomics for 2048 ROIs -- were 72 us).
 #include <device_rt.h>
+#include "box_decode.h"
 
 namespace {
 
@@ -116,14 +117,9 @@ __global__ void __launch_bounds__(256) box_decode_gt_kernel(const float* __restr
     if (r >= R) return;
     const float* pb = prop + 4 * (long)r;
     float* o = out + 4 * (long)r;
-    int c = cls[r];
+    const int c = cls[r];
     if (c < 0) { o[0] = pb[0]; o[1] = pb[1]; o[2] = pb[2]; o[3] = pb[3]; return; }
-    c = c > K - 1 ? K - 1 : c;                              // gt_classes.clamp_(0, K - 1): background rows use the last class
-    const float* d = pred + (long)r * ldp + (K + 1) + 4 * c;
-    const float w = pb[2] - pb[0], h = pb[3] - pb[1], cx = pb[0] + 0.5f * w, cy = pb[1] + 0.5f * h;
-    const float dx = d[0] / wx, dy = d[1] / wy, dw = fminf(d[2] / ww, scale_clamp), dh = fminf(d[3] / wh, scale_clamp);
-    const float pcx = dx * w + cx, pcy = dy * h + cy, pw = expf(dw) * w, ph = expf(dh) * h;
-    o[0] = pcx - 0.5f * pw; o[1] = pcy - 0.5f * ph; o[2] = pcx + 0.5f * pw; o[3] = pcy + 0.5f * ph;
+    omni_decode_gt_class_box(pred + (long)r * ldp, K, c, pb, wx, wy, ww, wh, scale_clamp, o);
 }
 
 }  // namespace

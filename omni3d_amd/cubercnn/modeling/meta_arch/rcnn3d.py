@@ -8,7 +8,7 @@ import torch
 from torch import nn
 
 from ....d2.config import configurable
-from ....d2.events import get_event_storage, has_event_storage
+from ....d2.events import get_event_storage, has_event_storage, is_vis_iteration
 from ....d2.layers import ShapeSpec
 from ....d2.structures import ImageList
 from .... import functional as HF
@@ -147,7 +147,18 @@ class RCNN3D(nn.Module):
         pk = {"targets": packed} if getattr(self.proposal_generator, "accepts_packed", False) else {}
         proposals, proposal_losses = self.proposal_generator(images, features, gt_instances, **pk)
         pk = {"packed": packed} if getattr(self.roi_heads, "accepts_packed", False) else {}
-        _, detector_losses = self.roi_heads(images, features, proposals, Ks, im_scales_ratio, gt_instances, **pk)
+        # rcnn3d.py:69-72.  Not for a caller that pre-staged its batch (bench.py, the capture of a graphed step): those pass `packed`
+        draw = packed_given is None and is_vis_iteration(self.vis_period)
+        if draw and hasattr(self.roi_heads, "want_predictions"):
+            self.roi_heads.want_predictions = True          # this iteration's training branch also returns its predictions
+        try:
+            instances, detector_losses = self.roi_heads(images, features, proposals, Ks, im_scales_ratio, gt_instances, **pk)
+        finally:
+            if draw and hasattr(self.roi_heads, "want_predictions"):
+                self.roi_heads.want_predictions = False
+        if draw:
+            self.visualize_training(batched_inputs, proposals, instances)
+        del instances
         losses = HF.LossDict()
         losses.update(detector_losses)
         losses.update(proposal_losses)
@@ -159,6 +170,78 @@ class RCNN3D(nn.Module):
             from ...solver.ddp import tie_to_anchor     # loop-level call under the script's DDP wrapper (cubercnn/solver/ddp.py)
             tie_to_anchor(self, losses)
         return losses
+
+    @torch.no_grad()
+    def visualize_training(self, batched_inputs, proposals, instances):
+        """rcnn3d.py:114-245: two images of the FIRST sample of the batch into the event storage, each (3, H, 2W) uint8 RGB -- ground-truth
+        2D boxes beside the first 20 proposals, and ground-truth cuboids beside the predicted ones.  `proposals`: list[Instances] or this
+        package's packed proposals; `instances`: what the ROI heads' training branch returned with `want_predictions` set, i.e. already
+        the rows the reference's class-agnostic NMS keeps (csrc/train_vis.hip).  Departures: no detectron2 `Visualizer` -- the 2D boxes
+        are `vis.draw_2d_box` outlines in `util.get_color(i)`, not its random colours; without USE_CONFIDENCE the scores are 1.0.
+        Reads only: no parameter, buffer or random state is touched."""
+        import numpy as np
+        from ....d2.data import MetadataCatalog
+        from ...util import math_util, util
+        from ...vis import vis
+        storage = get_event_storage()
+        max_vis_prop = 20
+        if not hasattr(self, "thing_classes"):
+            self.thing_classes = list(MetadataCatalog.get("omni3d_model").thing_classes)
+            self.num_classes = len(self.thing_classes)
+        if len(batched_inputs) == 0 or len(instances) == 0:
+            return
+        input, instances_i = batched_inputs[0], instances[0]            # only one image of a batch is drawn (rcnn3d.py:245)
+        img = input["image"].permute(1, 2, 0).cpu().numpy()
+        if self.input_format == "BGR":                                   # detectron2 convert_image_to_rgb
+            img = img[:, :, ::-1]
+        img = np.ascontiguousarray(img.astype(np.uint8, copy=False))
+        H, W = img.shape[:2]
+        img_3DGT = np.ascontiguousarray(img.copy()[:, :, [2, 1, 1]])     # (the reference's channel shuffle, kept as it is)
+        img_3DPR = np.ascontiguousarray(img.copy()[:, :, [2, 1, 1]])
+        gts = input["instances"]
+
+        # ---- the 2D ground truth and the proposals ----
+        if hasattr(proposals, "boxes"):                                  # packed (B, P, 4) + count, in score order
+            prop_boxes = proposals.boxes[0, :min(int(proposals.count[0]), max_vis_prop)]
+        else:
+            prop_boxes = proposals[0].proposal_boxes.tensor[:max_vis_prop]
+        anno_img, prop_img = img.copy(), img.copy()
+        for im, boxes in ((anno_img, gts.gt_boxes.tensor), (prop_img, prop_boxes)):
+            for i, (x1, y1, x2, y2) in enumerate(boxes.detach().cpu().tolist()):
+                vis.draw_2d_box(im, [x1, y1, x2 - x1, y2 - y1], color=util.get_color(i), thickness=max(1, int(np.round(2 * H / 500))))
+        storage.put_image("Left: GT 2D bounding boxes; Right: Predicted 2D proposals",
+                          np.ascontiguousarray(np.concatenate((anno_img, prop_img), axis=1).transpose(2, 0, 1)))
+
+        # ---- the 3D ground truth and the predictions ----
+        K = torch.tensor(input["K"], dtype=torch.float32)
+        scale = input["height"] / img.shape[0]
+        fx, sx = (val.item() / scale for val in K[0, [0, 2]])
+        fy, sy = (val.item() / scale for val in K[1, [1, 2]])
+        K_scaled = (torch.tensor([[1 / scale, 0, 0], [0, 1 / scale, 0], [0, 0, 1.0]], dtype=torch.float32) @ K).numpy()
+        gt_classes = gts.gt_classes.cpu()
+        fg = (gt_classes != -1) & (gt_classes >= 0) & (gt_classes < self.num_classes)
+        gt_classes = gt_classes[fg]
+        gt_class_names = [self.thing_classes[c] for c in gt_classes.tolist()]
+        gt_poses = gts.gt_poses.cpu()[fg]
+        gt_boxes3D = gts.gt_boxes3D.cpu()[fg]                           # projected 2D centre, depth, w, h, l, 3D centre
+        gt_z = gt_boxes3D[:, 2]                                         # mirrored / scaled by the loader: back-project the centre
+        gt_center_3D = torch.stack((gt_z * (gt_boxes3D[:, 0] - sx) / fx, gt_z * (gt_boxes3D[:, 1] - sy) / fy, gt_z)).T
+        gt_xyzwhl = torch.cat((gt_center_3D, gt_boxes3D[:, 3:6]), dim=1)
+        gt_meshes = [math_util.mesh_cuboid(gt_xyzwhl[i], gt_poses[i], torch.tensor(util.get_color(i)) / 255.0) for i in range(len(gt_xyzwhl))]
+
+        pred_xyzwhl = torch.cat((instances_i.pred_center_cam, instances_i.pred_dimensions), dim=1).cpu()
+        pred_pose = instances_i.pred_pose.cpu()
+        pred_class_names = ["{} {:.2f}".format(self.thing_classes[c], s)
+                            for c, s in zip(instances_i.pred_classes.tolist(), instances_i.scores.tolist())]
+        pred_meshes = [math_util.mesh_cuboid(pred_xyzwhl[i], pred_pose[i], torch.tensor(util.get_color(i)) / 255.0) for i in range(len(pred_xyzwhl))]
+        if pred_meshes:                                                 # (draw_scene_view concatenates the meshes: none, nothing to draw)
+            img_3DPR = vis.draw_scene_view(img_3DPR, K_scaled, pred_meshes, text=pred_class_names, mode="front", blend_weight=0.0,
+                                           blend_weight_overlay=0.85)
+        if gt_meshes:
+            img_3DGT = vis.draw_scene_view(img_3DGT, K_scaled, gt_meshes, text=gt_class_names, mode="front", blend_weight=0.0,
+                                           blend_weight_overlay=0.85)
+        vis_img_3d = np.concatenate((img_3DGT, img_3DPR), axis=1)[:, :, [2, 1, 0]]
+        storage.put_image("Left: GT 3D cuboids; Right: Predicted 3D cuboids", np.ascontiguousarray(vis_img_3d.astype(np.uint8).transpose(2, 0, 1)))
 
     def _all_packed(self):
         return getattr(self.proposal_generator, "accepts_packed", False) and getattr(self.roi_heads, "accepts_packed", False)

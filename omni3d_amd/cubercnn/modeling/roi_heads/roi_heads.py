@@ -122,6 +122,8 @@ class ROIHeads3D(nn.Module):
     accepts_packed = True     # forward() also takes the ground truth pre-packed on the device (RCNN3D.prepack)
     replayable_inference = True    # its eval pass is inference.roi_heads_inference_device + one host sync (meta_arch/infer_replay.py)
     pool_cut = None           # solver/graphed.py: callable applied to the pooled (box, cube) features = a backward stage boundary
+    want_predictions = False  # set by RCNN3D for one drawing iteration (VIS_PERIOD): the training branch also returns its predictions
+    max_vis_predictions = 20  # rcnn3d.py:131, 214
     @configurable
     def __init__(self, *, num_classes, batch_size_per_image, positive_fraction, proposal_iou_threshold, proposal_append_gt,
                  box_in_features, box_pooler, box_head, box_predictor, ignore_thresh, cube_head, cube_pooler, loss_w_3d,
@@ -258,6 +260,8 @@ class ROIHeads3D(nn.Module):
                     x_box, x_cube = self.pool_cut((x_box, x_cube))
             losses, cube_boxes = self._forward_box_train(feats, sboxes, scls, sgt, packed, x_box)
             losses.update(self._forward_cube_train(feats, cube_boxes, scls, sgt, packed, x_cube))
+            if self.want_predictions:
+                return self._train_predictions(images.image_sizes, sboxes, counts, packed), losses
             return [], losses
         from .inference import roi_heads_inference
         return roi_heads_inference(self, images, feats, proposals, packed), {}
@@ -284,6 +288,8 @@ class ROIHeads3D(nn.Module):
         if x is None:
             x = self.box_pooler(feats, rois, self._batch_index(B, S, rois.device))
         pred = self.box_predictor(self.box_head(x))
+        if self.want_predictions:
+            self.__dict__["_vis_pred"] = pred.detach()
         losses = self.box_predictor.losses(pred, scls.reshape(-1), rois, packed, self._gt_rows(sgt).reshape(-1))
         if self.train_on_pred_boxes:      # roi_heads.py:283-289: the 3D head trains on the (detached) 2D predictions of the GT classes
             with torch.no_grad():
@@ -321,6 +327,8 @@ class ROIHeads3D(nn.Module):
         if x is None:
             x = self.cube_pooler(feats, self.scale_proposals(rois), bidx)
         head = self.cube_head(x)
+        if self.want_predictions:
+            self.__dict__["_vis_cube"] = (head.detach(), rois, cls, bidx)
         priors = self.priors_dims_per_cat.detach().reshape(self.num_classes, 2, 3).contiguous()
         w3 = self.loss_w_3d
         # what each reduced term is multiplied by on the way into the loss dict; 0 = not a loss in this configuration
@@ -336,6 +344,53 @@ class ROIHeads3D(nn.Module):
         keep = [k for k, name in enumerate(order) if coef[k] != 0.0 or name in ("loss_xy", "loss_z", "loss_pose")]
         names = tuple("Cube/" + order[k] for k in keep)
         return HF.LossDict({n: vec[k] for n, k in zip(names, keep)}, vectors=[(vec, names)])
+
+    # ---- the training-mode return value of roi_heads.py:207-225, 771-822, reduced to what rcnn3d.py:207-214 keeps of it ----
+    @torch.no_grad()
+    def _train_predictions(self, image_sizes, sboxes, counts, packed):
+        """list[Instances], one per image: the at most `max_vis_predictions` foreground rows that survive the class-agnostic NMS of
+        `visualize_training` on their GT-class boxes in order of cube confidence (one launch of csrc/train_vis.hip), with the fields
+        the reference's training branch returns.  The 2D boxes are decoded from the sampler's own proposals (the reference sets
+        `pred_boxes` before TRAIN_ON_PRED_BOXES replaces them); the 3D fields come from `det.cube_decode` over the boxes the cube head
+        trained on.  Reads only: detached tensors, nothing kept after the call."""
+        pred = self.__dict__.pop("_vis_pred").contiguous()
+        head, rois, cls, bidx = self.__dict__.pop("_vis_cube")
+        head = head.contiguous()
+        K, B = self.num_classes, counts.shape[0]
+        Fc = cls.numel() // B
+        pre = self.__dict__.get("_cube_prefix")
+        if pre is not None and pre[0] is sboxes and pre[1][0] is not None and pre[1][0].shape[1] == Fc:
+            prop = pre[1][0]
+        else:
+            prop = sboxes[:, :Fc].contiguous()
+        bins = max(self.cluster_bins, 1)
+        uncert_off = (det.cube_head_width(self.cube_mode, bins) - 1) * K if self.use_confidence > 0 else -1
+        nfg = counts[:, 0].contiguous()
+        keep_row, keep_count, keep_box, keep_score = det.train_vis_pick(
+            pred, head, uncert_off, prop, cls.view(B, Fc), nfg, K, self.box_predictor.box2box_weights,
+            iou_thr=self.box_predictor.test_nms_thresh, max_keep=self.max_vis_predictions)
+        priors = self.priors_dims_per_cat.detach().reshape(K, 2, 3).contiguous()
+        n_fg, n_keep = nfg.tolist(), keep_count.tolist()
+        out = []
+        for b in range(B):
+            n, k, o = min(max(n_fg[b], 0), Fc), n_keep[b], b * Fc
+            if n > 0:
+                cube3d, pose, verts = det.cube_decode(head[o:o + n], K, rois[o:o + n], cls[o:o + n], bidx[o:o + n], packed.Ks, packed.v2r,
+                                                      packed.ratio, priors, self.cube_mode, self.clusters())
+            else:
+                cube3d, pose, verts = head.new_zeros((0, 9)), head.new_zeros((0, 3, 3)), head.new_zeros((0, 8, 3))
+            rows = keep_row[b, :k].long()
+            inst = Instances(tuple(image_sizes[b]))
+            inst.pred_boxes = Boxes(keep_box[b, :k])
+            inst.scores = keep_score[b, :k]
+            inst.pred_classes = cls[o:o + n][rows].long()
+            inst.pred_bbox3D = verts[rows]
+            inst.pred_center_cam = cube3d[rows, :3]
+            inst.pred_center_2D = cube3d[rows, 6:8]
+            inst.pred_dimensions = cube3d[rows, 3:6]
+            inst.pred_pose = pose[rows]
+            out.append(inst)
+        return out
 
     def flush_logs(self, storage):
         self.box_predictor.flush_logs(storage)

@@ -153,6 +153,7 @@ class AutoReplay:
         self.evictions = 0
         self.recaptures = 0                      # captures of a bucket that had been captured (and evicted) before
         self.eager_iters = 0                     # training iterations this object sent down the eager path
+        self.drawing_iters = 0                   # ... and those that ran eager launches because VIS_PERIOD asked for drawings
         self.ever = set()                        # buckets captured at least once
         self.level = 0                           # thrash-guard level (see GUARD_WINDOW)
         self.window = []                         # last GUARD_WINDOW iterations: True = replay of a cached bucket, False = miss
@@ -203,7 +204,7 @@ class AutoReplay:
     def stats(self):
         """what the cache did so far (bench.py `dropin_loop_multiscale`, tests)"""
         n = max(self.iters, 1)
-        return {"iterations": self.iters, "replays": self.replays, "eager": self.eager_iters, "captures": self.captures, "recaptures": self.recaptures,
+        return {"iterations": self.iters, "replays": self.replays, "eager": self.eager_iters, "drawing": self.drawing_iters, "captures": self.captures, "recaptures": self.recaptures,
                 "evictions": self.evictions, "buckets_seen": len(self.counts) + len([k for k in self.ever if k not in self.counts]),
                 "buckets_cached": len(self.cache), "hit_rate": self.replays / n, "guard_level": self.level, "bucket_granularity": self.granularity,
                 "cached_gb": round(sum(e.get("bytes", 0) for e in self.cache.values()) / (1 << 30), 2)}
@@ -274,6 +275,12 @@ class AutoReplay:
         if not ENABLED or self.failed is not None or not self.model.training:
             return None
         self._raise_if_poisoned()
+        from ...d2.events import is_vis_iteration
+        if is_vis_iteration(getattr(self.model, "vis_period", 0)):
+            # a drawing iteration (VIS_PERIOD): eager launches, where the training-mode predictions and every tensor the drawing reads
+            # are alive; the captured steps, their pools and the bucket bookkeeping are left alone
+            self.drawing_iters += 1
+            return None
         self._check_bn_mode()
         sig = self.signature(batched_inputs)
         entry = self.cache.get(sig)

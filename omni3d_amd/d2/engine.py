@@ -51,11 +51,37 @@ class JSONWriter:
         self._fh.close()
 
 
+class ImageWriter:
+    """The images of `EventStorage.put_image` (the training drawings of VIS_PERIOD) as JPEG files: entry k of the storage's
+    `_vis_data`, a (3, H, W) uint8 RGB array put at iteration `it`, becomes <output_dir>/vis_train/<it:07d>_<k>.jpg; the storage's images
+    are cleared afterwards, as detectron2's TensorboardXWriter does (tensorboard is not a dependency here).  Main process only."""
+
+    def __init__(self, output_dir):
+        self._dir = os.path.join(output_dir, "vis_train")
+
+    def write(self):
+        from . import comm
+        from .events import get_event_storage
+        st = get_event_storage()
+        if not comm.is_main_process() or not st._vis_data:
+            return
+        import numpy as np
+        from ..cubercnn.util import util
+        os.makedirs(self._dir, exist_ok=True)
+        for k, (_, img, it) in enumerate(st._vis_data):
+            img = np.asarray(img.cpu() if hasattr(img, "cpu") else img)
+            util.imwrite(img.transpose(1, 2, 0)[:, :, ::-1], os.path.join(self._dir, "%07d_%d.jpg" % (it, k)))      # imwrite takes BGR
+        st.clear_images()
+
+    def close(self):
+        pass
+
+
 def default_writers(output_dir, max_iter=None):
     if not output_dir:
         return []
     os.makedirs(output_dir, exist_ok=True)
-    return [JSONWriter(os.path.join(output_dir, "metrics.json"))]
+    return [JSONWriter(os.path.join(output_dir, "metrics.json")), ImageWriter(output_dir)]
 
 
 def _worker(local_rank, main_func, world, num_gpus_per_machine, machine_rank, dist_url, args):

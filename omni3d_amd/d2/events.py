@@ -14,6 +14,15 @@ def has_event_storage():
     return len(_CURRENT_STORAGE_STACK) > 0
 
 
+def is_vis_iteration(vis_period):
+    """the reference's condition for a drawing iteration (cubercnn/modeling/meta_arch/rcnn3d.py:69-71): VIS_PERIOD > 0 and the
+    storage's iteration a positive multiple of it; never outside an EventStorage.  RCNN3D and the captured step (AutoReplay) both ask here."""
+    if not vis_period or vis_period <= 0 or not _CURRENT_STORAGE_STACK:
+        return False
+    it = _CURRENT_STORAGE_STACK[-1].iter
+    return it > 0 and it % vis_period == 0
+
+
 class EventStorage:
     def __init__(self, start_iter=0):
         self._history = defaultdict(list)

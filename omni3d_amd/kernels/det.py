@@ -374,7 +374,29 @@ def box_decode_gt_class(pred, K, cls, prop, weights=(10.0, 10.0, 5.0, 5.0), scal
     return out
 
 
-CUBE_MODE_BASE = 0xDC0      # configs/Base.yaml: z direct, dims priors 'exp', 6d pose, allocentric, virtual depth, chamfer, confidence, joint
+def train_vis_pick(pred, head, uncert_off, rois, cls, nfg, K, weights=(10.0, 10.0, 5.0, 5.0), scale_clamp=4.135166556742356, iou_thr=0.5,
+                   max_keep=20):
+    """The rows `RCNN3D.visualize_training` draws (rcnn3d.py:207-214 on the training-mode predictions of roi_heads.py:276-281, 782-805):
+    pred (B*S, ldp) box-head output, head (B*Fc, ldh) cube-head output with its uncertainty block at column uncert_off (-1: no
+    confidence, score 1), rois (B, Fc, 4) / cls (B, Fc) int32 / nfg (B,) int32 the sampler's cube prefix and foreground counts
+    -> keep_row (B, max_keep) int32 (-1 beyond the count), keep_count (B,) int32, keep_box (B, max_keep, 4), keep_score (B, max_keep)"""
+    L = _dev(pred, head, rois, cls, nfg)
+    B, Fc = cls.shape
+    if B == 0 or pred.shape[0] % B or head.shape[0] != B * Fc or tuple(rois.shape) != (B, Fc, 4) or tuple(nfg.shape) != (B,):
+        raise ValueError(f"train_vis_pick: pred {tuple(pred.shape)}, head {tuple(head.shape)}, rois {tuple(rois.shape)}, nfg "
+                         f"{tuple(nfg.shape)} do not describe {B} images of {Fc} cube rows")
+    S, ldp, ldh = pred.shape[0] // B, pred.shape[1], head.shape[1]
+    keep_row = _empty((B, max_keep), torch.int32, pred)
+    keep_count = _empty((B,), torch.int32, pred)
+    keep_box = _empty((B, max_keep, 4), torch.float32, pred)
+    keep_score = _empty((B, max_keep), torch.float32, pred)
+    L.call("omni_train_vis_pick", _lib.ptr(pred), ldp, _lib.ptr(head), ldh, int(uncert_off), _lib.ptr(rois), _lib.ptr(cls), _lib.ptr(nfg),
+           B, S, Fc, int(K), *[float(w) for w in weights], float(scale_clamp), float(iou_thr), int(max_keep), _lib.ptr(keep_row),
+           _lib.ptr(keep_count), _lib.ptr(keep_box), _lib.ptr(keep_score), _lib.stream_of(pred))
+    return keep_row, keep_count, keep_box, keep_score
+
+
+CUBE_MODE_BASE = 0xDC0     # configs/Base.yaml: z direct, dims priors 'exp', 6d pose, allocentric, virtual depth, chamfer, confidence, joint
 _Z_TYPES = {"direct": 0, "sigmoid": 1, "log": 2, "clusters": 3}
 _POSE_TYPES = {"6d": 0, "quaternion": 1, "euler": 2}
 POSE_WIDTH = {"6d": 6, "quaternion": 4, "euler": 3}

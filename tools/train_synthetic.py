@@ -6,7 +6,10 @@ scalars, PeriodicCheckpointerOnlyOne.  Nothing in this loop knows about graphs: 
 `model(data)` switches to the staged hipGraph replay by itself (cubercnn/solver/autoreplay.py; OMNI_AUTO_REPLAY=0 keeps eager
 launches).
 
-    python tools/train_synthetic.py --iters 60 [--config cubercnn_ResNet34_FPN.yaml] [--out /tmp/run]
+    python tools/train_synthetic.py --iters 60 [--config cubercnn_ResNet34_FPN.yaml] [--out /tmp/run] [--vis-period 20]
+
+--vis-period N (with --out) sets VIS_PERIOD: every N-th iteration runs eager launches and the two training drawings of
+`RCNN3D.visualize_training` are written to <out>/vis_train/.
 """
 import argparse
 import os
@@ -49,12 +52,13 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--out", default="")
+    ap.add_argument("--vis-period", type=int, default=0)
     args = ap.parse_args()
     from omni3d_amd import synthetic
     cfg = get_cfg()
     get_cfg_defaults(cfg)
     cfg.merge_from_file(os.path.join(ROOT, "configs", args.config))
-    cfg.merge_from_list(["MODEL.WEIGHTS", "synthetic://random-init", "VIS_PERIOD", 0, "SOLVER.IMS_PER_BATCH", args.batch,
+    cfg.merge_from_list(["MODEL.WEIGHTS", "synthetic://random-init", "VIS_PERIOD", args.vis_period, "SOLVER.IMS_PER_BATCH", args.batch,
                          "SOLVER.BASE_LR", 0.12 * args.batch / 192.0, "SOLVER.MAX_ITER", args.iters,
                          "SOLVER.STEPS", (int(0.6 * args.iters), int(0.8 * args.iters)), "SOLVER.WARMUP_ITERS", max(args.iters // 10, 1),
                          "SOLVER.CHECKPOINT_PERIOD", max(args.iters // 2, 1), "MODEL.DEVICE", os.environ.get("OMNI_DEVICE", "cuda")])
@@ -70,6 +74,12 @@ def main():
         print("built on the CPU (dry run: the kernels need the GPU)")
         return
     from cubercnn.solver import StepGuard
+    from omni3d_amd.d2.data import MetadataCatalog
+    from omni3d_amd.d2.engine import default_writers
+    meta = MetadataCatalog.get("omni3d_model")
+    if meta.get("thing_classes") is None:                # the labels of the drawings; the synthetic batches have no dataset behind them
+        meta.thing_classes = ["class%02d" % c for c in range(cfg.MODEL.ROI_HEADS.NUM_CLASSES)]
+    writers = default_writers(args.out) if cfg.VIS_PERIOD > 0 else []
     guard = None
     pool = [synthetic.make_batch(args.batch, args.size, args.size, num_gt=8, seed=s, priors=priors) for s in range(4)]
     t0 = time.perf_counter()
@@ -95,6 +105,9 @@ def main():
                 print(f"!! restart requested at iteration {it} (exploding loss) !!")   # :272-285 returns False here
                 return False
             scheduler.step()
+            if storage._vis_data:
+                for w in writers:
+                    w.write()
             if not skipped:
                 ckpt.step(it)
             if it % 10 == 0 or it == cfg.SOLVER.MAX_ITER - 1:
