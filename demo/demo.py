@@ -1,5 +1,6 @@
 """Run a Cube R-CNN model on a folder of images and draw the predicted 3D boxes (reference demo/demo.py): for every image
-`<name>_boxes.jpg` (the boxes over the image), `<name>_novel.jpg` (the scene from a second viewpoint) and `<name>.json` (the kept
+`<name>_boxes.jpg` (the boxes over the image), `<name>_novel.jpg` (the scene from a second viewpoint, on the reference's ground
+grid with --ground-grid) and `<name>.json` (the kept
 detections: class name, score, center_cam, dimensions, pose, bbox3D) are written to cfg.OUTPUT_DIR.  Without a detection above the
 threshold the untouched image is written as `<name>_boxes.jpg` only.
 
@@ -76,7 +77,7 @@ def do_test(args, cfg, model):
 
         if len(meshes) > 0:
             im_drawn_rgb, im_topdown, _ = vis.draw_scene_view(im, K, meshes, text=meshes_text, scale=im.shape[0], blend_weight=0.5,
-                                                              blend_weight_overlay=0.85)
+                                                              blend_weight_overlay=0.85, ground_grid=getattr(args, "ground_grid", False))
             util.imwrite(im_drawn_rgb, os.path.join(output_dir, im_name + "_boxes.jpg"))
             util.imwrite(im_topdown, os.path.join(output_dir, im_name + "_novel.jpg"))
         else:
@@ -115,6 +116,7 @@ def argument_parser():
     parser.add_argument("--focal-length", type=float, default=0, help="focal length for image inputs (in px)")
     parser.add_argument("--principal-point", type=float, default=[], nargs=2, help="principal point for image inputs (in px)")
     parser.add_argument("--threshold", type=float, default=0.25, help="threshold on score for visualizing")
+    parser.add_argument("--ground-grid", default=False, action="store_true", help="draw the ground plane and its grid in the novel view")
     parser.add_argument("--display", default=False, action="store_true", help="accepted and ignored (logged)")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="'KEY VALUE' pairs that override the config")
     return parser

@@ -734,6 +734,30 @@ int omni_scene_compose(const int* index, const int* face, const float* R, const 
  * of image (3,H,W) uint8 whose centre lies within thickness / 2 of a segment takes (c0, c1, c2) (planes 0..2, rounded, clamped to
  * 0..255) of the LAST such segment of the list; the others are not touched.  A segment of length zero draws a disc. */
 int omni_draw_segments(const float* seg, int S, unsigned char* image, int H, int W, void* stream);
+/* Area fills blended in list order (csrc/shapes.hip): `draw_transparent_polygon`, `cv2.circle` and `draw_transparent_square`
+ * (vis.py:540-568, 684-703) as a gather.  shape (S,13) = [kind, x0, y0, x1, y1, x2, y2, x3, y3, blend, c0, c1, c2] on image
+ * (3,H,W) uint8.  kind 0: the quadrilateral (x0,y0) .. (x3,y3), vertices in order; a pixel is inside by the even-odd rule at its
+ * centre (x + 0.5, y + 0.5), so a folded quadrilateral leaves its doubly covered part out.  kind 1: the ring with centre (x0,y0),
+ * outer radius x1 and inner radius y1 (0: a disc): inside when inner <= distance of the centre <= outer.  Every pixel walks the
+ * list in order; a covering shape replaces each plane's value v by floor(v * blend + (1 - blend) * c), evaluated in double with one
+ * rounding per operation (numpy's float64 expression stored into uint8; clamped to 0..255), later shapes on the result of earlier
+ * ones.  Pixels no shape covers are not touched.  A row with a value that is not finite, another kind or a negative outer radius
+ * covers nothing; S = 0 launches nothing.  No atomics: two runs give the same bits. */
+int omni_fill_shapes(const float* shape, int S, unsigned char* image, int H, int W, void* stream);
+/* The ground plane of the novel view (vis.py:389-490; csrc/shapes.hip), per pixel and without a point mesh.  image (3,H,W) uint8;
+ * index (H,W) int32 or NULL: pixels with index >= 0 (omni_cuboid_depth: a box is seen there) keep their bytes, every other pixel
+ * is written.  K (9); the scene reaches view space by the rigid motion p' = A p + t (A (9) a rotation, t (3)); the plane is y = y0
+ * in scene coordinates; near > 0; thickness >= 0 in pixels; colours as 0xRRGGBB (plane 0 takes RR).  The lines are the reference's:
+ * X = k for k = x_start .. x_end - 2 over Z in [z_start, z_end - 1], and Z = k for k = z_start .. z_end - 2 over X in [x_start,
+ * x_end - 1]; none when x_end - x_start < 2 or z_end - z_start < 2.  The ray through the pixel centre meets the plane at P = (X,
+ * y0, Z).  The pixel takes bg_rgb when the ray does not meet the plane in front of the camera (nothing is drawn above the
+ * horizon), when the view depth of P is below `near`, or when P lies outside the two spans; otherwise it takes line_rgb iff its
+ * centre is within thickness / 2 pixels of the image of a drawn line next to P (k = floor and floor + 1 of X and of Z), bg_rgb if
+ * not.  So a line ends square at the bounds and at `near` (the reference clamps depth to 0.25 and projects the clamped point,
+ * which bends the line) and its end points are not truncated to integers.  |bounds| <= 2^24. */
+int omni_ground_grid(unsigned char* image, const int* index, const float* K, const float* A, const float* t, float y0, int x_start,
+                     int x_end, int z_start, int z_end, float near, float thickness, int bg_rgb, int line_rgb, int H, int W,
+                     void* stream);
 
 /* The 3D error report of `visualize_from_instances` (cubercnn/vis/vis.py:95-171, csrc/vis_errors.hip) for a whole dataset in one
  * call.  Rows are ragged by image: detections of image i are rows dt_off[i] .. dt_off[i + 1] - 1, ground truths gt_off[i] ..

@@ -78,3 +78,46 @@ def draw_segments(image, segments):
     L = _lib.check_device(image, segments)
     L.call("omni_draw_segments", _lib.ptr(segments), S, _lib.ptr(image), H, W, _lib.stream_of(image))
     return image
+
+
+def fill_shapes(image, shapes):
+    """In place on image (3,H,W) uint8: shapes (S,13) float32 [kind, x0, y0, x1, y1, x2, y2, x3, y3, blend, c0, c1, c2] in paint order.
+    kind 0: the quadrilateral of the four vertices (even-odd rule at the pixel centre); kind 1: the ring around (x0, y0) with outer
+    radius x1 and inner radius y1.  A covered pixel's value v becomes floor(v * blend + (1 - blend) * c) in float64, shape after
+    shape; rows that are not finite cover nothing."""
+    image = _image(image)
+    H, W = image.shape[1:]
+    S = shapes.shape[0]
+    shapes = _f32(shapes, (S, 13), "shapes")
+    L = _lib.check_device(image, shapes)
+    L.call("omni_fill_shapes", _lib.ptr(shapes), S, _lib.ptr(image), H, W, _lib.stream_of(image))
+    return image
+
+
+def _rgb(color, name):
+    c = [int(v) for v in color]
+    if len(c) != 3 or min(c) < 0 or max(c) > 255:
+        raise ValueError(f"{name} must be three values in 0..255")
+    return (c[0] << 16) | (c[1] << 8) | c[2]
+
+
+def ground_grid(image, K, A, t, y0, bounds, index=None, near=0.25, thickness=1.0, bg_color=(225, 225, 225), line_color=(175, 175, 175)):
+    """In place on image (3,H,W) uint8: the plane y = y0 of the scene, seen through p' = A p + t (A a rotation, (3,3) or (9,)) and K,
+    with the grid lines X = k, k = x_start .. x_end - 2, and Z = k, k = z_start .. z_end - 2, of bounds = (x_start, x_end, z_start,
+    z_end), `thickness` pixels wide in `line_color` on `bg_color`.  Pixels with index (H,W) int32 >= 0 keep their bytes; all others
+    are written.  Plane points nearer than `near` or outside the bounds are background."""
+    image = _image(image)
+    H, W = image.shape[1:]
+    K, A, t = _f32(K.reshape(9), (9,), "K"), _f32(A.reshape(9), (9,), "A"), _f32(t.reshape(3), (3,), "t")
+    if index is not None:
+        if index.dtype != torch.int32 or tuple(index.shape) != (H, W):
+            raise ValueError("index must be int32 (H, W)")
+        index = index.contiguous()
+    x_start, x_end, z_start, z_end = (int(b) for b in bounds)
+    if not near > 0 or not thickness >= 0:
+        raise ValueError("near must be positive and thickness not negative")
+    L = _lib.check_device(image, index, K, A, t)
+    L.call("omni_ground_grid", _lib.ptr(image), _lib.ptr(index), _lib.ptr(K), _lib.ptr(A), _lib.ptr(t), float(y0), x_start, x_end,
+           z_start, z_end, float(near), float(thickness), _rgb(bg_color, "bg_color"), _rgb(line_color, "line_color"), H, W,
+           _lib.stream_of(image))
+    return image
