@@ -46,6 +46,32 @@ int omni_iou_box3d_pairs_algo(const float* boxes1, const float* boxes2, const in
 int omni_box3d_validity(const float* boxes, int N, float eps_coplanar, float eps_nonzero, int* valid,
                         int* counts, void* stream);
 
+/* Suppression of duplicate cuboids among the fixed (B, S) detection slots of the inference pass, by IoU3D and (optionally) across
+ * categories (csrc/iou_box3d.hip).  The reference has no such step: fast_rcnn_inference_single_image
+ * (cubercnn/modeling/roi_heads/fast_rcnn.py:57-143) suppresses per class and in 2D only; this stands for the `box3d_overlap` loop its
+ * users run on the host afterwards.
+ *   verts (B*S,8,3)   corner lists in the order of omni_iou_box3d; score (B*S); cls (B*S) int32; count (B) int32: image b uses the
+ *                     slots s < count[b] (clamped to [0, S]); the slots behind it are not read
+ *   iou_thr           a kept slot i removes every lower-ranked slot j with iou[b][i][j] > iou_thr (strict, as torchvision's nms)
+ *   class_agnostic    0: only pairs of equal class are compared (the others have IoU 0 here)
+ *   eps_coplanar, eps_nonzero   the validity test of omni_box3d_validity, taken per box
+ * Two launches.  (1) the self-overlap of every image: one lane screens each pair i < j (exact 0 when j >= count[b], the classes
+ * differ and class_agnostic == 0, either box is invalid, or the bounding spheres are disjoint), the others run the pair algorithm
+ * of omni_iou_box3d (32 lanes per pair, full-capacity lists); the value is written to iou[b][i][j] and iou[b][j][i], the diagonal
+ * is 0, every entry of iou (B,S,S) is written whatever the counts.  (2) one 256-thread workgroup per image ranks the slots by
+ * descending score (ties to the lower slot; bitonic network over 64-bit keys) and walks the ranking: a candidate that has not been
+ * removed is kept and removes the later candidates it overlaps by more than iou_thr.  A slot whose box is invalid (or has a
+ * non-finite vertex) or whose score is not finite is kept, never suppresses and is never suppressed.  Out:
+ *   keep (B,S) int32       1 for a kept slot, 0 for a removed one and for s >= count[b]
+ *   order (B,S) int32      the kept slots in ASCENDING slot order, then -1: gathering by it takes rows out and reorders nothing
+ *   new_count (B) int32    number of kept slots
+ *   overflow (1) int32     incremented when a pair exceeded the LDS triangle capacity, as in omni_iou_box3d (the caller zeroes it)
+ * No atomics in (2), no arrival order anywhere: two runs give the same bits.  S > 1024 (the LDS capacity of (2)) returns
+ * OMNI_ERR_ARG before any launch; B == 0 or S == 0 launches nothing. */
+int omni_nms3d(const float* verts, const float* score, const int* cls, const int* count, int B, int S, float iou_thr,
+               int class_agnostic, float eps_coplanar, float eps_nonzero, float* iou, int* keep, int* order, int* new_count,
+               int* overflow, void* stream);
+
 /* ------------------------------------------------- convolution / linear (fp32 MFMA, NHWC) */
 
 /* torch.nn.Conv2d forward as used by the DLA-34 bottom-up (cubercnn/modeling/backbone/dla.py:

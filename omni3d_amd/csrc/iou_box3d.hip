@@ -701,3 +701,241 @@ int omni_box3d_validity(const float* boxes, int N, float eps_coplanar, float eps
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// omni_nms3d -- suppression of duplicate cuboids at inference (the reference has no such step: `fast_rcnn_inference` suppresses per
+// class and in 2D only).  Two launches over the fixed (B, S) slots of the inference pass:
+//   nms3d_iou_kernel   the block-diagonal self-overlap: for every image the IoU3D of its slot pairs i < j, mirrored into a full
+//                      (S, S) matrix.  The pair index is turned into (i, j) by arithmetic; a lane screens its pair out (exact 0) when
+//                      j lies behind the image's count, the classes differ (class-specific mode), a box fails the validity test, or
+//                      the bounding spheres are disjoint; the survivors go through iou_pair_body, 32 lanes per pair over the
+//                      full-capacity lists (one launch, no retry pass).  Two launches leave no place for a device-wide per-box pass,
+//                      so every wave takes the validity of its image's boxes ONCE, as ballots into LDS, before its first pair.
+//   nms3d_pick_kernel  one 256-thread workgroup per image: bitonic sort of 64-bit keys [~ordered score bits | slot] (the network of
+//                      csrc/train_vis.hip), a walk down the ranking in which a live candidate removes the later candidates whose
+//                      IoU3D with it is > iou_thr (a candidate whose row holds no such value is passed over without a load or a
+//                      barrier), then an ordered compaction of the surviving slots by wave ballots.  No atomics.
+// A slot whose box is invalid (or has a non-finite vertex) or whose score is not finite is kept, never suppresses and is never
+// suppressed: it sorts behind every ranked slot and the walk ends at the first such key.
+namespace {
+
+constexpr int NMS3D_MAXS = 1024;                     // slots per image the LDS arrays of the pick kernel hold
+constexpr unsigned NMS3D_UNRANKED = 0xFFFFFFFFu;     // high key word of padding and of the slots that take no part in the suppression
+
+__device__ __forceinline__ bool nms3d_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// the test of box3d_validity_kernel for one box (the same operations in the same order), false for a non-finite vertex
+__device__ __forceinline__ bool nms3d_box_valid(const float* __restrict__ B, float eps_coplanar, float eps_nonzero) {
+    bool finite = true;
+    for (int k = 0; k < 24; ++k) finite = finite && nms3d_finite(B[k]);
+    float acc = 0.f;
+    for (int p = 0; p < 6; ++p) {
+        V3 q[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = ldv(B + 3 * c_box_planes[p][k]);
+        V3 e0 = vsub(q[1], q[0]), e1 = vsub(q[2], q[0]);
+        e0 = vdiv(e0, fmaxf(vnorm(e0), 1e-12f));
+        e1 = vdiv(e1, fmaxf(vnorm(e1), 1e-12f));
+        V3 n = vcross(e0, e1);
+        n = vdiv(n, fmaxf(vnorm(n), 1e-12f));
+        acc += vdot(vsub(q[3], q[0]), n);
+    }
+    const bool coplanar = fabsf(acc) < eps_coplanar;
+    bool nonzero = true;
+    for (int t = 0; t < 12; ++t) {
+        V3 a = ldv(B + 3 * c_box_tris[t][0]), b = ldv(B + 3 * c_box_tris[t][1]), c = ldv(B + 3 * c_box_tris[t][2]);
+        float area = vnorm(vcross(vsub(b, a), vsub(c, a))) / 2.0f;
+        if (!(area > eps_nonzero)) nonzero = false;
+    }
+    return finite && coplanar && nonzero;
+}
+
+// pair q of the S (S - 1) / 2 pairs i < j of one image, rows of the upper triangle one after another: row i starts at
+// i (2S - 1 - i) / 2.  The float root is exact to a unit for S <= 1024 ((2S - 1)^2 and 8q are integers below 2^24); the two loops
+// settle the last unit.
+__device__ __forceinline__ void nms3d_pair(int q, int S, int& i, int& j) {
+    const float t = (float)(2 * S - 1);
+    int r = (int)((t - sqrtf(t * t - 8.0f * (float)q)) * 0.5f);
+    r = r < 0 ? 0 : (r > S - 2 ? S - 2 : r);
+    while (r > 0 && r * (2 * S - 1 - r) / 2 > q) --r;
+    while ((r + 1) * (2 * S - 2 - r) / 2 <= q) ++r;
+    i = r;
+    j = q - r * (2 * S - 1 - r) / 2 + r + 1;
+}
+
+template <int SUB, int CAPT>
+__global__ void __launch_bounds__(64) OMNI_WAVES_PER_EU(4) nms3d_iou_kernel(
+    const float* __restrict__ verts, const int* __restrict__ cls, const int* __restrict__ count, int S, int class_agnostic,
+    float eps_coplanar, float eps_nonzero, float* __restrict__ iou_out, int* __restrict__ overflow, int chunk) {
+    constexpr int G = 64 / SUB;
+    __shared__ PairLds<CAPT> Lall[G];
+    __shared__ unsigned long long s_valid[NMS3D_MAXS / 64];      // bit s: slot s is in use and its box is valid
+    const int lane = threadIdx.x, g = lane / SUB, sl = lane % SUB;
+    const int b = blockIdx.y;
+    int n = count[b];
+    n = n < 0 ? 0 : (n > S ? S : n);
+    const float* V = verts + (size_t)b * S * 24;
+    const int* C = cls + (size_t)b * S;
+    float* O = iou_out + (size_t)b * S * S;
+    for (int s0 = 0; s0 < S; s0 += 64) {
+        const int s = s0 + lane;
+        const unsigned long long m = __ballot(s < n && nms3d_box_valid(V + (size_t)s * 24, eps_coplanar, eps_nonzero));
+        if (lane == 0) s_valid[s0 >> 6] = m;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0)
+        for (int s = lane; s < S; s += 64) O[(size_t)s * S + s] = 0.f;
+    const int P = S * (S - 1) / 2;
+    for (int c0 = blockIdx.x * chunk; c0 < P; c0 += gridDim.x * chunk) {
+        const int q = c0 + lane;
+        int ia = 0, ib = 0;
+        bool live = false;
+        if (lane < chunk && q < P) {
+            nms3d_pair(q, S, ia, ib);
+            live = ib < n && (class_agnostic != 0 || C[ia] == C[ib]) && ((s_valid[ia >> 6] >> (ia & 63)) & 1ull) != 0ull &&
+                   ((s_valid[ib >> 6] >> (ib & 63)) & 1ull) != 0ull && !spheres_disjoint(V + (size_t)ia * 24, V + (size_t)ib * 24);
+            if (!live) { O[(size_t)ia * S + ib] = 0.f; O[(size_t)ib * S + ia] = 0.f; }
+        }
+        unsigned long long todo = __ballot(live);
+        while (todo != 0ull) {
+            // sub-group g takes the (g+1)-th lowest survivor of this round
+            int j = -1;
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                const int f = todo != 0ull ? __ffsll(todo) - 1 : -1;
+                if (todo != 0ull) todo &= todo - 1ull;
+                if (k == g) j = f;
+            }
+            const bool act = j >= 0;
+            const int src = act ? j : 0;
+            const int pa = __shfl(ia, src, 64), pb = __shfl(ib, src, 64);
+            float vol, iou;
+            bool over;
+            iou_pair_body<SUB, CAPT>(Lall[g], act, V + (size_t)pa * 24, V + (size_t)pb * 24, lane, vol, iou, over);
+            if (act && sl == 0) {
+                O[(size_t)pa * S + pb] = iou;
+                O[(size_t)pb * S + pa] = iou;
+                if (over && overflow) atomicAdd(overflow, 1);
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) nms3d_pick_kernel(const float* __restrict__ verts, const float* __restrict__ score,
+                                                         const int* __restrict__ count, int S, float iou_thr, float eps_coplanar,
+                                                         float eps_nonzero, const float* __restrict__ iou, int* __restrict__ keep,
+                                                         int* __restrict__ order, int* __restrict__ new_count) {
+    __shared__ unsigned long long s_key[NMS3D_MAXS];      // sorted: [~ordered score bits | slot]
+    __shared__ unsigned char s_dead[NMS3D_MAXS];          // by sorted position
+    __shared__ unsigned char s_keep[NMS3D_MAXS];          // by slot
+    __shared__ unsigned char s_hot[NMS3D_MAXS];           // by slot: some IoU of its row exceeds the threshold
+    __shared__ int s_tot[NMS3D_MAXS / 64];                // kept slots per group of 64
+    const int t = threadIdx.x, b = blockIdx.x;
+    int n = count[b];
+    n = n < 0 ? 0 : (n > S ? S : n);
+    int NP = 1;
+    while (NP < n) NP <<= 1;
+    // ---- 1. keys ----
+    for (int j = t; j < NP; j += 256) {
+        unsigned hi = NMS3D_UNRANKED;
+        if (j < n) {
+            const float sc = score[(size_t)b * S + j] + 0.0f;      // (-0 -> +0)
+            if (nms3d_finite(sc) && nms3d_box_valid(verts + ((size_t)b * S + j) * 24, eps_coplanar, eps_nonzero)) {
+                // bit pattern that grows with the value, for either sign; a finite score never maps to 0, so ~u is never UNRANKED
+                const unsigned u = __float_as_uint(sc);
+                hi = ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+            }
+        }
+        s_key[j] = ((unsigned long long)hi << 32) | (unsigned)j;
+        s_dead[j] = 0;
+    }
+    for (int s = t; s < NMS3D_MAXS; s += 256) s_keep[s] = s < n ? 1 : 0;
+    // rows that can suppress anything at all, one row per wave and round, all loads independent: a step of the walk below costs a
+    // dependent global load and a barrier (0.7 us measured), and most rows of a real image overlap nothing
+    for (int r = t >> 6; r < n; r += 4) {
+        const float* R = iou + ((size_t)b * S + r) * S;
+        bool any = false;
+        for (int j = t & 63; j < n; j += 64) any = any || R[j] > iou_thr;
+        const unsigned long long m = __ballot(any);
+        if ((t & 63) == 0) s_hot[r] = m != 0ull ? 1 : 0;
+    }
+    __syncthreads();
+    // ---- 2. bitonic sort, ascending keys = descending score, ties to the lower slot ----
+    for (int k = 2; k <= NP; k <<= 1) {
+        for (int jj = k >> 1; jj > 0; jj >>= 1) {
+            for (int i = t; i < NP; i += 256) {
+                const int l = i ^ jj;
+                if (l > i) {
+                    const unsigned long long a = s_key[i], c = s_key[l];
+                    if ((a > c) == ((i & k) == 0)) { s_key[i] = c; s_key[l] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // ---- 3. the walk (every thread sees the same `cur` and the same flags, so the barriers are uniform) ----
+    for (int cur = 0; cur < n; ++cur) {
+        const unsigned long long key = s_key[cur];
+        if ((unsigned)(key >> 32) == NMS3D_UNRANKED) break;          // the unranked slots sort last
+        if (s_dead[cur] || !s_hot[(unsigned)key]) continue;          // (both written before the last barrier)
+        const float* R = iou + ((size_t)b * S + (unsigned)key) * S;
+        for (int j = cur + 1 + t; j < n; j += 256) {
+            const unsigned long long kj = s_key[j];
+            if ((unsigned)(kj >> 32) == NMS3D_UNRANKED) break;
+            if (!s_dead[j] && R[(unsigned)kj] > iou_thr) { s_dead[j] = 1; s_keep[(unsigned)kj] = 0; }
+        }
+        __syncthreads();
+    }
+    // ---- 4. the kept slots in ascending order: ballots per wave, totals per group of 64 slots ----
+    unsigned long long mine[NMS3D_MAXS / 256];
+#pragma unroll
+    for (int r = 0; r < NMS3D_MAXS / 256; ++r) {
+        const int s = r * 256 + t;
+        mine[r] = __ballot(s_keep[s] != 0);
+        if ((t & 63) == 0) s_tot[s >> 6] = __popcll(mine[r]);
+    }
+    __syncthreads();
+    int total = 0;
+    for (int k = 0; k < NMS3D_MAXS / 64; ++k) total += s_tot[k];
+#pragma unroll
+    for (int r = 0; r < NMS3D_MAXS / 256; ++r) {
+        const int s = r * 256 + t;
+        if (s < S) {
+            int pos = 0;
+            for (int k = 0; k < (s >> 6); ++k) pos += s_tot[k];
+            const int l = t & 63;
+            pos += __popcll(mine[r] & (l == 0 ? 0ull : (~0ull >> (64 - l))));
+            const bool kept = ((mine[r] >> l) & 1ull) != 0ull;
+            keep[(size_t)b * S + s] = kept ? 1 : 0;
+            if (kept) order[(size_t)b * S + pos] = s;
+            if (s >= total) order[(size_t)b * S + s] = -1;
+        }
+    }
+    if (t == 0) new_count[b] = total;
+}
+
+}  // namespace
+
+extern "C" {
+
+// verts (B*S, 8, 3), score (B*S), cls (B*S), count (B) -> iou (B, S, S) (every entry written), keep (B, S), order (B, S), new_count (B);
+// overflow (1) is incremented like that of omni_iou_box3d
+int omni_nms3d(const float* verts, const float* score, const int* cls, const int* count, int B, int S, float iou_thr,
+               int class_agnostic, float eps_coplanar, float eps_nonzero, float* iou, int* keep, int* order, int* new_count,
+               int* overflow, void* stream) {
+    if (B < 0 || S < 0 || S > NMS3D_MAXS || B > 65535) return OMNI_ERR_ARG;
+    if (B == 0 || S == 0) return OMNI_OK;
+    const long long P = (long long)S * (S - 1) / 2;
+    const int chunk = iou_chunk(P * B);
+    long long gx = (P + chunk - 1) / chunk, cap = (256 * 16 + B - 1) / B;
+    gx = gx > cap ? cap : gx;
+    gx = gx < 1 ? 1 : gx;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(nms3d_iou_kernel<32, CAP>), dim3((unsigned)gx, (unsigned)B), dim3(64), 0, st, verts, cls, count, S,
+                       class_agnostic, eps_coplanar, eps_nonzero, iou, overflow, chunk);
+    hipLaunchKernelGGL(nms3d_pick_kernel, dim3((unsigned)B), dim3(256), 0, st, verts, score, count, S, iou_thr, eps_coplanar,
+                       eps_nonzero, iou, keep, order, new_count);
+    return omni_launch_status();
+}
+
+}  // extern "C"

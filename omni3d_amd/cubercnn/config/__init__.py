@@ -1,1 +1,1 @@
-from .config import get_cfg_defaults  # noqa: F401
+from .config import add_nms3d_config, get_cfg_defaults  # noqa: F401

@@ -84,7 +84,10 @@ class InferReplay:
         g = AutoReplay._model_bucket(self.model)
         H = max(b["image"].shape[-2] for b in batch)
         W = max(b["image"].shape[-1] for b in batch)
-        return (len(batch), -(-H // g) * g, -(-W // g) * g)
+        sig = (len(batch), -(-H // g) * g, -(-W // g) * g)
+        # settings that change WHICH launches the pass consists of: a pass captured under one is never replayed under another
+        thr = getattr(self.model.roi_heads, "nms3d_thresh", None)
+        return sig if thr is None else sig + (("nms3d", float(thr), bool(self.model.roi_heads.nms3d_class_agnostic)),)
 
     def _digest(self):
         """changes whenever a captured pass could be stale: a write torch knows about (`_version`), one it cannot see (PARAM_EPOCH:

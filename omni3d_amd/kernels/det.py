@@ -396,6 +396,34 @@ def train_vis_pick(pred, head, uncert_off, rois, cls, nfg, K, weights=(10.0, 10.
     return keep_row, keep_count, keep_box, keep_score
 
 
+def nms3d(verts, scores, cls, count, iou_thr, class_agnostic=True, eps_coplanar=1e-4, eps_nonzero=1e-8):
+    """Greedy suppression of duplicate cuboids among the fixed detection slots (csrc/iou_box3d.hip, omni_nms3d): verts (B*S, 8, 3)
+    float32, scores (B*S,) float32, cls (B, S) or (B*S,) int32, count (B,) int32 -> keep (B, S) int32, order (B, S) int32 (the kept
+    slots in ascending order, then -1), new_count (B,) int32, iou (B, S, S) float32 (the IoU3D of the compared pairs, 0 elsewhere),
+    overflow (1,) int32.  Two launches, no host synchronisation."""
+    if count.dim() != 1 or count.dtype != torch.int32:
+        raise ValueError(f"nms3d: count must be int32 of shape (B,), got {count.dtype} {tuple(count.shape)}")
+    B = count.shape[0]
+    if verts.dim() != 3 or tuple(verts.shape[1:]) != (8, 3) or verts.dtype != torch.float32 or (B and verts.shape[0] % B) or (not B and verts.shape[0]):
+        raise ValueError(f"nms3d: verts must be float32 of shape (B*S, 8, 3) for B = {B}, got {verts.dtype} {tuple(verts.shape)}")
+    N = verts.shape[0]
+    S = N // B if B else 0
+    if scores.dtype != torch.float32 or tuple(scores.shape) != (N,):
+        raise ValueError(f"nms3d: scores must be float32 of shape ({N},), got {scores.dtype} {tuple(scores.shape)}")
+    if cls.dtype != torch.int32 or cls.numel() != N or tuple(cls.shape) not in ((N,), (B, S)):
+        raise ValueError(f"nms3d: cls must be int32 of shape ({B}, {S}) or ({N},), got {cls.dtype} {tuple(cls.shape)}")
+    L = _dev(verts, scores, cls, count)
+    iou = _empty((B, S, S), torch.float32, verts)
+    keep = _empty((B, S), torch.int32, verts)
+    order = _empty((B, S), torch.int32, verts)
+    new_count = _empty((B,), torch.int32, verts)
+    overflow = torch.zeros(1, dtype=torch.int32, device=verts.device)      # a counter the kernel adds to
+    L.call("omni_nms3d", _lib.ptr(verts), _lib.ptr(scores), _lib.ptr(cls), _lib.ptr(count), B, S, float(iou_thr), int(bool(class_agnostic)),
+           float(eps_coplanar), float(eps_nonzero), _lib.ptr(iou), _lib.ptr(keep), _lib.ptr(order), _lib.ptr(new_count), _lib.ptr(overflow),
+           _lib.stream_of(verts))
+    return keep, order, new_count, iou, overflow
+
+
 CUBE_MODE_BASE = 0xDC0     # configs/Base.yaml: z direct, dims priors 'exp', 6d pose, allocentric, virtual depth, chamfer, confidence, joint
 _Z_TYPES = {"direct": 0, "sigmoid": 1, "log": 2, "clusters": 3}
 _POSE_TYPES = {"6d": 0, "quaternion": 1, "euler": 2}
