@@ -72,6 +72,29 @@ int omni_nms3d(const float* verts, const float* score, const int* cls, const int
                int class_agnostic, float eps_coplanar, float eps_nonzero, float* iou, int* keep, int* order, int* new_count,
                int* overflow, void* stream);
 
+/* IoU in the bird's-eye view (csrc/bev_iou.hip): the overlap of the cuboids' footprints on the ground plane, the matching criterion
+ * of AP-BEV.  The reference has no counterpart: it EXTENDS `box3d_overlap` / omni_iou_box3d_pairs with a third kind of overlap next
+ * to the 2D and 3D ones of Omni3Deval.computeIoU (omni3d_evaluation.py:1359-1431).
+ *
+ * omni_bev_footprint: verts (N,8,3) corner lists in any order; e1, e2: an orthonormal basis of the plane orthogonal to the up
+ * vector (derived on the host; up = (0,-1,0) gives e1 = x, e2 = z and an exact projection).  Out, one thread per box:
+ *   poly (N,8,2)   the convex hull of the eight points (v.e1, v.e2), counter-clockwise in the (e1, e2) plane, strictly convex
+ *                  (duplicate and collinear points dropped); the slots behind `count` are 0
+ *   count (N)      int32 hull size, 3 .. 8; 0 for an INVALID box: a non-finite vertex, or footprint area <= eps_area
+ *   area (N)       footprint area (fan from the first hull vertex); 0 for an invalid box
+ *   invalid        [nullable, int32[1]] += number of invalid boxes (the caller zeroes it; one integer atomic per invalid box)
+ * omni_bev_iou_pairs: iou[p] = area(P ^ Q) / (area P + area Q - area(P ^ Q)) clamped to [0, 1] for P = footprint idx1[p] of the
+ * first set (n1 footprints), Q = footprint idx2[p] of the second (n2).  One thread per pair: exactly 0 when either footprint is
+ * invalid, an index lies outside its set, or the bounding rectangles are disjoint; otherwise both polygons are moved to a local
+ * origin (the first vertex of P) BEFORE any product is formed, P is clipped by every edge of Q (Sutherland-Hodgman, <= 16 vertices,
+ * per-thread LDS lists) and the fan area taken.  Never NaN.  No atomics: two launches give the same bits.
+ * N == 0 / npairs == 0 launch nothing; negative sizes, a NaN or negative eps_area, a component of e1 / e2 that is no unit vector's
+ * or a missing array return OMNI_ERR_ARG before anything touches the device. */
+int omni_bev_footprint(const float* verts, int N, float e1x, float e1y, float e1z, float e2x, float e2y, float e2z, float eps_area,
+                       float* poly, int* count, float* area, int* invalid, void* stream);
+int omni_bev_iou_pairs(const float* poly1, const int* count1, const float* area1, int n1, const float* poly2, const int* count2,
+                       const float* area2, int n2, const int* idx1, const int* idx2, long long npairs, float* iou, void* stream);
+
 /* ------------------------------------------------- convolution / linear (fp32 MFMA, NHWC) */
 
 /* torch.nn.Conv2d forward as used by the DLA-34 bottom-up (cubercnn/modeling/backbone/dla.py:

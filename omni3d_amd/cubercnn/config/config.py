@@ -49,3 +49,33 @@ def add_nms3d_config(cfg):
     for key, value in _NMS_3D.items():
         cfg.TEST.NMS_3D.setdefault(key, value)
     return cfg
+
+
+_EVAL_BEV = {"ENABLED": False, "UP": [0.0, -1.0, 0.0]}
+
+
+def add_bev_eval_config(cfg):
+    """TEST.EVAL_BEV.*: AP in the bird's-eye view next to AP2D / AP3D (`Omni3Deval(mode="BEV")`, csrc/bev_iou.hip): detections are
+    matched by the IoU of the cuboids' footprints on the ground plane, under the 3D protocol otherwise.  The reference has no such
+    mode and `get_cfg_defaults` stays key for key what the reference defines, so, as with `add_nms3d_config`, the node is absent
+    until this call; without it nothing is evaluated in BEV.  Idempotent: values already set are kept.
+    UP is the up vector of the ground plane IN THE CAMERA FRAME, one for the whole evaluation.  [0, -1, 0] (camera y points down)
+    is the right ground plane for the outdoor splits (KITTI, nuScenes), whose cameras are level with the road.  For indoor splits
+    with a pitched camera a single camera-frame vector is an approximation the user chooses knowingly."""
+    if "EVAL_BEV" not in cfg.TEST:
+        cfg.TEST.EVAL_BEV = CN()
+    for key, value in _EVAL_BEV.items():
+        cfg.TEST.EVAL_BEV.setdefault(key, list(value) if isinstance(value, list) else value)
+    return cfg
+
+
+def bev_eval_args(cfg):
+    """TEST.EVAL_BEV -> the keyword arguments of `Omni3DEvaluationHelper` / `Omni3DEvaluator`:
+    `Omni3DEvaluationHelper(names, filter_settings, folder, **bev_eval_args(cfg))`.  A cfg without the node: the feature off."""
+    node = cfg.TEST.get("EVAL_BEV")
+    if node is None:
+        return {"eval_bev": False, "bev_up": tuple(_EVAL_BEV["UP"])}
+    up = tuple(float(v) for v in node.UP)
+    if len(up) != 3:
+        raise ValueError("TEST.EVAL_BEV.UP must hold three numbers")
+    return {"eval_bev": bool(node.ENABLED), "bev_up": up}

@@ -3,7 +3,11 @@ form the evaluator needs: `Omni3Deval.evaluate` calls `computeIoU` once per (ima
 comprehension (:1339-1343, :1357-1431), i.e. thousands of tiny `box3d_overlap` calls; `box3d_overlap_groups` takes all
 groups at once -- one validity launch + one ragged pairs launch + one readback.  `Omni3Deval` runs the COCO-style greedy
 matching and the precision / recall accumulation around it on the device as well; `Omni3DEvaluator` / `Omni3DEvaluationHelper`
-are the per-split drivers `tools/train_net.py:do_test` uses."""
+are the per-split drivers `tools/train_net.py:do_test` uses.
+
+Extension without a counterpart in the reference: mode "BEV" = the 3D protocol with the IoU of the cuboids' footprints on the ground
+plane (`bev_overlap_groups`, csrc/bev_iou.hip) in place of IoU3D, i.e. the AP-BEV of the outdoor benchmarks; `eval_bev` switches it
+on in the two drivers, off by default."""
 import copy
 import datetime
 import json
@@ -13,7 +17,9 @@ import os
 import numpy as np
 import torch
 
-from ...kernels import iou3d
+from ...kernels import bev, iou3d
+
+BEV_UP = bev.UP            # camera y points down: the ground plane of the outdoor splits
 
 
 def box3d_overlap(boxes_dt: torch.Tensor, boxes_gt: torch.Tensor, eps_coplanar: float = 1e-4, eps_nonzero: float = 1e-8) -> torch.Tensor:
@@ -25,13 +31,23 @@ def box3d_overlap(boxes_dt: torch.Tensor, boxes_gt: torch.Tensor, eps_coplanar: 
     return out.to(boxes_dt.device)
 
 
-def box3d_overlap_groups(boxes_dt, boxes_gt, dt_sizes, gt_sizes, eps_coplanar: float = 1e-4, eps_nonzero: float = 1e-8, warn=False):
-    """All (image, category) groups of an evaluation in one pass.
+def _ragged_pairs(dt_sizes, gt_sizes):
+    """the pair list of all groups, row-major inside each group (host index arithmetic on the group table):
+    -> (row of the detection (P,), row of the ground truth (P,), offsets of the groups' pairs (groups + 1,))"""
+    counts = dt_sizes * gt_sizes
+    pair_off = np.concatenate([[0], np.cumsum(counts)])
+    P = int(pair_off[-1])
+    gid = np.repeat(np.arange(len(counts)), counts)
+    local = np.arange(P) - pair_off[gid]
+    ng = np.maximum(gt_sizes[gid], 1)
+    dt_off = np.concatenate([[0], np.cumsum(dt_sizes)])[:-1]
+    gt_off = np.concatenate([[0], np.cumsum(gt_sizes)])[:-1]
+    return (dt_off[gid] + local // ng).astype(np.int64), (gt_off[gid] + local % ng).astype(np.int64), pair_off
 
-    boxes_dt (sum(dt_sizes), 8, 3) / boxes_gt (sum(gt_sizes), 8, 3): the groups' detection (already score-sorted and cut to
-    maxDets, :1374-1377) and ground-truth corner lists, concatenated in group order; dt_sizes / gt_sizes: per-group counts.
-    -> list of (Nd_g, Ng_g) float32 IoU matrices (views of one flat device tensor, in group order; empty groups give
-    empty matrices), each equal to `box3d_overlap(dt_g, gt_g)` of the reference."""
+
+def _group_pairs(boxes_dt, boxes_gt, dt_sizes, gt_sizes):
+    """what `box3d_overlap_groups` and `bev_overlap_groups` share: the checked group table, the boxes on the device the kernels
+    run on, the ragged pair list uploaded once as int32"""
     dt_sizes = np.asarray(dt_sizes, dtype=np.int64)
     gt_sizes = np.asarray(gt_sizes, dtype=np.int64)
     if dt_sizes.shape != gt_sizes.shape or dt_sizes.ndim != 1:
@@ -42,19 +58,25 @@ def box3d_overlap_groups(boxes_dt, boxes_gt, dt_sizes, gt_sizes, eps_coplanar: f
     if not boxes_dt.is_cuda and iou3d._lib.get().emulated:      # host-emulated kernels in the GPU-less test suite
         dev = boxes_dt.device
     dt, gt = boxes_dt.to(dev).float().contiguous(), boxes_gt.to(dev).float().contiguous()
-    counts = dt_sizes * gt_sizes
-    pair_off = np.concatenate([[0], np.cumsum(counts)])
-    P = int(pair_off[-1])
-    # ragged pair list, row-major inside each group (host index arithmetic on the group table, one upload)
-    gid = np.repeat(np.arange(len(counts)), counts)
-    local = np.arange(P) - pair_off[gid]
-    ng = np.maximum(gt_sizes[gid], 1)
-    dt_off = np.concatenate([[0], np.cumsum(dt_sizes)])[:-1]
-    gt_off = np.concatenate([[0], np.cumsum(gt_sizes)])[:-1]
-    idx1 = torch.from_numpy((dt_off[gid] + local // ng).astype(np.int32)).to(dev)
-    idx2 = torch.from_numpy((gt_off[gid] + local % ng).astype(np.int32)).to(dev)
-    if P == 0:
-        flat = torch.zeros(0, dtype=torch.float32, device=dev)
+    i1, i2, pair_off = _ragged_pairs(dt_sizes, gt_sizes)
+    idx1, idx2 = torch.from_numpy(i1.astype(np.int32)).to(dev), torch.from_numpy(i2.astype(np.int32)).to(dev)
+    return dt_sizes, gt_sizes, dt, gt, idx1, idx2, pair_off
+
+
+def _group_views(flat, dt_sizes, gt_sizes, pair_off):
+    return [flat[pair_off[g]:pair_off[g + 1]].view(int(dt_sizes[g]), int(gt_sizes[g])) for g in range(len(dt_sizes))]
+
+
+def box3d_overlap_groups(boxes_dt, boxes_gt, dt_sizes, gt_sizes, eps_coplanar: float = 1e-4, eps_nonzero: float = 1e-8, warn=False):
+    """All (image, category) groups of an evaluation in one pass.
+
+    boxes_dt (sum(dt_sizes), 8, 3) / boxes_gt (sum(gt_sizes), 8, 3): the groups' detection (already score-sorted and cut to
+    maxDets, :1374-1377) and ground-truth corner lists, concatenated in group order; dt_sizes / gt_sizes: per-group counts.
+    -> list of (Nd_g, Ng_g) float32 IoU matrices (views of one flat device tensor, in group order; empty groups give
+    empty matrices), each equal to `box3d_overlap(dt_g, gt_g)` of the reference."""
+    dt_sizes, gt_sizes, dt, gt, idx1, idx2, pair_off = _group_pairs(boxes_dt, boxes_gt, dt_sizes, gt_sizes)
+    if int(pair_off[-1]) == 0:
+        flat = torch.zeros(0, dtype=torch.float32, device=dt.device)
     else:
         valid, vcounts = iou3d.box3d_validity(dt, eps_coplanar, eps_nonzero)
         _, flat = iou3d.iou_box3d_pairs(dt, gt, idx1, idx2, valid1=valid)
@@ -64,7 +86,22 @@ def box3d_overlap_groups(boxes_dt, boxes_gt, dt_sizes, gt_sizes, eps_coplanar: f
                 print('Warning: skipping {:d} non-coplanar boxes at eval.'.format(int(c[0])))
             if c[1] > 0:
                 print('Warning: skipping {:d} zero volume boxes at eval.'.format(int(c[1])))
-    return [flat[pair_off[g]:pair_off[g + 1]].view(int(dt_sizes[g]), int(gt_sizes[g])) for g in range(len(counts))]
+    return _group_views(flat, dt_sizes, gt_sizes, pair_off)
+
+
+def bev_overlap_groups(boxes_dt, boxes_gt, dt_sizes, gt_sizes, up=BEV_UP, eps_area: float = 1e-8, warn=False):
+    """`box3d_overlap_groups` with the IoU of the boxes' footprints on the ground plane orthogonal to `up` (csrc/bev_iou.hip) in
+    place of IoU3D: the same arguments, the same return layout (views of one flat device tensor in group order).  Two footprint
+    launches, one pairs launch.  A box with a non-finite vertex or a footprint area <= eps_area overlaps nothing, on either side."""
+    dt_sizes, gt_sizes, dt, gt, idx1, idx2, pair_off = _group_pairs(boxes_dt, boxes_gt, dt_sizes, gt_sizes)
+    if int(pair_off[-1]) == 0:
+        flat = torch.zeros(0, dtype=torch.float32, device=dt.device)
+    else:
+        bad = torch.zeros(1, dtype=torch.int32, device=dt.device) if warn else None
+        flat = bev.bev_iou_pairs(bev.bev_footprints(dt, up, eps_area, counts=bad), bev.bev_footprints(gt, up, eps_area), idx1, idx2)
+        if warn and int(bad) > 0:
+            print('Warning: skipping {:d} boxes without a footprint at eval.'.format(int(bad)))
+    return _group_views(flat, dt_sizes, gt_sizes, pair_off)
 
 
 def evaluate_groups(ious_flat, dt_sizes, gt_sizes, gt_ignore, gt_range, dt_range, area_ranges, iou_thrs):
@@ -129,7 +166,7 @@ class Omni3DParams:
     def __init__(self, mode="2D"):
         if mode == "2D":
             self.setDet2DParams()
-        elif mode == "3D":
+        elif mode in ("3D", "BEV"):            # BEV: the 3D protocol (thresholds, depth ranges), so AP-BEV compares with AP3D
             self.setDet3DParams()
         else:
             raise Exception("mode %s not supported" % (mode))
@@ -164,24 +201,12 @@ class AnnotationIndex:
         return [self.anns[i] for i in ids]
 
 
-def _ragged_pairs(dt_sizes, gt_sizes):
-    counts = dt_sizes * gt_sizes
-    pair_off = np.concatenate([[0], np.cumsum(counts)])
-    P = int(pair_off[-1])
-    gid = np.repeat(np.arange(len(counts)), counts)
-    local = np.arange(P) - pair_off[gid]
-    ng = np.maximum(gt_sizes[gid], 1)
-    dt_off = np.concatenate([[0], np.cumsum(dt_sizes)])[:-1]
-    gt_off = np.concatenate([[0], np.cumsum(gt_sizes)])[:-1]
-    return (dt_off[gid] + local // ng).astype(np.int64), (gt_off[gid] + local % ng).astype(np.int64), pair_off
-
-
 class Omni3Deval:
     """`Omni3Deval(cocoGt, cocoDt, mode=...)` with the reference's evaluate() / accumulate() / summarize() and result layout
     (`eval['precision']` [T,R,K,A,M], `eval['recall']` [T,K,A,M], `eval['scores']`, `stats` (13,)).
 
-    evaluate(): all (image, category) groups at once -- one IoU pass (`box3d_overlap_groups` in 3D, a vectorised box IoU in
-    2D) and one greedy-matching launch for every group x range x threshold (`evaluate_groups`, csrc/eval_match.hip);
+    evaluate(): all (image, category) groups at once -- one IoU pass (`box3d_overlap_groups` in 3D, `bev_overlap_groups` with the
+    up vector `up` in BEV -- which otherwise is the 3D mode: `bbox3D`, `ignore3D`, `depth` --, a vectorised box IoU in 2D) and one greedy-matching launch for every group x range x threshold (`evaluate_groups`, csrc/eval_match.hip);
     accumulate(): one launch for every (category, range, maxDets, threshold) (`omni_eval_accumulate`).  The reference runs
     these as Python loops over dict-of-list structures (:1339-1351, :1230-1301).
 
@@ -190,10 +215,10 @@ class Omni3Deval:
     ground truth in proximity is ignored.  True / False like the reference, or a collection of image ids (extension: the
     helper evaluates the union of several datasets of which only some use proximity evaluation)."""
 
-    def __init__(self, cocoGt=None, cocoDt=None, iouType="bbox", mode="2D", eval_prox=False):
-        if mode not in ["2D", "3D"]:
+    def __init__(self, cocoGt=None, cocoDt=None, iouType="bbox", mode="2D", eval_prox=False, up=BEV_UP):
+        if mode not in ["2D", "3D", "BEV"]:
             raise Exception("mode %s not supported" % (mode))
-        self.mode, self.eval_prox = mode, eval_prox
+        self.mode, self.eval_prox, self.up = mode, eval_prox, tuple(float(v) for v in up)
         self.cocoGt, self.cocoDt = cocoGt, cocoDt
         self.params = Omni3DParams(mode)
         self.eval, self.stats, self._dev = {}, [], None
@@ -237,8 +262,9 @@ class Omni3Deval:
         if device is None:
             device = torch.device("cpu") if iou3d._lib.get().emulated else torch.device("cuda")
         f32 = lambda v, shape: torch.tensor(np.asarray(v, dtype=np.float32).reshape(shape)).to(device)      # noqa: E731
-        if self.mode == "3D":
-            mats = box3d_overlap_groups(f32([x[key] for x in all_d], (-1, 8, 3)), f32([x[key] for x in all_g], (-1, 8, 3)), dt_sizes, gt_sizes)
+        if self.mode != "2D":
+            b_d, b_g = f32([x[key] for x in all_d], (-1, 8, 3)), f32([x[key] for x in all_g], (-1, 8, 3))
+            mats = box3d_overlap_groups(b_d, b_g, dt_sizes, gt_sizes) if self.mode == "3D" else bev_overlap_groups(b_d, b_g, dt_sizes, gt_sizes, up=self.up)
             flat = torch.cat([m.reshape(-1) for m in mats]) if mats else torch.zeros(0, device=device)
         else:
             i1, i2, _ = _ragged_pairs(dt_sizes, gt_sizes)
@@ -439,6 +465,7 @@ def inference_on_dataset(model, data_loader):
 
 
 _METRICS = {"2D": ["AP", "AP50", "AP75", "AP95", "APs", "APm", "APl"], "3D": ["AP", "AP15", "AP25", "AP50", "APn", "APm", "APf"]}
+_METRICS["BEV"] = _METRICS["3D"]
 
 
 def _derive_results(ev, mode, class_names):
@@ -468,11 +495,15 @@ class Omni3DEvaluator:
     reference caches per-image match tables under '*_evals_per_cat_area' for the same purpose).
 
     Short form (in-memory ground truth): `Omni3DEvaluator(gt_annotations, img_ids, cat_ids, only_2d)` with
-    `process(inputs, outputs)` taking model outputs -> {'bbox': {'AP2D', 'AP3D', 'omni_eval_*'}}."""
+    `process(inputs, outputs)` taking model outputs -> {'bbox': {'AP2D', 'AP3D', 'omni_eval_*'}}.
+
+    eval_bev (extension, off by default; `bev_up` = the up vector of the ground plane in the camera frame): unless only_2d, a third
+    pass in mode 'BEV' adds 'bbox_BEV', 'log_str_BEV', 'bbox_BEV_merge' (short form: 'APBEV', 'omni_eval_BEV'); nothing else changes."""
 
     def __init__(self, dataset_name, tasks=None, distributed=True, output_dir=None, *, max_dets_per_image=None, use_fast_impl=False,
-                 eval_prox=False, only_2d=False, filter_settings=None, img_ids=None, cat_ids=None):
+                 eval_prox=False, only_2d=False, filter_settings=None, img_ids=None, cat_ids=None, eval_bev=False, bev_up=BEV_UP):
         self._only_2d, self._eval_prox, self._output_dir, self._distributed = only_2d, eval_prox, output_dir, distributed
+        self._eval_bev, self._bev_up = bool(eval_bev), tuple(float(v) for v in bev_up)
         if not isinstance(dataset_name, str):                   # short form: (gt_annotations, img_ids, cat_ids, only_2d)
             self._gt, self._omni_api = dataset_name, None
             self._img_ids = tasks if tasks is not None else img_ids
@@ -504,11 +535,15 @@ class Omni3DEvaluator:
                     pred["p2"] = inp["p2"]
                 self._predictions.append(pred)
 
+    def _modes(self):
+        """2D, 3D unless only_2d, and -- an extension the reference does not have, off by default -- BEV after them"""
+        return ["2D"] if self._only_2d else ["2D", "3D"] + (["BEV"] if self._eval_bev else [])
+
     def _evaluate_short(self):
         res = {}
-        for mode in (["2D"] if self._only_2d else ["2D", "3D"]):
+        for mode in self._modes():
             ev = Omni3Deval(AnnotationIndex(copy.deepcopy(self._gt), self._img_ids, self._cat_ids),
-                            AnnotationIndex(copy.deepcopy(self._predictions), self._img_ids, self._cat_ids), mode=mode)
+                            AnnotationIndex(copy.deepcopy(self._predictions), self._img_ids, self._cat_ids), mode=mode, up=self._bev_up)
             ev.evaluate()
             ev.accumulate()
             ev.summarize()
@@ -557,8 +592,8 @@ class Omni3DEvaluator:
         if not self._do_evaluation or len(kept) == 0:
             return copy.deepcopy(self._results)
         omni_dt = self._omni_api.loadRes(kept)
-        for mode in (["2D"] if self._only_2d else ["2D", "3D"]):
-            ev = Omni3Deval(self._omni_api, omni_dt, mode=mode, eval_prox=self._eval_prox)
+        for mode in self._modes():
+            ev = Omni3Deval(self._omni_api, omni_dt, mode=mode, eval_prox=self._eval_prox, up=self._bev_up)
             if img_ids is not None:
                 ev.params.imgIds = img_ids
             ev.evaluate()
@@ -579,7 +614,7 @@ class Omni3DEvaluationHelper:
     reference's concatenation of cached per-image match tables), with proximity evaluation applied to the images of the splits
     that use it."""
 
-    def __init__(self, dataset_names, filter_settings, output_folder, iter_label="-", only_2d=False):
+    def __init__(self, dataset_names, filter_settings, output_folder, iter_label="-", only_2d=False, eval_bev=False, bev_up=BEV_UP):
         from collections import OrderedDict
         from ...d2.data import MetadataCatalog
         from ..data.datasets import simple_register
@@ -587,13 +622,16 @@ class Omni3DEvaluationHelper:
         self.iter_label, self.only_2d = iter_label, only_2d
         self.evaluators, self.results = OrderedDict(), OrderedDict()
         self.results_analysis, self.results_omni3d = OrderedDict(), OrderedDict()
+        # extension (off by default): AP in the bird's-eye view per split and for <Concat>, in `results_bev`
+        self.eval_bev, self.bev_up, self.results_bev = bool(eval_bev) and not only_2d, tuple(float(v) for v in bev_up), OrderedDict()
         self.overall_imgIds, self.overall_catIds = set(), set()
         self.output_folders = {n: os.path.join(output_folder, n) for n in self.dataset_names}
         for name in self.dataset_names:
             if MetadataCatalog.get(name).get("json_file") is None:
                 simple_register(name, filter_settings, filter_empty=False)
             ev = Omni3DEvaluator(name, output_dir=self.output_folders[name], filter_settings=filter_settings, only_2d=only_2d,
-                                 eval_prox=("Objectron" in name or "SUNRGBD" in name), distributed=False)
+                                 eval_prox=("Objectron" in name or "SUNRGBD" in name), distributed=False, eval_bev=self.eval_bev,
+                                 bev_up=self.bev_up)
             ev.reset()
             self.evaluators[name] = ev
             self.overall_imgIds.update(ev._omni_api.getImgIds())
@@ -610,6 +648,12 @@ class Omni3DEvaluationHelper:
     def _mean(values):
         values = list(values)
         return float(np.mean(values)) if values else float("nan")
+
+    def _bev_row(self, rb, categories):
+        """the row of `results_bev`: APBEV = mean of the per-category APs like AP3D, then the headline columns"""
+        return {"iters": self.iter_label, "APBEV": self._mean(rb["AP-" + c] for c in categories if "AP-" + c in rb),
+                "APBEV@15": rb["AP15"], "APBEV@25": rb["AP25"], "APBEV@50": rb["AP50"], "APBEV-N": rb["APn"], "APBEV-M": rb["APm"],
+                "APBEV-F": rb["APf"]}
 
     def _aggregates(self, res2d, res3d, categories):
         nan = float("nan")
@@ -629,6 +673,8 @@ class Omni3DEvaluationHelper:
         log.info("\n" + res["log_str_2D"].replace("mode=2D", tag + "2D"))
         if not self.only_2d:
             log.info("\n" + res["log_str_3D"].replace("mode=3D", tag + "3D"))
+        if self.eval_bev and "log_str_BEV" in res:
+            log.info("\n" + res["log_str_BEV"].replace("mode=BEV", tag + "BEV"))
         names = self.filter_settings["category_names"]
         r2, r3 = res["bbox_2D"], res.get("bbox_3D", {})
         present = {c for c in names if "AP-" + c in r2}
@@ -642,6 +688,8 @@ class Omni3DEvaluationHelper:
         self.results_analysis[dataset_name] = {"iters": self.iter_label, "AP2D": general["AP2D"], "AP3D": general["AP3D"],
                                                "AP3D@15": extras["AP15"], "AP3D@25": extras["AP25"], "AP3D@50": extras["AP50"],
                                                "AP3D-N": extras["APn"], "AP3D-M": extras["APm"], "AP3D-F": extras["APf"]}
+        if self.eval_bev and "bbox_BEV" in res:
+            self.results_bev[dataset_name] = self._bev_row(res["bbox_BEV"], present)
         logperf.print_ap_category_histogram(dataset_name, self._per_category(r2, r3))
 
     def _per_category(self, r2, r3):
@@ -666,7 +714,7 @@ class Omni3DEvaluationHelper:
         ordered = [meta.thing_classes[meta.thing_dataset_id_to_contiguous_id[c]] for c in cat_ids]
         categories = set(ordered)
         merged = {}
-        for mode in (["2D"] if self.only_2d else ["2D", "3D"]):
+        for mode in (["2D"] if self.only_2d else ["2D", "3D"] + (["BEV"] if self.eval_bev else [])):
             gts, dts, prox_imgs = [], [], set()
             for name in self.dataset_names:
                 rec = self.results[name].get("bbox_" + mode + "_merge")
@@ -678,7 +726,7 @@ class Omni3DEvaluationHelper:
                     prox_imgs.update(rec["img_ids"])
             ev = Omni3Deval(AnnotationIndex(copy.deepcopy(gts), self.overall_imgIds, cat_ids),
                             AnnotationIndex(copy.deepcopy(dts), self.overall_imgIds, cat_ids), mode=mode,
-                            eval_prox=(prox_imgs if prox_imgs else False))
+                            eval_prox=(prox_imgs if prox_imgs else False), up=self.bev_up)
             ev.evaluate()
             ev.accumulate()
             ev.summarize()
@@ -686,6 +734,8 @@ class Omni3DEvaluationHelper:
             if len(ordered) == 1:       # _derive_results skips the per-category part for a single class
                 merged[mode]["AP-" + ordered[0]] = merged[mode]["AP"]
         r2, r3 = merged["2D"], merged.get("3D", {})
+        if "BEV" in merged:
+            self.results_bev["<Concat>"] = self._bev_row(merged["BEV"], categories)
         general = self._aggregates(r2, r3, categories)
         extras = {k: (r3[k] if not self.only_2d else float("nan")) for k in ("AP15", "AP25", "AP50", "APn", "APm", "APf")}
         self.results_analysis["<Concat>"] = {"iters": self.iter_label, "AP2D": general["AP2D"], "AP3D": general["AP3D"],
