@@ -20,7 +20,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from omni3d_amd.cubercnn import util, vis  # noqa: E402
-from omni3d_amd.cubercnn.config import add_nms3d_config, get_cfg_defaults  # noqa: E402
+from omni3d_amd.cubercnn.config import add_nms3d_exact_config, get_cfg_defaults  # noqa: E402
 from omni3d_amd.cubercnn.data.dataset_mapper import DatasetMapper3D  # noqa: E402
 from omni3d_amd.d2.checkpoint import DetectionCheckpointer  # noqa: E402
 from omni3d_amd.d2.config import get_cfg  # noqa: E402
@@ -87,7 +87,7 @@ def do_test(args, cfg, model):
 def setup(args):
     cfg = get_cfg()
     get_cfg_defaults(cfg)
-    add_nms3d_config(cfg)                         # TEST.NMS_3D.*: settable from the YAML file and from `opts`
+    add_nms3d_exact_config(cfg)                   # TEST.NMS_3D.* with IOU_TYPE: settable from the YAML file and from `opts`
     config_file = args.config_file
     if config_file.startswith(util.CubeRCNNHandler.PREFIX):
         config_file = util.CubeRCNNHandler._get_local_path(util.CubeRCNNHandler, config_file)
@@ -95,6 +95,8 @@ def setup(args):
     cfg.merge_from_list(args.opts)
     if getattr(args, "nms3d", None) is not None:
         cfg.merge_from_list(["TEST.NMS_3D.ENABLED", True, "TEST.NMS_3D.IOU_THRESH", float(args.nms3d)])
+    if getattr(args, "nms3d_iou", None) is not None:
+        cfg.merge_from_list(["TEST.NMS_3D.IOU_TYPE", args.nms3d_iou])
     cfg.freeze()
     default_setup(cfg, args)
     return cfg
@@ -122,6 +124,8 @@ def argument_parser():
     parser.add_argument("--ground-grid", default=False, action="store_true", help="draw the ground plane and its grid in the novel view")
     parser.add_argument("--nms3d", type=float, default=None, metavar="THRESH",
                         help="drop duplicate cuboids across categories by IoU3D above THRESH (TEST.NMS_3D.ENABLED True + IOU_THRESH)")
+    parser.add_argument("--nms3d-iou", choices=("evaluator", "exact"), default=None,
+                        help="IoU3D --nms3d decides with: the evaluator's pair algorithm, or exact geometry (TEST.NMS_3D.IOU_TYPE)")
     parser.add_argument("--display", default=False, action="store_true", help="accepted and ignored (logged)")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="'KEY VALUE' pairs that override the config")
     return parser

@@ -72,6 +72,45 @@ int omni_nms3d(const float* verts, const float* score, const int* cls, const int
                int class_agnostic, float eps_coplanar, float eps_nonzero, float* iou, int* keep, int* order, int* new_count,
                int* overflow, void* stream);
 
+/* IoU3D of two cuboids from exact geometry, in double (csrc/cuboid_exact.h, csrc/iou3d_exact.hip).  The reference has no
+ * counterpart: pytorch3d's pair algorithm, which omni_iou_box3d restates, treats a triangle within 2.56 degrees of a face plane as
+ * lying in it and is up to 0.3 off on near-aligned boxes.  The evaluator keeps that algorithm; this one EXTENDS the library for
+ * callers that need the geometry (TEST.NMS_3D.IOU_TYPE "exact").
+ *
+ * omni_cuboid_fit: verts (N,8,3) float32 corner lists in the order of omni_iou_box3d -> the cuboid they are taken for, one thread
+ * per box, all in double:
+ *   centre (N,3)   the vertex mean
+ *   axes (N,3,3)   axes[n][k] = unit axis k: the mean of the four edges parallel to it, orthonormalised (x, then y by Gram-Schmidt,
+ *                  then z = +-(x cross y) on the side of the measured z)
+ *   dims (N,3)     the norms of the three mean edges
+ *   valid (N)      int32, 0 for an INVALID box: a non-finite vertex, a dimension <= eps_dim, or a vertex further than fit_tol x the
+ *                  largest dimension from its fitted corner; centre, axes and dims of an invalid box are 0
+ *   invalid        [nullable, int32[1]] += number of invalid boxes (the caller zeroes it; one integer atomic per invalid box)
+ * The IoU below is DEFINED as that of the fitted cuboids: float32-rounded corners are not coplanar to better than 1e-6 of their
+ * magnitude and bound no solid.  eps_dim 1e-8 and fit_tol 1e-3 are the defaults of the callers: conditions on the input.
+ * omni_iou3d_exact_pairs: pair p compares fitted box idx1[p] of the first set (n1 boxes) with idx2[p] of the second (n2): vol[p] =
+ * volume of the intersection, iou[p] = vol / (v1 + v2 - vol) clamped to [0, 1], v = the product of the fitted dimensions.  One
+ * thread per pair: exactly 0 when either box is invalid, an index lies outside its set or the bounding spheres are disjoint;
+ * otherwise every face of either box, as a rectangle in the frame of its own box, is clipped by the other box's six half-spaces
+ * (Sutherland-Hodgman, <= 10 vertices, per-thread LDS lists) and vol = 1/3 sum (n . p0) area.  A signed distance within 1e-12 of
+ * the pair's largest coordinate is 0; the second box's faces are clipped by OPEN half-spaces, the first's by half-spaces that are
+ * closed where the two outward normals agree, so a shared face plane counts once (same side) or not at all (touching).  Never NaN.
+ * No atomics: two launches give the same bits.  N == 0 / npairs == 0 launch nothing; negative sizes, a NaN or negative eps_dim /
+ * fit_tol or a missing array return OMNI_ERR_ARG before anything touches the device.
+ * omni_nms3d_exact: omni_nms3d with the arguments and outputs of omni_nms3d, deciding by this IoU.  Launch (1) is one THREAD per
+ * slot pair i < j, written to both halves of iou (B,S,S), diagonal 0, every entry written; a slot takes part only if it passes the
+ * validity test of omni_nms3d AND the fit (eps_dim 1e-8, fit_tol 1e-3), otherwise it is kept, never suppresses and is never
+ * suppressed.  Launch (2) is that of omni_nms3d.  invalid (1) int32 [nullable] += number of slots s < count[b] whose fit fails
+ * (the caller zeroes it); it takes the place of `overflow`: nothing here can outgrow a list. */
+int omni_cuboid_fit(const float* verts, int N, double eps_dim, double fit_tol, double* centre, double* axes, double* dims, int* valid,
+                    int* invalid, void* stream);
+int omni_iou3d_exact_pairs(const double* centre1, const double* axes1, const double* dims1, const int* valid1, int n1,
+                           const double* centre2, const double* axes2, const double* dims2, const int* valid2, int n2, const int* idx1,
+                           const int* idx2, long long npairs, float* vol, float* iou, void* stream);
+int omni_nms3d_exact(const float* verts, const float* score, const int* cls, const int* count, int B, int S, float iou_thr,
+                     int class_agnostic, float eps_coplanar, float eps_nonzero, float* iou, int* keep, int* order, int* new_count,
+                     int* invalid, void* stream);
+
 /* IoU in the bird's-eye view (csrc/bev_iou.hip): the overlap of the cuboids' footprints on the ground plane, the matching criterion
  * of AP-BEV.  The reference has no counterpart: it EXTENDS `box3d_overlap` / omni_iou_box3d_pairs with a third kind of overlap next
  * to the 2D and 3D ones of Omni3Deval.computeIoU (omni3d_evaluation.py:1359-1431).

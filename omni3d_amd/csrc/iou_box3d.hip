@@ -18,6 +18,7 @@
 // CPU oracle (oracle/iou_box3d_oracle.c), which the parity tests compare against.
 #include <device_rt.h>
 #pragma clang fp contract(off)
+#include "cuboid_exact.h"
 
 #if defined(OMNI_HIPEMU) && defined(IOU_DEBUG_HIST)
 // (host-emulator instrumentation of tools/iou3d_list_sizes.py: sizes of the joint triangle list entering each plane pass / the dedupe
@@ -933,6 +934,86 @@ int omni_nms3d(const float* verts, const float* score, const int* cls, const int
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(nms3d_iou_kernel<32, CAP>), dim3((unsigned)gx, (unsigned)B), dim3(64), 0, st, verts, cls, count, S,
                        class_agnostic, eps_coplanar, eps_nonzero, iou, overflow, chunk);
+    hipLaunchKernelGGL(nms3d_pick_kernel, dim3((unsigned)B), dim3(256), 0, st, verts, score, count, S, iou_thr, eps_coplanar,
+                       eps_nonzero, iou, keep, order, new_count);
+    return omni_launch_status();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// omni_nms3d_exact -- omni_nms3d deciding with the exact IoU3D of cuboid_exact.h instead of the evaluator's pair algorithm, which is up
+// to 0.3 off on the near-aligned duplicates this step exists for.  Launch 2 is nms3d_pick_kernel as it stands.
+//   nms3d_exact_iou_kernel  one THREAD per slot pair i < j of one image, mirrored into the full (S, S) matrix; the diagonal is 0 and
+//                           every entry is written.  As in nms3d_iou_kernel every wave takes the validity of its image's slots once, as
+//                           ballots into LDS: a slot takes part if it passes the evaluator's test AND the fit of cuboid_exact.h.  A
+//                           thread fits the two boxes of its pair itself (a twentieth of the clipping that follows) and keeps its clip
+//                           lists in a [slot][thread] LDS slice (the float32 sphere screen of nms3d_iou_kernel in front of the fits was
+//                           measured and costs more than it saves: +6 us clustered, +2 us sparse at B = 4, S = 100).  The slots < count whose fit fails are counted into `invalid` by the
+//                           first workgroup of the image, one integer atomic each.  No atomics on the pair path, no arrival order.
+namespace {
+
+__global__ void __launch_bounds__(64) nms3d_exact_iou_kernel(const float* __restrict__ verts, const int* __restrict__ cls,
+                                                             const int* __restrict__ count, int S, int class_agnostic, float eps_coplanar,
+                                                             float eps_nonzero, float* __restrict__ iou_out, int* __restrict__ invalid) {
+    __shared__ double s_v[2 * 2 * CX_CAP * 64];                   // two clip lists [vertex][x | y][thread]: 20 KB
+    __shared__ unsigned long long s_valid[NMS3D_MAXS / 64];       // bit s: slot s is in use, valid for the evaluator and a cuboid
+    const int lane = threadIdx.x;
+    const int b = blockIdx.y;
+    int n = count[b];
+    n = n < 0 ? 0 : (n > S ? S : n);
+    const float* V = verts + (size_t)b * S * 24;
+    const int* C = cls + (size_t)b * S;
+    float* O = iou_out + (size_t)b * S * S;
+    for (int s0 = 0; s0 < S; s0 += 64) {
+        const int s = s0 + lane;
+        bool fit = false;
+        if (s < n) {
+            CxBox box;
+            fit = cuboid_fit(V + (size_t)s * 24, CX_EPS_DIM, CX_FIT_TOL, box);
+            if (!fit && blockIdx.x == 0 && invalid) atomicAdd(invalid, 1);
+        }
+        const unsigned long long m = __ballot(fit && nms3d_box_valid(V + (size_t)s * 24, eps_coplanar, eps_nonzero));
+        if (lane == 0) s_valid[s0 >> 6] = m;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0)
+        for (int s = lane; s < S; s += 64) O[(size_t)s * S + s] = 0.f;
+    const int P = S * (S - 1) / 2;
+    for (int q = blockIdx.x * 64 + lane; q < P; q += gridDim.x * 64) {
+        int ia, ib;
+        nms3d_pair(q, S, ia, ib);
+        float vol = 0.f, iou = 0.f;
+        if (ib < n && (class_agnostic != 0 || C[ia] == C[ib]) && ((s_valid[ia >> 6] >> (ia & 63)) & 1ull) != 0ull &&
+            ((s_valid[ib >> 6] >> (ib & 63)) & 1ull) != 0ull) {
+            CxBox A, Bx;
+            cuboid_fit(V + (size_t)ia * 24, CX_EPS_DIM, CX_FIT_TOL, A);
+            cuboid_fit(V + (size_t)ib * 24, CX_EPS_DIM, CX_FIT_TOL, Bx);
+            cuboid_pair_iou<64>(A, Bx, s_v + lane, s_v + 2 * CX_CAP * 64 + lane, vol, iou);
+        }
+        O[(size_t)ia * S + ib] = iou;
+        O[(size_t)ib * S + ia] = iou;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// the arguments of omni_nms3d; `invalid` (1) is incremented once per slot < count whose corners are no cuboid (the caller zeroes it)
+int omni_nms3d_exact(const float* verts, const float* score, const int* cls, const int* count, int B, int S, float iou_thr,
+                     int class_agnostic, float eps_coplanar, float eps_nonzero, float* iou, int* keep, int* order, int* new_count,
+                     int* invalid, void* stream) {
+    if (B < 0 || S < 0 || S > NMS3D_MAXS || B > 65535) return OMNI_ERR_ARG;
+    if (B == 0 || S == 0) return OMNI_OK;
+    if (!verts || !score || !cls || !count || !iou || !keep || !order || !new_count) return OMNI_ERR_ARG;
+    const long long P = (long long)S * (S - 1) / 2;
+    long long gx = (P + 63) / 64, cap = (256 * 8 + B - 1) / B;
+    gx = gx > cap ? cap : gx;
+    gx = gx < 1 ? 1 : gx;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(nms3d_exact_iou_kernel, dim3((unsigned)gx, (unsigned)B), dim3(64), 0, st, verts, cls, count, S, class_agnostic,
+                       eps_coplanar, eps_nonzero, iou, invalid);
     hipLaunchKernelGGL(nms3d_pick_kernel, dim3((unsigned)B), dim3(256), 0, st, verts, score, count, S, iou_thr, eps_coplanar,
                        eps_nonzero, iou, keep, order, new_count);
     return omni_launch_status();

@@ -87,7 +87,11 @@ class InferReplay:
         sig = (len(batch), -(-H // g) * g, -(-W // g) * g)
         # settings that change WHICH launches the pass consists of: a pass captured under one is never replayed under another
         thr = getattr(self.model.roi_heads, "nms3d_thresh", None)
-        return sig if thr is None else sig + (("nms3d", float(thr), bool(self.model.roi_heads.nms3d_class_agnostic)),)
+        if thr is None:
+            return sig
+        entry = ("nms3d", float(thr), bool(self.model.roi_heads.nms3d_class_agnostic))
+        kind = getattr(self.model.roi_heads, "nms3d_iou_type", "evaluator")
+        return sig + (entry if kind == "evaluator" else entry + (kind,),)           # (the default entry stays the 3-tuple it was)
 
     def _digest(self):
         """changes whenever a captured pass could be stale: a write torch knows about (`_version`), one it cannot see (PARAM_EPOCH:

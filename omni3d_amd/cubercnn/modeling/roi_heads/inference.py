@@ -44,7 +44,8 @@ def roi_heads_inference_device(heads, feats, proposals, packed):
     if heads.nms3d_thresh is not None:
         # duplicate cuboids (TEST.NMS_3D; the reference has no such step): greedy suppression by IoU3D over the decoded slots, then
         # every field gathered by the kept slots in their ascending order -- rows taken out, nothing reordered, still no host sync
-        _, order, dcount, _, _ = det.nms3d(verts, final, dcls, dcount, heads.nms3d_thresh, heads.nms3d_class_agnostic)
+        _, order, dcount, _, _ = det.nms3d(verts, final, dcls, dcount, heads.nms3d_thresh, heads.nms3d_class_agnostic,
+                                             method=heads.nms3d_iou_type)
         flat = (order.clamp(min=0) + dimg.view(B, topk) * topk).view(-1).long()                   # (the -1 behind the count: any row)
         dbox, final, full, dcls, verts, cube3d, pose = (t.reshape(B * topk, -1)[flat].view(t.shape)
                                                         for t in (dbox, final, full, dcls, verts, cube3d, pose))

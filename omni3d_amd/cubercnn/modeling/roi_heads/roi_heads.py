@@ -130,7 +130,8 @@ class ROIHeads3D(nn.Module):
                  loss_w_xy, loss_w_z, loss_w_dims, loss_w_pose, loss_w_joint, use_confidence, inverse_z_weight, z_type,
                  pose_type, cluster_bins, priors=None, dims_priors_enabled=None, dims_priors_func=None, disentangled_loss=None,
                  virtual_depth=None, virtual_focal=None, test_scale=None, allocentric_pose=None, chamfer_pose=None,
-                 scale_roi_boxes=None, train_on_pred_boxes=False, nms3d_thresh=None, nms3d_class_agnostic=True):
+                 scale_roi_boxes=None, train_on_pred_boxes=False, nms3d_thresh=None, nms3d_class_agnostic=True,
+                 nms3d_iou_type="evaluator"):
         super().__init__()
         self.num_classes = num_classes
         self.batch_size_per_image = batch_size_per_image
@@ -149,6 +150,10 @@ class ROIHeads3D(nn.Module):
         # TEST.NMS_3D (config.add_nms3d_config): IoU3D threshold of the duplicate-cuboid suppression at inference, None = off (the reference)
         self.nms3d_thresh = None if nms3d_thresh is None else float(nms3d_thresh)
         self.nms3d_class_agnostic = bool(nms3d_class_agnostic)
+        # TEST.NMS_3D.IOU_TYPE (config.add_nms3d_exact_config): "evaluator" = the pair algorithm of AP3D, "exact" = exact geometry
+        if nms3d_iou_type not in det.NMS3D_METHODS:
+            raise ValueError(f"TEST.NMS_3D.IOU_TYPE '{nms3d_iou_type}' is not one of {det.NMS3D_METHODS}")
+        self.nms3d_iou_type = nms3d_iou_type
         if loss_w_3d <= 0:
             raise NotImplementedError("MI355X hot path: LOSS_W_3D <= 0 (no cube head) is not built; the reference's training branch "
                                       "fails there as well (roi_heads.py:219-225 returns an unassigned `instances_3d`)")
@@ -192,6 +197,7 @@ class ROIHeads3D(nn.Module):
         return {
             "nms3d_thresh": nms3d.IOU_THRESH if nms3d is not None and nms3d.ENABLED else None,
             "nms3d_class_agnostic": nms3d.CLASS_AGNOSTIC if nms3d is not None else True,
+            "nms3d_iou_type": nms3d.IOU_TYPE if nms3d is not None and "IOU_TYPE" in nms3d else "evaluator",     # add_nms3d_exact_config
             "num_classes": cfg.MODEL.ROI_HEADS.NUM_CLASSES, "batch_size_per_image": cfg.MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE,
             "positive_fraction": cfg.MODEL.ROI_HEADS.POSITIVE_FRACTION, "proposal_iou_threshold": cfg.MODEL.ROI_HEADS.IOU_THRESHOLDS[0],
             "proposal_append_gt": cfg.MODEL.ROI_HEADS.PROPOSAL_APPEND_GT, "train_on_pred_boxes": cfg.MODEL.ROI_BOX_HEAD.TRAIN_ON_PRED_BOXES,

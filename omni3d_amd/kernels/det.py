@@ -396,11 +396,19 @@ def train_vis_pick(pred, head, uncert_off, rois, cls, nfg, K, weights=(10.0, 10.
     return keep_row, keep_count, keep_box, keep_score
 
 
-def nms3d(verts, scores, cls, count, iou_thr, class_agnostic=True, eps_coplanar=1e-4, eps_nonzero=1e-8):
+NMS3D_METHODS = ("evaluator", "exact")
+
+
+def nms3d(verts, scores, cls, count, iou_thr, class_agnostic=True, eps_coplanar=1e-4, eps_nonzero=1e-8, method="evaluator"):
     """Greedy suppression of duplicate cuboids among the fixed detection slots (csrc/iou_box3d.hip, omni_nms3d): verts (B*S, 8, 3)
     float32, scores (B*S,) float32, cls (B, S) or (B*S,) int32, count (B,) int32 -> keep (B, S) int32, order (B, S) int32 (the kept
     slots in ascending order, then -1), new_count (B,) int32, iou (B, S, S) float32 (the IoU3D of the compared pairs, 0 elsewhere),
-    overflow (1,) int32.  Two launches, no host synchronisation."""
+    overflow (1,) int32.  Two launches, no host synchronisation.
+    method: "evaluator" decides with the evaluator's pair algorithm (omni_nms3d); "exact" with the exact IoU3D of the cuboids fitted
+    to the corners (omni_nms3d_exact, csrc/cuboid_exact.h), which is right on near-aligned duplicates too -- the last output is then
+    the number of slots in use whose corners are no cuboid, and such a slot takes no part."""
+    if method not in NMS3D_METHODS:
+        raise ValueError(f"nms3d: method must be one of {NMS3D_METHODS}, got {method!r}")
     if count.dim() != 1 or count.dtype != torch.int32:
         raise ValueError(f"nms3d: count must be int32 of shape (B,), got {count.dtype} {tuple(count.shape)}")
     B = count.shape[0]
@@ -418,7 +426,7 @@ def nms3d(verts, scores, cls, count, iou_thr, class_agnostic=True, eps_coplanar=
     order = _empty((B, S), torch.int32, verts)
     new_count = _empty((B,), torch.int32, verts)
     overflow = torch.zeros(1, dtype=torch.int32, device=verts.device)      # a counter the kernel adds to
-    L.call("omni_nms3d", _lib.ptr(verts), _lib.ptr(scores), _lib.ptr(cls), _lib.ptr(count), B, S, float(iou_thr), int(bool(class_agnostic)),
+    L.call("omni_nms3d" if method == "evaluator" else "omni_nms3d_exact", _lib.ptr(verts), _lib.ptr(scores), _lib.ptr(cls), _lib.ptr(count), B, S, float(iou_thr), int(bool(class_agnostic)),
            float(eps_coplanar), float(eps_nonzero), _lib.ptr(iou), _lib.ptr(keep), _lib.ptr(order), _lib.ptr(new_count), _lib.ptr(overflow),
            _lib.stream_of(verts))
     return keep, order, new_count, iou, overflow

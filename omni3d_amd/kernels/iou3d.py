@@ -8,6 +8,10 @@ import torch
 from .. import lib as _lib
 
 
+def _empty(shape, dtype, like):
+    return torch.empty(shape, dtype=dtype, device=like.device)
+
+
 def _check_boxes(b, name):
     if b.dim() != 3 or b.shape[1] != 8 or b.shape[2] != 3:
         raise ValueError(f"{name} must have shape (B, 8, 3), got {tuple(b.shape)}")
@@ -80,3 +84,95 @@ def box3d_overlap(boxes_dt, boxes_gt, eps_coplanar=1e-4, eps_nonzero=1e-8, warn=
         if c[1] > 0:
             print('Warning: skipping {:d} zero volume boxes at eval.'.format(int(c[1])))
     return iou
+
+
+# ---- exact geometry (csrc/cuboid_exact.h, csrc/iou3d_exact.hip) --------------------------------------------------------------------
+
+def cuboid_fit(boxes, eps_dim=1e-8, fit_tol=1e-3, counts=None):
+    """boxes (N,8,3) float32 contiguous corner lists in the order of `boxgen.UNIT` -> the fitted cuboids ``(centre (N,3), axes (N,3,3),
+    dims (N,3), valid (N,) int32)``, the first three float64: centre = vertex mean, axes[n, k] = unit axis k (mean of the four parallel
+    edges, orthonormalised), dims = the norms of the mean edges.  A box is invalid (valid 0, the rest 0) when a vertex is not finite, a
+    dimension is <= eps_dim, or a vertex lies further than fit_tol x the largest dimension from its fitted corner.  counts: optional
+    int32 (1,) tensor the number of invalid boxes is added to.  ValueError on a wrong shape / dtype / stride / argument before
+    anything is launched; N == 0 launches nothing."""
+    if not isinstance(boxes, torch.Tensor):
+        raise ValueError("boxes must be a tensor")
+    _check_boxes(boxes, "boxes")
+    if not boxes.is_contiguous():
+        raise ValueError("boxes must be contiguous")
+    if not float(eps_dim) >= 0.0 or not float(fit_tol) >= 0.0 or float(eps_dim) == float("inf") or float(fit_tol) == float("inf"):
+        raise ValueError("eps_dim and fit_tol must be finite and >= 0")
+    if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.numel() != 1
+                               or counts.device != boxes.device):
+        raise ValueError("counts must be one int32 on the boxes' device")
+    L = _lib.check_device(boxes, counts)
+    N = boxes.shape[0]
+    centre, axes, dims = _empty((N, 3), torch.float64, boxes), _empty((N, 3, 3), torch.float64, boxes), _empty((N, 3), torch.float64, boxes)
+    valid = _empty((N,), torch.int32, boxes)
+    if N > 0:
+        L.call("omni_cuboid_fit", _lib.ptr(boxes), N, float(eps_dim), float(fit_tol), _lib.ptr(centre), _lib.ptr(axes), _lib.ptr(dims),
+               _lib.ptr(valid), _lib.ptr(counts), _lib.stream_of(boxes))
+    return centre, axes, dims, valid
+
+
+def _check_fit(fit, name):
+    if not isinstance(fit, (tuple, list)) or len(fit) != 4 or not all(isinstance(t, torch.Tensor) for t in fit):
+        raise ValueError(f"{name} must be the (centre, axes, dims, valid) of cuboid_fit")
+    centre, axes, dims, valid = fit
+    n = centre.shape[0] if centre.dim() else -1
+    for t, shape in ((centre, (n, 3)), (axes, (n, 3, 3)), (dims, (n, 3))):
+        if tuple(t.shape) != shape or t.dtype != torch.float64:
+            raise ValueError(f"{name}: expected float64 of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+    if tuple(valid.shape) != (n,) or valid.dtype != torch.int32:
+        raise ValueError(f"{name}: valid must be int32 of shape ({n},)")
+    if not all(t.is_contiguous() for t in fit):
+        raise ValueError(f"{name} must be contiguous")
+    return n
+
+
+def iou_fitted_pairs(fit1, fit2, idx1, idx2):
+    """(vol, iou), each (P,) float32: the exact intersection volume and IoU3D of fitted cuboid idx1[p] of fit1 and idx2[p] of fit2
+    (the tuples of `cuboid_fit`).  idx1 / idx2: 1-D int32 or int64 tensors of equal length.  Exactly 0 for a pair with an invalid box,
+    an index outside its set or disjoint bounding spheres; never NaN; two calls give the same bits; P == 0 launches nothing."""
+    n1, n2 = _check_fit(fit1, "fit1"), _check_fit(fit2, "fit2")
+    for i in (idx1, idx2):
+        if not isinstance(i, torch.Tensor) or i.dim() != 1 or i.dtype not in (torch.int32, torch.int64):
+            raise ValueError("idx1 / idx2 must be 1-D int32 or int64 tensors")
+    if idx1.shape != idx2.shape:
+        raise ValueError("idx1 / idx2 must be of equal length")
+    tensors = (*fit1, *fit2, idx1, idx2)
+    if len({t.device for t in tensors}) != 1:
+        raise ValueError("all inputs must live on one device")
+    idx1, idx2 = idx1.to(torch.int32).contiguous(), idx2.to(torch.int32).contiguous()
+    L = _lib.check_device(*tensors)
+    P = idx1.numel()
+    vol, iou = _empty((P,), torch.float32, idx1), _empty((P,), torch.float32, idx1)
+    if P > 0:
+        L.call("omni_iou3d_exact_pairs", *[_lib.ptr(t) for t in fit1], n1, *[_lib.ptr(t) for t in fit2], n2, _lib.ptr(idx1), _lib.ptr(idx2),
+               P, _lib.ptr(vol), _lib.ptr(iou), _lib.stream_of(idx1))
+    return vol, iou
+
+
+def iou_box3d_exact_pairs(boxes1, boxes2, idx1, idx2, eps_dim=1e-8, fit_tol=1e-3):
+    """Ragged / paired form of `iou_box3d_exact`: (vol, iou)[p] for boxes1[idx1[p]] and boxes2[idx2[p]].  Two fits and one pair launch."""
+    return iou_fitted_pairs(cuboid_fit(boxes1, eps_dim, fit_tol), cuboid_fit(boxes2, eps_dim, fit_tol), idx1, idx2)
+
+
+def iou_box3d_exact(boxes1, boxes2, eps_dim=1e-8, fit_tol=1e-3):
+    """(N,8,3), (M,8,3) float32 corner lists -> (vol (N,M), iou (N,M)) float32 from exact geometry in double: the IoU3D of the cuboids
+    fitted to the corners (`cuboid_fit`), right whatever the relative pose of the two boxes.  The rows and columns of invalid boxes
+    are exactly 0."""
+    fit1, fit2 = cuboid_fit(boxes1, eps_dim, fit_tol), cuboid_fit(boxes2, eps_dim, fit_tol)
+    N, M, dev = boxes1.shape[0], boxes2.shape[0], boxes1.device
+    idx1 = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(M)
+    idx2 = torch.arange(M, dtype=torch.int32, device=dev).repeat(N)
+    vol, iou = iou_fitted_pairs(fit1, fit2, idx1, idx2)
+    return vol.view(N, M), iou.view(N, M)
+
+
+def box3d_overlap_exact(boxes_dt, boxes_gt):
+    """(N,8,3), (M,8,3) -> iou (N,M): the IoU3D of the two sets from exact geometry (`iou_box3d_exact`), next to `box3d_overlap`.
+    `Omni3Deval` does NOT use it: AP3D is only comparable with the reference's numbers when it is matched with the reference's own
+    pair algorithm, near-planar rule included, so the evaluator keeps `box3d_overlap`.  This one is for consumers that need the
+    overlap itself, such as TEST.NMS_3D.IOU_TYPE "exact"."""
+    return iou_box3d_exact(boxes_dt, boxes_gt)[1]
