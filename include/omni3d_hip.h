@@ -134,6 +134,38 @@ int omni_bev_footprint(const float* verts, int N, float e1x, float e1y, float e1
 int omni_bev_iou_pairs(const float* poly1, const int* count1, const float* area1, int n1, const float* poly2, const int* count2,
                        const float* area2, int n2, const int* idx1, const int* idx2, long long npairs, float* iou, void* stream);
 
+/* True-positive errors of the centre-distance protocol (csrc/tp_errors.hip): translation, scale and orientation error of a pair of
+ * cuboids, and their averages along the recall curve (the ATE / ASE / AOE of nuScenes), for `Omni3Deval(mode="DIST")`.  The reference
+ * has no counterpart.
+ *
+ * omni_pair_errors: pair p compares fitted box idx1[p] of the first set (n1 boxes, the arrays of omni_cuboid_fit) with idx2[p] of the
+ * second (n2); err (npairs,3) double, one thread per pair, all in double:
+ *   err[p][0]  trans   |d| with d = centre1 - centre2; with an up vector (upx, upy, upz), a UNIT vector, the distance in the plane
+ *                      orthogonal to it, sqrt(max(0, |d|^2 - (d.up)^2)); up = (0, 0, 0) means the full 3D distance
+ *   err[p][1]  scale   1 - inter / (V1 + V2 - inter), inter = prod_k min(dims1[k], dims2[k]), V = the product of the dimensions
+ *   err[p][2]  orient  the geodesic angle of R = R1 R2^T (columns = the unit axes) in [0, pi] radians:
+ *                      atan2(0.5 |(R32 - R23, R13 - R31, R21 - R12)|, 0.5 (trace R - 1))
+ * (+inf, NaN, NaN) when either box is invalid (valid 0, or a dimension <= 0) or an index lies outside its set.  No atomics: two
+ * launches give the same bits.  npairs == 0 launches nothing; negative sizes, an `up` that is neither all zeros nor of norm 1 (a NaN
+ * included) or a missing array return OMNI_ERR_ARG before anything touches the device.
+ * omni_eval_tp_errors: one 64-lane wave per (category k, depth range a).  order (N) / cat_off (K+1): the merge order of
+ * omni_eval_accumulate; dt_match / dt_ignore (A,sumD): the slices of omni_eval_match's tables at ONE threshold; pair_row (sumD):
+ * the row of err (npairs,3) that holds the pair (detection d, ground truth 0 of its group), so a matched detection's errors are row
+ * pair_row[d] + dt_match[d]; npig (K,A), has_e (K), rec_thrs (R) ascending as in omni_eval_accumulate.  A detection with
+ * dt_match >= 0 and dt_ignore == 0 is a true positive; at the c-th one m_c = the mean of each error over the first c; the recall
+ * threshold r_j takes m_c when r_j >= min_recall and (c-1)/npig < r_j <= c/npig (the doubles and expressions of
+ * omni_eval_accumulate).  tp_err (K,A,3) = the mean of the values taken, 1.0 when ground truths exist but no threshold took one;
+ * tp_count (K,A) = the number of true positives.  Both are written only where has_e[k] and npig[k][a] > 0: the caller pre-fills
+ * them (-1 and 0).  Sums are ballot prefixes and lane-ordered scans in double, no floating-point atomics: two launches give the same
+ * bits.  K == 0 launches nothing; bad sizes, a min_recall outside [0, 1] or a missing array return OMNI_ERR_ARG before any launch. */
+int omni_pair_errors(const double* centre1, const double* axes1, const double* dims1, const int* valid1, int n1, const double* centre2,
+                     const double* axes2, const double* dims2, const int* valid2, int n2, const int* idx1, const int* idx2,
+                     long long npairs, double upx, double upy, double upz, double* err, void* stream);
+int omni_eval_tp_errors(const int* order, const int* cat_off, const int* dt_match, const unsigned char* dt_ignore,
+                        const long long* pair_row, const double* err, long long npairs, const int* npig, const int* has_e,
+                        const double* rec_thrs, double min_recall, int K, int A, int R, int sumD, double* tp_err, int* tp_count,
+                        void* stream);
+
 /* ------------------------------------------------- convolution / linear (fp32 MFMA, NHWC) */
 
 /* torch.nn.Conv2d forward as used by the DLA-34 bottom-up (cubercnn/modeling/backbone/dla.py:

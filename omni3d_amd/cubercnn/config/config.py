@@ -93,3 +93,41 @@ def bev_eval_args(cfg):
     if len(up) != 3:
         raise ValueError("TEST.EVAL_BEV.UP must hold three numbers")
     return {"eval_bev": bool(node.ENABLED), "bev_up": up}
+
+
+_EVAL_DIST = {"ENABLED": False, "UP": [], "DIST_THRS": [0.5, 1.0, 2.0, 4.0], "TP_DIST": 2.0, "MIN_RECALL": 0.1}
+
+
+def add_dist_eval_config(cfg):
+    """TEST.EVAL_DIST.*: the centre-distance protocol of nuScenes next to AP2D / AP3D (`Omni3Deval(mode="DIST")`, csrc/tp_errors.hip):
+    detections are matched by the distance of the fitted centres, under the 3D protocol otherwise, and the matched pairs are scored
+    for translation, scale and orientation error along the recall curve (ATE / ASE / AOE).  The reference has no such mode and
+    `get_cfg_defaults` stays key for key what the reference defines, so, as with `add_bev_eval_config`, the node is absent until this
+    call; without it nothing is evaluated by distance.  Idempotent: values already set are kept.
+    UP: empty = the full 3D distance (Omni3D has no world frame; indoor cameras are pitched), else the three components of the up
+    vector IN THE CAMERA FRAME, and the distance is taken in the ground plane orthogonal to it ([0, -1, 0] for the level outdoor
+    cameras, nuScenes' definition).  DIST_THRS: the matching thresholds in metres; TP_DIST: the one of them at which the three
+    errors are taken; MIN_RECALL: the recall below which they are not averaged.  The defaults are nuScenes'."""
+    if "EVAL_DIST" not in cfg.TEST:
+        cfg.TEST.EVAL_DIST = CN()
+    for key, value in _EVAL_DIST.items():
+        cfg.TEST.EVAL_DIST.setdefault(key, list(value) if isinstance(value, list) else value)
+    return cfg
+
+
+def dist_eval_args(cfg):
+    """TEST.EVAL_DIST -> the keyword arguments of `Omni3DEvaluationHelper` / `Omni3DEvaluator`:
+    `Omni3DEvaluationHelper(names, filter_settings, folder, **dist_eval_args(cfg))`.  A cfg without the node: the feature off.
+    ValueError when UP holds neither none nor three numbers, or TP_DIST is not one of DIST_THRS."""
+    node = cfg.TEST.get("EVAL_DIST")
+    if node is None:
+        node = _EVAL_DIST
+    get = (lambda k: node[k]) if isinstance(node, dict) else (lambda k: getattr(node, k))       # noqa: E731
+    up = tuple(float(v) for v in get("UP"))
+    if len(up) not in (0, 3):
+        raise ValueError("TEST.EVAL_DIST.UP must be empty or hold three numbers")
+    thrs = [float(v) for v in get("DIST_THRS")]
+    if float(get("TP_DIST")) not in thrs:
+        raise ValueError("TEST.EVAL_DIST.TP_DIST must be one of DIST_THRS")
+    return {"eval_dist": bool(get("ENABLED")), "dist_up": up if up else None,
+            "dist_params": {"distThrs": thrs, "tpDist": float(get("TP_DIST")), "minRecall": float(get("MIN_RECALL"))}}

@@ -7,7 +7,11 @@ are the per-split drivers `tools/train_net.py:do_test` uses.
 
 Extension without a counterpart in the reference: mode "BEV" = the 3D protocol with the IoU of the cuboids' footprints on the ground
 plane (`bev_overlap_groups`, csrc/bev_iou.hip) in place of IoU3D, i.e. the AP-BEV of the outdoor benchmarks; `eval_bev` switches it
-on in the two drivers, off by default."""
+on in the two drivers, off by default.
+
+A second one: mode "DIST" = the centre-distance protocol of nuScenes (`dist_errors_groups`, csrc/tp_errors.hip): detections are matched
+by the distance of the fitted centres, and the matched pairs are scored for translation, scale and orientation error along the recall
+curve (ATE / ASE / AOE); `eval_dist` switches it on in the two drivers, off by default.  See `Omni3Deval`."""
 import copy
 import datetime
 import json
@@ -17,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from ...kernels import bev, iou3d
+from ...kernels import bev, iou3d, tperr
 
 BEV_UP = bev.UP            # camera y points down: the ground plane of the outdoor splits
 
@@ -104,6 +108,25 @@ def bev_overlap_groups(boxes_dt, boxes_gt, dt_sizes, gt_sizes, up=BEV_UP, eps_ar
     return _group_views(flat, dt_sizes, gt_sizes, pair_off)
 
 
+def dist_errors_groups(boxes_dt, boxes_gt, dt_sizes, gt_sizes, up=None, warn=False):
+    """The pair errors of the centre-distance protocol for all (image, category) groups in one pass: the arguments of
+    `box3d_overlap_groups`, `up` as in `kernels.tperr` (None = the full 3D distance).  Both sides are fitted by `cuboid_fit` with its
+    default eps_dim and fit_tol (two launches), then one pairs launch (csrc/tp_errors.hip).
+    -> (flat (P, 3) float64 device tensor of (trans, scale, orient) in group order, row-major inside a group; the list of its
+    per-group views (Nd_g, Ng_g, 3)).  A pair with an invalid box on either side is (+inf, NaN, NaN): it matches nothing."""
+    dt_sizes, gt_sizes, dt, gt, idx1, idx2, pair_off = _group_pairs(boxes_dt, boxes_gt, dt_sizes, gt_sizes)
+    tperr.unit_up(up)                                              # a bad `up` is refused whether or not there is a pair
+    if int(pair_off[-1]) == 0:
+        flat = torch.zeros((0, 3), dtype=torch.float64, device=dt.device)
+    else:
+        bad = torch.zeros(1, dtype=torch.int32, device=dt.device) if warn else None
+        flat = tperr.pair_errors(iou3d.cuboid_fit(dt, counts=bad), iou3d.cuboid_fit(gt), idx1, idx2, up)
+        if warn and int(bad) > 0:
+            print('Warning: skipping {:d} boxes that are no cuboid at eval.'.format(int(bad)))
+    views = [flat[pair_off[g]:pair_off[g + 1]].view(int(dt_sizes[g]), int(gt_sizes[g]), 3) for g in range(len(dt_sizes))]
+    return flat, views
+
+
 def evaluate_groups(ious_flat, dt_sizes, gt_sizes, gt_ignore, gt_range, dt_range, area_ranges, iou_thrs):
     """The greedy matching of `Omni3Deval.evaluateImg` (:1433-1551, 3D mode, eval_prox off) for every (image, category)
     group x depth range x IoU threshold in one launch (the reference loops over them in Python, :1346-1351).
@@ -163,11 +186,23 @@ class Omni3DParams:
         self.areaRngLbl = ["all", "near", "medium", "far"]
         self.useCats = 1
 
+    def setDetDistParams(self):
+        """the 3D protocol's depth ranges and maxDets; a match needs dist <= d for d in distThrs (metres).  iouThrs holds the
+        thresholds mapped to the similarity 1 / (1 + dist) the matching kernel compares (`Omni3Deval.evaluate` refreshes it from
+        distThrs); the TP errors are taken at tpDist along the recall thresholds >= minRecall"""
+        self.setDet3DParams()
+        self.distThrs = np.array([0.5, 1.0, 2.0, 4.0])
+        self.tpDist = 2.0
+        self.minRecall = 0.1
+        self.iouThrs = 1.0 / (1.0 + self.distThrs)
+
     def __init__(self, mode="2D"):
         if mode == "2D":
             self.setDet2DParams()
         elif mode in ("3D", "BEV"):            # BEV: the 3D protocol (thresholds, depth ranges), so AP-BEV compares with AP3D
             self.setDet3DParams()
+        elif mode == "DIST":
+            self.setDetDistParams()
         else:
             raise Exception("mode %s not supported" % (mode))
         self.iouType = "bbox"
@@ -213,12 +248,37 @@ class Omni3Deval:
     eval_prox (proximity evaluation for non-exhaustively annotated datasets, :1419-1429, :1499, :1534-1536): a detection may
     only match ground truths whose 2D box overlaps its own by more than `params.proximity_thresh`, and a detection with no
     ground truth in proximity is ignored.  True / False like the reference, or a collection of image ids (extension: the
-    helper evaluates the union of several datasets of which only some use proximity evaluation)."""
+    helper evaluates the union of several datasets of which only some use proximity evaluation).
 
-    def __init__(self, cocoGt=None, cocoDt=None, iouType="bbox", mode="2D", eval_prox=False, up=BEV_UP):
-        if mode not in ["2D", "3D", "BEV"]:
+    Mode "DIST" (extension, the centre-distance protocol of nuScenes; `up` = None or the up vector of the ground plane).
+    Boxes: both sides are the eight `bbox3D` corners in the order of `boxgen.UNIT`, fitted by `cuboid_fit` (default eps_dim, fit_tol);
+    an invalid box on either side has distance +inf and matches nothing.
+    Distance: the Euclidean distance of the fitted centres; with `up`, the distance in the ground plane orthogonal to it (nuScenes'
+    definition; (0, -1, 0) for level outdoor cameras).  The default is the full 3D distance: Omni3D has no world frame and indoor
+    cameras are pitched.
+    Matching: the 3D protocol (depth ranges, `ignore3D`, maxDets, eval_prox; `evaluate_groups` unchanged) on the similarity
+    s = 1 / (1 + dist), computed in double and stored as float32 (0 for +inf), against the thresholds 1 / (1 + d), d in
+    `params.distThrs` (default 0.5, 1, 2, 4 m); `params.iouThrs` holds the mapped thresholds.  Departures from nuScenes: a match needs
+    dist <= d (nuScenes: <), and AP is this evaluator's 101-point AP averaged over the distance thresholds, without nuScenes' 10 %
+    recall and precision clipping.
+    TP metrics: at `params.tpDist` (default 2.0, one of distThrs) and the largest maxDets, per category and depth range: the
+    category's detections in the merge order of accumulate(), the ignored ones skipped; at the c-th true positive m_c = the mean of
+    (trans, scale, orient) of `kernels.tperr` over the first c; the recall threshold r_j of `params.recThrs` takes m_c when r_j >=
+    `params.minRecall` (default 0.1) and (c-1)/npig < r_j <= c/npig; the metric is the mean of the values taken, -1 without ground
+    truth or evaluated image, 1.0 when no threshold took a value (nuScenes' rule).  Departure: nuScenes interpolates over confidence,
+    this is the step rule above.  accumulate() fills `eval['tp_errors']` (K, A, 3) and `eval['tp_count']` (K, A); summarize() keeps
+    the `stats` layout (slots 1..3: AP at 0.5, 1 and 2 m, looked up in distThrs), appends mATE / mASE / mAOE = the means over the
+    categories with a value > -1 at range "all", and sets `tp_stats`.  No composite score: NDS needs velocity and attribute errors
+    one image does not give."""
+
+    def __init__(self, cocoGt=None, cocoDt=None, iouType="bbox", mode="2D", eval_prox=False, up=None):
+        if mode not in ["2D", "3D", "BEV", "DIST"]:
             raise Exception("mode %s not supported" % (mode))
-        self.mode, self.eval_prox, self.up = mode, eval_prox, tuple(float(v) for v in up)
+        self.mode, self.eval_prox = mode, eval_prox
+        if mode == "DIST":                     # None: the full 3D distance
+            self.up = None if up is None else tperr.unit_up(up)
+        else:                                  # the ground plane of mode BEV
+            self.up = tuple(float(v) for v in (BEV_UP if up is None else up))
         self.cocoGt, self.cocoDt = cocoGt, cocoDt
         self.params = Omni3DParams(mode)
         self.eval, self.stats, self._dev = {}, [], None
@@ -243,6 +303,15 @@ class Omni3Deval:
             g_by.setdefault((g["image_id"], g["category_id"]), []).append(g)
         for d in dts:
             d_by.setdefault((d["image_id"], d["category_id"]), []).append(d)
+        if self.mode == "DIST":
+            p.distThrs = np.asarray(p.distThrs, dtype=np.float64).reshape(-1)
+            if not (np.isfinite(p.distThrs).all() and (p.distThrs >= 0).all()):
+                raise ValueError("distThrs must be finite and >= 0")
+            if not np.any(p.distThrs == float(p.tpDist)):
+                raise ValueError("tpDist %r is not one of distThrs %r" % (p.tpDist, p.distThrs.tolist()))
+            if not 0.0 <= float(p.minRecall) <= 1.0:
+                raise ValueError("minRecall must lie in [0, 1]")
+            p.iouThrs = 1.0 / (1.0 + p.distThrs)
         maxDet = p.maxDets[-1]
         # group table in (category, image) order = the order evalImgs / accumulate walk (:1346-1351, :1230-1241)
         groups = []
@@ -264,8 +333,12 @@ class Omni3Deval:
         f32 = lambda v, shape: torch.tensor(np.asarray(v, dtype=np.float32).reshape(shape)).to(device)      # noqa: E731
         if self.mode != "2D":
             b_d, b_g = f32([x[key] for x in all_d], (-1, 8, 3)), f32([x[key] for x in all_g], (-1, 8, 3))
-            mats = box3d_overlap_groups(b_d, b_g, dt_sizes, gt_sizes) if self.mode == "3D" else bev_overlap_groups(b_d, b_g, dt_sizes, gt_sizes, up=self.up)
-            flat = torch.cat([m.reshape(-1) for m in mats]) if mats else torch.zeros(0, device=device)
+            if self.mode == "DIST":
+                pair_err, _ = dist_errors_groups(b_d, b_g, dt_sizes, gt_sizes, up=self.up, warn=True)
+                flat = (1.0 / (1.0 + pair_err[:, 0])).float()                 # in double; +inf -> 0
+            else:
+                mats = box3d_overlap_groups(b_d, b_g, dt_sizes, gt_sizes) if self.mode == "3D" else bev_overlap_groups(b_d, b_g, dt_sizes, gt_sizes, up=self.up)
+                flat = torch.cat([m.reshape(-1) for m in mats]) if mats else torch.zeros(0, device=device)
         else:
             i1, i2, _ = _ragged_pairs(dt_sizes, gt_sizes)
             bd, bg = f32([x[key] for x in all_d], (-1, 4))[torch.from_numpy(i1).to(device)], f32([x[key] for x in all_g], (-1, 4))[torch.from_numpy(i2).to(device)]
@@ -303,6 +376,8 @@ class Omni3Deval:
         self._dev = {"groups": groups, "dt_sizes": dt_sizes, "gt_sizes": gt_sizes, "match": m, "device": device,
                      "scores": np.array([x["score"] for x in all_d], dtype=np.float64),
                      "dt_ids": np.array([x.get("id", 0) for x in all_d]), "gt_ids": np.array([x.get("id", 0) for x in all_g])}
+        if self.mode == "DIST":
+            self._dev["pair_err"] = pair_err
         self._paramsEval = copy.deepcopy(self.params)
         self._evalImgs = None
 
@@ -375,6 +450,14 @@ class Omni3Deval:
                _p(t_md), K, A, M, T, R, sumD, _p(prec), _p(rec), _p(scr), iou3d._lib.stream_of(prec))
         self.eval = {"params": p, "counts": [T, R, K, A, M], "date": datetime.datetime.now().strftime("%Y-%m-%d %H:%M:%S"),
                      "precision": prec.cpu().numpy(), "recall": rec.cpu().numpy(), "scores": scr.cpu().numpy()}
+        if self.mode == "DIST":
+            # the lists were cut to the largest maxDets in evaluate(): every detection takes part
+            ti = int(np.flatnonzero(np.asarray(pe.distThrs) == float(pe.tpDist))[0])
+            pair_off = np.concatenate([[0], np.cumsum(dt_sizes * gt_sizes)])[:-1]
+            pair_row = np.repeat(pair_off, dt_sizes) + det_rank.astype(np.int64) * np.repeat(gt_sizes, dt_sizes)
+            tp_err, tp_cnt = tperr.tp_errors(t_order, t_off, dm[:, ti].contiguous(), dg[:, ti].contiguous(), tod(pair_row.astype(np.int64)),
+                                             d["pair_err"], t_npig, t_has, t_thr, float(pe.minRecall))
+            self.eval["tp_errors"], self.eval["tp_count"] = tp_err.cpu().numpy(), tp_cnt.cpu().numpy()
 
     # ---- summarize (:1553-1704) ---------------------------------------------------------------------------------------
     def summarize(self):
@@ -385,26 +468,28 @@ class Omni3Deval:
 
         def one(ap=1, iouThr=None, areaRng="all", maxDets=100):
             fmt = (" {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}" if mode == "2D"
+                   else " {:<18} {} @[ dist={:<9}| depth={:>6s} | maxDets={:>3d} ] = {:0.3f}" if mode == "DIST"
                    else " {:<18} {} @[ IoU={:<9} | depth={:>6s} | maxDets={:>3d} ] = {:0.3f}")
-            iouStr = "{:0.2f}:{:0.2f}".format(p.iouThrs[0], p.iouThrs[-1]) if iouThr is None else "{:0.2f}".format(iouThr)
+            shown = p.distThrs if mode == "DIST" else p.iouThrs            # DIST: thresholds are named, and looked up, in metres
+            iouStr = "{:0.2f}:{:0.2f}".format(shown[0], shown[-1]) if iouThr is None else "{:0.2f}".format(iouThr)
             aind = [i for i, a in enumerate(p.areaRngLbl) if a == areaRng]
             mind = [i for i, m in enumerate(p.maxDets) if m == maxDets]
             if ap == 1:
                 s = ev["precision"]
                 if iouThr is not None:
-                    s = s[np.where(np.isclose(iouThr, p.iouThrs.astype(float)))[0]]
+                    s = s[np.where(np.isclose(iouThr, np.asarray(shown).astype(float)))[0]]
                 s = s[:, :, :, aind, mind]
             else:
                 s = ev["recall"]
                 if iouThr is not None:
-                    s = s[np.where(iouThr == p.iouThrs)[0]]
+                    s = s[np.where(iouThr == np.asarray(shown))[0]]
                 s = s[:, :, aind, mind]
             mean_s = -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
             lines.append("mode={} ".format(mode) + fmt.format("Average Precision" if ap == 1 else "Average Recall", "(AP)" if ap == 1 else "(AR)",
                                                              iouStr, areaRng, maxDets, mean_s))
             return mean_s
 
-        thres = [0.5, 0.75, 0.95] if mode == "2D" else [0.15, 0.25, 0.50]
+        thres = [0.5, 0.75, 0.95] if mode == "2D" else [0.5, 1.0, 2.0] if mode == "DIST" else [0.15, 0.25, 0.50]
         L, md = p.areaRngLbl, p.maxDets
         stats = np.zeros((13,))
         stats[0] = one(1)
@@ -417,6 +502,14 @@ class Omni3Deval:
         for i in range(3):
             stats[10 + i] = one(0, areaRng=L[1 + i], maxDets=md[2])
         self.stats = stats
+        if mode == "DIST":
+            aall = p.areaRngLbl.index("all")
+            self.tp_stats = np.full((3,), -1.0)
+            for j, (name, short) in enumerate((("Translation Error", "(mATE)"), ("Scale Error", "(mASE)"), ("Orientation Error", "(mAOE)"))):
+                v = ev["tp_errors"][:, aall, j]
+                self.tp_stats[j] = np.mean(v[v > -1]) if (v > -1).any() else -1.0
+                lines.append("mode={} ".format(mode) + " {:<18} {} @[ dist={:<9}| depth={:>6s} | maxDets={:>3d} ] = {:0.3f}".format(
+                    name, short, "{:0.2f}".format(float(p.tpDist)), "all", md[-1], self.tp_stats[j]))
         return "\n".join(lines)
 
     def __str__(self):
@@ -466,12 +559,16 @@ def inference_on_dataset(model, data_loader):
 
 _METRICS = {"2D": ["AP", "AP50", "AP75", "AP95", "APs", "APm", "APl"], "3D": ["AP", "AP15", "AP25", "AP50", "APn", "APm", "APf"]}
 _METRICS["BEV"] = _METRICS["3D"]
+_METRICS["DIST"] = ["AP", "AP@0.5m", "AP@1m", "AP@2m", "APn", "APm", "APf"]
+_TP_NAMES = ("ATE", "ASE", "AOE")          # metres, 1 - IoU of the aligned boxes, radians: not scaled by 100
 
 
 def _derive_results(ev, mode, class_names):
     """omni3d_evaluation.py:765-846: the seven headline numbers (x100, NaN when undefined) + per-category AP ('AP-<name>': mean
     of the precision table over thresholds and recall points at area 'all', maxDets 100)"""
     res = {name: float(ev.stats[i] * 100 if ev.stats[i] >= 0 else "nan") for i, name in enumerate(_METRICS[mode])}
+    if mode == "DIST":
+        res.update({"m" + n: float(ev.tp_stats[j] if ev.tp_stats[j] > -1 else "nan") for j, n in enumerate(_TP_NAMES)})
     if class_names is None or len(class_names) <= 1:
         return res
     prec = ev.eval["precision"]
@@ -480,7 +577,42 @@ def _derive_results(ev, mode, class_names):
         vals = prec[:, :, k, 0, -1]
         vals = vals[vals > -1]
         res["AP-" + name] = float(np.mean(vals) * 100) if vals.size else float("nan")
+        if mode == "DIST":
+            tp = ev.eval["tp_errors"][k, 0]
+            res.update({n + "-" + name: float(tp[j] if tp[j] > -1 else "nan") for j, n in enumerate(_TP_NAMES)})
     return res
+
+
+def _dist_up(up):
+    """None, or the unit vector along three finite numbers (ValueError otherwise)"""
+    return None if up is None else tperr.unit_up(up)
+
+
+_DIST_KEYS = ("distThrs", "tpDist", "minRecall")
+
+
+def _dist_params(params):
+    """None or a dict with some of distThrs / tpDist / minRecall -> a checked copy"""
+    if params is None:
+        return {}
+    if not isinstance(params, dict) or set(params) - set(_DIST_KEYS):
+        raise ValueError("dist_params must be a dict with keys out of %r" % (_DIST_KEYS,))
+    out = dict(params)
+    if "distThrs" in out:
+        out["distThrs"] = [float(v) for v in out["distThrs"]]
+    thrs = out.get("distThrs", Omni3DParams("DIST").distThrs.tolist())
+    if float(out.get("tpDist", Omni3DParams("DIST").tpDist)) not in thrs:
+        raise ValueError("tpDist must be one of distThrs")
+    return out
+
+
+def _make_eval(gt, dt, mode, eval_prox, bev_up, dist_up, dist_params):
+    """the Omni3Deval of one pass of the drivers: `up` is the BEV ground plane, except in mode DIST, which has its own"""
+    ev = Omni3Deval(gt, dt, mode=mode, eval_prox=eval_prox, up=dist_up if mode == "DIST" else bev_up)
+    if mode == "DIST":
+        for key, value in dist_params.items():
+            setattr(ev.params, key, np.asarray(value, dtype=np.float64) if key == "distThrs" else float(value))
+    return ev
 
 
 class Omni3DEvaluator:
@@ -498,12 +630,19 @@ class Omni3DEvaluator:
     `process(inputs, outputs)` taking model outputs -> {'bbox': {'AP2D', 'AP3D', 'omni_eval_*'}}.
 
     eval_bev (extension, off by default; `bev_up` = the up vector of the ground plane in the camera frame): unless only_2d, a third
-    pass in mode 'BEV' adds 'bbox_BEV', 'log_str_BEV', 'bbox_BEV_merge' (short form: 'APBEV', 'omni_eval_BEV'); nothing else changes."""
+    pass in mode 'BEV' adds 'bbox_BEV', 'log_str_BEV', 'bbox_BEV_merge' (short form: 'APBEV', 'omni_eval_BEV'); nothing else changes.
+
+    eval_dist (extension, off by default; `dist_up` = None for the full 3D distance or the up vector of the ground plane; `dist_params`
+    = optional dict of `distThrs` / `tpDist` / `minRecall` set on the pass's params): unless only_2d, one more pass in mode 'DIST'
+    after 3D and BEV adds 'bbox_DIST' (the headline APs, 'AP-<name>', 'ATE-<name>', 'ASE-<name>', 'AOE-<name>', 'mATE', 'mASE',
+    'mAOE'), 'log_str_DIST', 'bbox_DIST_merge' (short form: 'APDIST', 'omni_eval_DIST'); nothing else changes."""
 
     def __init__(self, dataset_name, tasks=None, distributed=True, output_dir=None, *, max_dets_per_image=None, use_fast_impl=False,
-                 eval_prox=False, only_2d=False, filter_settings=None, img_ids=None, cat_ids=None, eval_bev=False, bev_up=BEV_UP):
+                 eval_prox=False, only_2d=False, filter_settings=None, img_ids=None, cat_ids=None, eval_bev=False, bev_up=BEV_UP,
+                 eval_dist=False, dist_up=None, dist_params=None):
         self._only_2d, self._eval_prox, self._output_dir, self._distributed = only_2d, eval_prox, output_dir, distributed
         self._eval_bev, self._bev_up = bool(eval_bev), tuple(float(v) for v in bev_up)
+        self._eval_dist, self._dist_up, self._dist_params = bool(eval_dist), _dist_up(dist_up), _dist_params(dist_params)
         if not isinstance(dataset_name, str):                   # short form: (gt_annotations, img_ids, cat_ids, only_2d)
             self._gt, self._omni_api = dataset_name, None
             self._img_ids = tasks if tasks is not None else img_ids
@@ -536,14 +675,17 @@ class Omni3DEvaluator:
                 self._predictions.append(pred)
 
     def _modes(self):
-        """2D, 3D unless only_2d, and -- an extension the reference does not have, off by default -- BEV after them"""
-        return ["2D"] if self._only_2d else ["2D", "3D"] + (["BEV"] if self._eval_bev else [])
+        """2D, 3D unless only_2d, and -- extensions the reference does not have, off by default -- BEV and DIST after them"""
+        return ["2D"] if self._only_2d else ["2D", "3D"] + (["BEV"] if self._eval_bev else []) + (["DIST"] if self._eval_dist else [])
+
+    def _make_eval(self, gt, dt, mode, eval_prox=False):
+        return _make_eval(gt, dt, mode, eval_prox, self._bev_up, self._dist_up, self._dist_params)
 
     def _evaluate_short(self):
         res = {}
         for mode in self._modes():
-            ev = Omni3Deval(AnnotationIndex(copy.deepcopy(self._gt), self._img_ids, self._cat_ids),
-                            AnnotationIndex(copy.deepcopy(self._predictions), self._img_ids, self._cat_ids), mode=mode, up=self._bev_up)
+            ev = self._make_eval(AnnotationIndex(copy.deepcopy(self._gt), self._img_ids, self._cat_ids),
+                                 AnnotationIndex(copy.deepcopy(self._predictions), self._img_ids, self._cat_ids), mode)
             ev.evaluate()
             ev.accumulate()
             ev.summarize()
@@ -593,7 +735,7 @@ class Omni3DEvaluator:
             return copy.deepcopy(self._results)
         omni_dt = self._omni_api.loadRes(kept)
         for mode in self._modes():
-            ev = Omni3Deval(self._omni_api, omni_dt, mode=mode, eval_prox=self._eval_prox, up=self._bev_up)
+            ev = self._make_eval(self._omni_api, omni_dt, mode, self._eval_prox)
             if img_ids is not None:
                 ev.params.imgIds = img_ids
             ev.evaluate()
@@ -614,7 +756,8 @@ class Omni3DEvaluationHelper:
     reference's concatenation of cached per-image match tables), with proximity evaluation applied to the images of the splits
     that use it."""
 
-    def __init__(self, dataset_names, filter_settings, output_folder, iter_label="-", only_2d=False, eval_bev=False, bev_up=BEV_UP):
+    def __init__(self, dataset_names, filter_settings, output_folder, iter_label="-", only_2d=False, eval_bev=False, bev_up=BEV_UP,
+                 eval_dist=False, dist_up=None, dist_params=None):
         from collections import OrderedDict
         from ...d2.data import MetadataCatalog
         from ..data.datasets import simple_register
@@ -624,6 +767,9 @@ class Omni3DEvaluationHelper:
         self.results_analysis, self.results_omni3d = OrderedDict(), OrderedDict()
         # extension (off by default): AP in the bird's-eye view per split and for <Concat>, in `results_bev`
         self.eval_bev, self.bev_up, self.results_bev = bool(eval_bev) and not only_2d, tuple(float(v) for v in bev_up), OrderedDict()
+        # extension (off by default): centre-distance AP and ATE / ASE / AOE per split and for <Concat>, in `results_dist`
+        self.eval_dist, self.dist_up, self.dist_params = bool(eval_dist) and not only_2d, _dist_up(dist_up), _dist_params(dist_params)
+        self.results_dist = OrderedDict()
         self.overall_imgIds, self.overall_catIds = set(), set()
         self.output_folders = {n: os.path.join(output_folder, n) for n in self.dataset_names}
         for name in self.dataset_names:
@@ -631,7 +777,7 @@ class Omni3DEvaluationHelper:
                 simple_register(name, filter_settings, filter_empty=False)
             ev = Omni3DEvaluator(name, output_dir=self.output_folders[name], filter_settings=filter_settings, only_2d=only_2d,
                                  eval_prox=("Objectron" in name or "SUNRGBD" in name), distributed=False, eval_bev=self.eval_bev,
-                                 bev_up=self.bev_up)
+                                 bev_up=self.bev_up, eval_dist=self.eval_dist, dist_up=self.dist_up, dist_params=self.dist_params)
             ev.reset()
             self.evaluators[name] = ev
             self.overall_imgIds.update(ev._omni_api.getImgIds())
@@ -655,6 +801,12 @@ class Omni3DEvaluationHelper:
                 "APBEV@15": rb["AP15"], "APBEV@25": rb["AP25"], "APBEV@50": rb["AP50"], "APBEV-N": rb["APn"], "APBEV-M": rb["APm"],
                 "APBEV-F": rb["APf"]}
 
+    def _dist_row(self, rd, categories):
+        """the row of `results_dist`: APDIST = mean of the per-category APs like AP3D, the headline columns, the three mean errors"""
+        return {"iters": self.iter_label, "APDIST": self._mean(rd["AP-" + c] for c in categories if "AP-" + c in rd),
+                "APDIST@0.5m": rd["AP@0.5m"], "APDIST@1m": rd["AP@1m"], "APDIST@2m": rd["AP@2m"], "APDIST-N": rd["APn"],
+                "APDIST-M": rd["APm"], "APDIST-F": rd["APf"], "mATE": rd["mATE"], "mASE": rd["mASE"], "mAOE": rd["mAOE"]}
+
     def _aggregates(self, res2d, res3d, categories):
         nan = float("nan")
         out = {"AP2D": self._mean(res2d["AP-" + c] for c in categories), "AP3D": nan}
@@ -675,6 +827,8 @@ class Omni3DEvaluationHelper:
             log.info("\n" + res["log_str_3D"].replace("mode=3D", tag + "3D"))
         if self.eval_bev and "log_str_BEV" in res:
             log.info("\n" + res["log_str_BEV"].replace("mode=BEV", tag + "BEV"))
+        if self.eval_dist and "log_str_DIST" in res:
+            log.info("\n" + res["log_str_DIST"].replace("mode=DIST", tag + "DIST"))
         names = self.filter_settings["category_names"]
         r2, r3 = res["bbox_2D"], res.get("bbox_3D", {})
         present = {c for c in names if "AP-" + c in r2}
@@ -690,6 +844,8 @@ class Omni3DEvaluationHelper:
                                                "AP3D-N": extras["APn"], "AP3D-M": extras["APm"], "AP3D-F": extras["APf"]}
         if self.eval_bev and "bbox_BEV" in res:
             self.results_bev[dataset_name] = self._bev_row(res["bbox_BEV"], present)
+        if self.eval_dist and "bbox_DIST" in res:
+            self.results_dist[dataset_name] = self._dist_row(res["bbox_DIST"], present)
         logperf.print_ap_category_histogram(dataset_name, self._per_category(r2, r3))
 
     def _per_category(self, r2, r3):
@@ -714,7 +870,7 @@ class Omni3DEvaluationHelper:
         ordered = [meta.thing_classes[meta.thing_dataset_id_to_contiguous_id[c]] for c in cat_ids]
         categories = set(ordered)
         merged = {}
-        for mode in (["2D"] if self.only_2d else ["2D", "3D"] + (["BEV"] if self.eval_bev else [])):
+        for mode in (["2D"] if self.only_2d else ["2D", "3D"] + (["BEV"] if self.eval_bev else []) + (["DIST"] if self.eval_dist else [])):
             gts, dts, prox_imgs = [], [], set()
             for name in self.dataset_names:
                 rec = self.results[name].get("bbox_" + mode + "_merge")
@@ -724,18 +880,22 @@ class Omni3DEvaluationHelper:
                 dts += rec["dt"]
                 if rec["eval_prox"]:
                     prox_imgs.update(rec["img_ids"])
-            ev = Omni3Deval(AnnotationIndex(copy.deepcopy(gts), self.overall_imgIds, cat_ids),
-                            AnnotationIndex(copy.deepcopy(dts), self.overall_imgIds, cat_ids), mode=mode,
-                            eval_prox=(prox_imgs if prox_imgs else False), up=self.bev_up)
+            ev = _make_eval(AnnotationIndex(copy.deepcopy(gts), self.overall_imgIds, cat_ids),
+                            AnnotationIndex(copy.deepcopy(dts), self.overall_imgIds, cat_ids), mode,
+                            (prox_imgs if prox_imgs else False), self.bev_up, self.dist_up, self.dist_params)
             ev.evaluate()
             ev.accumulate()
             ev.summarize()
             merged[mode] = _derive_results(ev, mode, ordered if len(ordered) > 1 else None)
             if len(ordered) == 1:       # _derive_results skips the per-category part for a single class
                 merged[mode]["AP-" + ordered[0]] = merged[mode]["AP"]
+                if mode == "DIST":
+                    merged[mode].update({n + "-" + ordered[0]: merged[mode]["m" + n] for n in _TP_NAMES})
         r2, r3 = merged["2D"], merged.get("3D", {})
         if "BEV" in merged:
             self.results_bev["<Concat>"] = self._bev_row(merged["BEV"], categories)
+        if "DIST" in merged:
+            self.results_dist["<Concat>"] = self._dist_row(merged["DIST"], categories)
         general = self._aggregates(r2, r3, categories)
         extras = {k: (r3[k] if not self.only_2d else float("nan")) for k in ("AP15", "AP25", "AP50", "APn", "APm", "APf")}
         self.results_analysis["<Concat>"] = {"iters": self.iter_label, "AP2D": general["AP2D"], "AP3D": general["AP3D"],
