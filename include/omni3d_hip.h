@@ -47,7 +47,7 @@ int omni_box3d_validity(const float* boxes, int N, float eps_coplanar, float eps
                         int* counts, void* stream);
 
 /* Suppression of duplicate cuboids among the fixed (B, S) detection slots of the inference pass, by IoU3D and (optionally) across
- * categories (csrc/iou_box3d.hip).  The reference has no such step: fast_rcnn_inference_single_image
+ * categories (csrc/nms3d.hip).  The reference has no such step: fast_rcnn_inference_single_image
  * (cubercnn/modeling/roi_heads/fast_rcnn.py:57-143) suppresses per class and in 2D only; this stands for the `box3d_overlap` loop its
  * users run on the host afterwards.
  *   verts (B*S,8,3)   corner lists in the order of omni_iou_box3d; score (B*S); cls (B*S) int32; count (B) int32: image b uses the

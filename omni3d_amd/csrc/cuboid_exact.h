@@ -1,6 +1,6 @@
 // cuboid_exact.h -- the exact IoU3D of two cuboids, in double, as device functions: shared by csrc/iou3d_exact.hip (omni_cuboid_fit,
-// omni_iou3d_exact_pairs) and by the pair-matrix launch of omni_nms3d_exact in csrc/iou_box3d.hip.  Both files switch multiply-add
-// contraction off before they include this header, so the host emulator and the device do the same arithmetic.
+// omni_iou3d_exact_pairs) and by the pair-matrix launch of omni_nms3d_exact in csrc/nms3d.hip.  Every file that includes it switches multiply-add
+// contraction off before it includes this header, so the host emulator and the device do the same arithmetic.
 //
 //   cuboid_fit       eight float32 corners in the order of boxgen.UNIT -> the cuboid they are taken for: centre = vertex mean, axis k =
 //                    mean of the four edges parallel to it (dimension = its norm), the axes orthonormalised (x, then y by Gram-Schmidt,

@@ -1,8 +1,8 @@
-// iou3d_exact.hip -- IoU3D of two cuboids that is right whatever their relative pose.  The evaluator's pair algorithm (csrc/iou_box3d.hip,
+// iou3d_exact.hip -- IoU3D of two cuboids that is right whatever their relative pose.  The evaluator's pair algorithm (csrc/box3d_pair.h,
 // the float32 restatement of pytorch3d's iou_box3d) treats a triangle within 2.56 degrees of a face plane, and close to it, as lying in
 // that plane; on near-aligned duplicates it is up to 0.3 away from exact geometry.  AP3D keeps it to stay comparable with the reference;
 // this file is for the callers that want the geometry itself (kernels/iou3d.py: cuboid_fit, iou_box3d_exact*; TEST.NMS_3D.IOU_TYPE
-// "exact" goes through omni_nms3d_exact in csrc/iou_box3d.hip, which shares the device functions of cuboid_exact.h).
+// "exact" goes through omni_nms3d_exact in csrc/nms3d.hip, which shares the device functions of cuboid_exact.h).
 //
 //   cuboid_fit_kernel         one thread per box: cuboid_fit, the result stored as doubles; an invalid box is counted into `invalid`.
 //   iou3d_exact_pairs_kernel  one thread per pair: cuboid_pair_iou on two fitted boxes; exactly 0 for an invalid box or an index outside

@@ -40,7 +40,7 @@ _NMS_3D = {"ENABLED": False, "IOU_THRESH": 0.25, "CLASS_AGNOSTIC": True}
 
 
 def add_nms3d_config(cfg):
-    """TEST.NMS_3D.*: suppression of duplicate cuboids by IoU3D at inference (csrc/iou_box3d.hip, omni_nms3d).  The reference has no
+    """TEST.NMS_3D.*: suppression of duplicate cuboids by IoU3D at inference (csrc/nms3d.hip, omni_nms3d).  The reference has no
     such step and `get_cfg_defaults` stays key for key what the reference defines, so -- detectron2's convention for project keys --
     the node is added by this call; a cfg without it builds a model with the feature off.  Idempotent: values already set are kept.
     IOU_THRESH 0.25 is a convention, the middle of the evaluator's 0.05 .. 0.5 IoU3D range, not a measured optimum."""

@@ -400,7 +400,7 @@ NMS3D_METHODS = ("evaluator", "exact")
 
 
 def nms3d(verts, scores, cls, count, iou_thr, class_agnostic=True, eps_coplanar=1e-4, eps_nonzero=1e-8, method="evaluator"):
-    """Greedy suppression of duplicate cuboids among the fixed detection slots (csrc/iou_box3d.hip, omni_nms3d): verts (B*S, 8, 3)
+    """Greedy suppression of duplicate cuboids among the fixed detection slots (csrc/nms3d.hip, omni_nms3d): verts (B*S, 8, 3)
     float32, scores (B*S,) float32, cls (B, S) or (B*S,) int32, count (B,) int32 -> keep (B, S) int32, order (B, S) int32 (the kept
     slots in ascending order, then -1), new_count (B,) int32, iou (B, S, S) float32 (the IoU3D of the compared pairs, 0 elsewhere),
     overflow (1,) int32.  Two launches, no host synchronisation.

@@ -75,7 +75,7 @@ def test_validity_masks(oracle_lib, rng):
 
 
 def test_oracle_gives_exact_zero_for_sphere_separated_boxes(oracle_lib, rng):
-    """The kernel's bounding-sphere screening (csrc/iou_box3d.hip spheres_disjoint) writes vol = iou = 0 without running the
+    """The kernel's bounding-sphere screening (csrc/box3d_pair.h spheres_disjoint) writes vol = iou = 0 without running the
     clipping passes.  That is only a shortcut if the ALGORITHM, epsilon rules included, returns exactly 0 for such pairs: checked
     here on the oracle for 60k random sphere-separated pairs, among them near misses (gap of 1e-3 of the radii), boxes sharing a
     face plane at a distance (the coplanarity rule keeps such triangles "as is" for that one plane), and axis-aligned rows."""

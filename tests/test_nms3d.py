@@ -1,4 +1,4 @@
-"""csrc/iou_box3d.hip (omni_nms3d, `kernels.det.nms3d`) against a float64 reference written here from the definition: greedy
+"""csrc/nms3d.hip (omni_nms3d, `kernels.det.nms3d`) against a float64 reference written here from the definition: greedy
 suppression over IoU3D.  Per image the slots `< count` whose box is valid (the coplanarity / area test of the evaluator, finite
 vertices) and whose score is finite are ranked by descending score, ties to the lower slot; a candidate that has not been removed is
 kept and removes every later candidate it overlaps by more than the threshold (strictly).  Every other slot `< count` is kept and

@@ -1,4 +1,4 @@
-"""omni_nms3d_exact (`kernels.det.nms3d(method="exact")`, csrc/iou_box3d.hip + csrc/cuboid_exact.h) on the case tests/test_nms3d.py had
+"""omni_nms3d_exact (`kernels.det.nms3d(method="exact")`, csrc/nms3d.hip + csrc/cuboid_exact.h) on the case tests/test_nms3d.py had
 to exclude: near-aligned duplicates.  B = 2, S = 64.  Image 0 holds four clusters of 12 copies of an upright box, jittered by 0.15:
 half of each cluster is yaw-only (relative yaw from {0, 1e-6, 1e-4, 1e-3, 0.01, 0.03, 0.1} rad) with the height and y centre of its
 original, the other half is turned 0 to 2 degrees about random axes; the other 16 slots are sparse.  Image 1 is sparse with count

@@ -1,4 +1,4 @@
-"""Times of the duplicate-cuboid suppression (csrc/iou_box3d.hip, omni_nms3d), run by hand on an MI355X; not part of bench.py.
+"""Times of the duplicate-cuboid suppression (csrc/nms3d.hip, omni_nms3d), run by hand on an MI355X; not part of bench.py.
  1. omni_nms3d alone (its two launches, outputs allocated once) between device events at B = 4, S = 100: with clustered boxes (60 of
     the 100 slots of every image jittered around 4 centres: ~400 overlapping pairs per image go through the pair algorithm) and with
     sparse boxes (almost every pair ends at the bounding-sphere screen).
@@ -88,7 +88,7 @@ def time_passes(blocks=6, per_block=20):
 
 def main(out=None):
     assert torch.cuda.is_available(), "needs the GPU"
-    lines = ["csrc/iou_box3d.hip omni_nms3d -- B = %d images, S = %d slots, threshold %.2f, class-agnostic" % (B, S, THR)]
+    lines = ["csrc/nms3d.hip omni_nms3d -- B = %d images, S = %d slots, threshold %.2f, class-agnostic" % (B, S, THR)]
     for clustered in (True, False):
         us, pairs, counts, over = time_kernels(clustered)
         lines.append("omni_nms3d alone, %s boxes: %.1f us per call (two launches; device events, 200 calls); %d pairs above the threshold, "
