@@ -166,6 +166,40 @@ int omni_eval_tp_errors(const int* order, const int* cat_off, const int* dt_matc
                         const double* rec_thrs, double min_recall, int K, int A, int R, int sumD, double* tp_err, int* tp_count,
                         void* stream);
 
+/* Longitudinal-error-tolerant 3D metrics (csrc/let_iou.hip): LET-3D-AP / LET-3D-APL of Hung et al. 2022, the camera-only metric of the
+ * Waymo Open Dataset, for `Omni3Deval(mode="LET")`.  The reference has no counterpart.
+ *
+ * omni_let_pairs: pair p takes fitted box idx1[p] of the first set (the DETECTIONS, n1 boxes, the arrays of omni_cuboid_fit; centre P)
+ * and idx2[p] of the second (the GROUND TRUTHS, n2; centre G), the sensor at the origin of the coordinates, one thread per pair, all
+ * in double:
+ *   lon[p]  (double)  (G - P) . u with u = P / |P|: the signed longitudinal error, positive when the detection is too near
+ *   aff[p]  (double)  1 - min(|lon| / T, 1) with T = max(tol_frac |G|, tol_min): the longitudinal affinity in [0, 1]
+ *   iou[p]  (float)   the exact IoU3D (that of omni_iou3d_exact_pairs) of the ground truth and the detection with its centre moved
+ *                     to P + lon u, the point of its line of sight closest to G, when aff > 0; exactly 0 when aff == 0
+ * (0, 0, NaN) for a gated pair: either box invalid (valid 0, or a dimension <= 0), an index outside its set, or |P| <= 1e-8 (no
+ * line of sight).  NaN never leaves through iou or aff.  No atomics: two launches give the same bits.  npairs == 0 launches nothing;
+ * negative sizes, a tol_frac that is not finite and >= 0, a tol_min that is not finite and > 0 or a missing array return
+ * OMNI_ERR_ARG before anything touches the device.
+ * omni_eval_accumulate_let: one 64-lane wave per (k, a, m, t), on the arguments of omni_eval_accumulate (order, cat_off, rank,
+ * dt_match / dt_ignore (A,T,sumD), npig, has_e, rec_thrs, max_dets) plus pair_row (sumD), the row of aff / lon (npairs) that holds the
+ * pair (detection d, ground truth 0 of its group): the pair of a true positive is pair_row[d] + dt_match[a][t][d]; a row outside
+ * [0, npairs) counts as NaN and nothing is read.  With prec_L(s) = (sum of aff over the true positives up to list position s) /
+ * (tp + fp + eps), eps = 2^-52:
+ *   precision_l (T,R,K,A,M)  prec_L made monotone from the right and sampled at rec_thrs exactly as `precision` is
+ *   tp_affinity (T,K,A,M)    the mean aff of the true positives among the included detections (rank < max_dets[m])
+ *   tp_lon      (T,K,A,M)    the mean signed lon of the same, metres
+ * precision_l is written where omni_eval_accumulate writes `precision` (has_e[k] and npig[k][a] > 0), the two means where there is
+ * a true positive as well: the caller pre-fills all three with -1.  Sums are ballot prefixes and lane-ordered scans in double, no
+ * floating-point atomics: two launches give the same bits.  K == 0 launches nothing; bad sizes or a missing array return
+ * OMNI_ERR_ARG before any launch. */
+int omni_let_pairs(const double* centre1, const double* axes1, const double* dims1, const int* valid1, int n1, const double* centre2,
+                   const double* axes2, const double* dims2, const int* valid2, int n2, const int* idx1, const int* idx2,
+                   long long npairs, double tol_frac, double tol_min, float* iou, double* aff, double* lon, void* stream);
+int omni_eval_accumulate_let(const int* order, const int* cat_off, const int* rank, const int* dt_match, const unsigned char* dt_ignore,
+                             const long long* pair_row, const double* aff, const double* lon, long long npairs, const int* npig,
+                             const int* has_e, const double* rec_thrs, const int* max_dets, int K, int A, int M, int T, int R, int sumD,
+                             double* precision_l, double* tp_affinity, double* tp_lon, void* stream);
+
 /* ------------------------------------------------- convolution / linear (fp32 MFMA, NHWC) */
 
 /* torch.nn.Conv2d forward as used by the DLA-34 bottom-up (cubercnn/modeling/backbone/dla.py:

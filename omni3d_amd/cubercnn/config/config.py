@@ -131,3 +131,42 @@ def dist_eval_args(cfg):
         raise ValueError("TEST.EVAL_DIST.TP_DIST must be one of DIST_THRS")
     return {"eval_dist": bool(get("ENABLED")), "dist_up": up if up else None,
             "dist_params": {"distThrs": thrs, "tpDist": float(get("TP_DIST")), "minRecall": float(get("MIN_RECALL"))}}
+
+
+_EVAL_LET = {"ENABLED": False, "LON_TOL_FRAC": 0.1, "LON_TOL_MIN": 0.5}
+
+
+def add_let_eval_config(cfg):
+    """TEST.EVAL_LET.*: the longitudinal-error-tolerant metrics of the Waymo camera-only benchmark next to AP2D / AP3D
+    (`Omni3Deval(mode="LET")`, csrc/let_iou.hip): a detection may slide along its own line of sight onto the ground truth, the exact
+    IoU3D of the slid box decides the match under the 3D protocol (LET-AP), and LET-APL scales precision by how little sliding was
+    needed.  The reference has no such mode and `get_cfg_defaults` stays key for key what the reference defines, so, as with
+    `add_dist_eval_config`, the node is absent until this call; without it nothing is evaluated this way.  Idempotent: values already
+    set are kept.
+    LON_TOL_FRAC / LON_TOL_MIN: the slide may be as long as max(LON_TOL_FRAC x the range of the ground truth, LON_TOL_MIN metres).  The
+    defaults are Waymo's, taken as a convention."""
+    if "EVAL_LET" not in cfg.TEST:
+        cfg.TEST.EVAL_LET = CN()
+    for key, value in _EVAL_LET.items():
+        cfg.TEST.EVAL_LET.setdefault(key, value)
+    return cfg
+
+
+def let_eval_args(cfg):
+    """TEST.EVAL_LET -> the keyword arguments of `Omni3DEvaluationHelper` / `Omni3DEvaluator`:
+    `Omni3DEvaluationHelper(names, filter_settings, folder, **let_eval_args(cfg))`.  A cfg without the node: the feature off.
+    ValueError unless LON_TOL_FRAC is finite and >= 0 and LON_TOL_MIN finite and > 0."""
+    import math
+    node = cfg.TEST.get("EVAL_LET")
+    if node is None:
+        node = _EVAL_LET
+    get = (lambda k: node[k]) if isinstance(node, dict) else (lambda k: getattr(node, k))       # noqa: E731
+    try:
+        frac, tmin = float(get("LON_TOL_FRAC")), float(get("LON_TOL_MIN"))
+    except (TypeError, ValueError):
+        raise ValueError("TEST.EVAL_LET.LON_TOL_FRAC / LON_TOL_MIN must be numbers") from None
+    if not (math.isfinite(frac) and frac >= 0.0):
+        raise ValueError("TEST.EVAL_LET.LON_TOL_FRAC must be finite and >= 0")
+    if not (math.isfinite(tmin) and tmin > 0.0):
+        raise ValueError("TEST.EVAL_LET.LON_TOL_MIN must be finite and > 0")
+    return {"eval_let": bool(get("ENABLED")), "let_params": {"lonTolFrac": frac, "lonTolMin": tmin}}

@@ -11,7 +11,12 @@ on in the two drivers, off by default.
 
 A second one: mode "DIST" = the centre-distance protocol of nuScenes (`dist_errors_groups`, csrc/tp_errors.hip): detections are matched
 by the distance of the fitted centres, and the matched pairs are scored for translation, scale and orientation error along the recall
-curve (ATE / ASE / AOE); `eval_dist` switches it on in the two drivers, off by default.  See `Omni3Deval`."""
+curve (ATE / ASE / AOE); `eval_dist` switches it on in the two drivers, off by default.  See `Omni3Deval`.
+
+A third one: mode "LET" = the longitudinal-error-tolerant metrics of the Waymo camera-only benchmark (`let_overlap_groups`,
+csrc/let_iou.hip): a detection may slide along its own line of sight onto the ground truth within a tolerance that grows with range, the
+exact IoU3D of the slid box decides the match (LET-AP), and a second table scales precision by how little sliding was needed (LET-APL);
+`eval_let` switches it on in the two drivers, off by default.  See `Omni3Deval`."""
 import copy
 import datetime
 import json
@@ -21,7 +26,7 @@ import os
 import numpy as np
 import torch
 
-from ...kernels import bev, iou3d, tperr
+from ...kernels import bev, iou3d, let, tperr
 
 BEV_UP = bev.UP            # camera y points down: the ground plane of the outdoor splits
 
@@ -127,6 +132,26 @@ def dist_errors_groups(boxes_dt, boxes_gt, dt_sizes, gt_sizes, up=None, warn=Fal
     return flat, views
 
 
+def let_overlap_groups(boxes_dt, boxes_gt, dt_sizes, gt_sizes, tol_frac=let.TOL_FRAC, tol_min=let.TOL_MIN, warn=False):
+    """The longitudinal-error-tolerant IoU3D, affinity and longitudinal error of `kernels.let` for all (image, category) groups in one
+    pass: the arguments of `box3d_overlap_groups` plus the tolerance T = max(tol_frac |G|, tol_min).  Both sides are fitted by
+    `cuboid_fit` with its default eps_dim and fit_tol (two launches), then one pairs launch (csrc/let_iou.hip).
+    -> (iou (P,) float32, aff (P,) float64, lon (P,) float64: flat device tensors in group order, row-major inside a group; the list
+    of the per-group views (Nd_g, Ng_g) of iou).  A gated pair (an invalid box on either side, a detection on the sensor) is
+    (0, 0, NaN): it matches nothing."""
+    dt_sizes, gt_sizes, dt, gt, idx1, idx2, pair_off = _group_pairs(boxes_dt, boxes_gt, dt_sizes, gt_sizes)
+    tol_frac, tol_min = let.check_tolerance(tol_frac, tol_min)    # a bad tolerance is refused whether or not there is a pair
+    if int(pair_off[-1]) == 0:
+        iou = torch.zeros(0, dtype=torch.float32, device=dt.device)
+        aff, lon = torch.zeros(0, dtype=torch.float64, device=dt.device), torch.zeros(0, dtype=torch.float64, device=dt.device)
+    else:
+        bad = torch.zeros(1, dtype=torch.int32, device=dt.device) if warn else None
+        iou, aff, lon = let.let_pairs(iou3d.cuboid_fit(dt, counts=bad), iou3d.cuboid_fit(gt), idx1, idx2, tol_frac, tol_min)
+        if warn and int(bad) > 0:
+            print('Warning: skipping {:d} boxes that are no cuboid at eval.'.format(int(bad)))
+    return iou, aff, lon, _group_views(iou, dt_sizes, gt_sizes, pair_off)
+
+
 def evaluate_groups(ious_flat, dt_sizes, gt_sizes, gt_ignore, gt_range, dt_range, area_ranges, iou_thrs):
     """The greedy matching of `Omni3Deval.evaluateImg` (:1433-1551, 3D mode, eval_prox off) for every (image, category)
     group x depth range x IoU threshold in one launch (the reference loops over them in Python, :1346-1351).
@@ -196,6 +221,13 @@ class Omni3DParams:
         self.minRecall = 0.1
         self.iouThrs = 1.0 / (1.0 + self.distThrs)
 
+    def setDetLetParams(self):
+        """the 3D protocol (thresholds on the longitudinal-error-tolerant IoU3D, depth ranges, maxDets); a detection may slide along
+        its line of sight by up to max(lonTolFrac x range of the ground truth, lonTolMin metres)"""
+        self.setDet3DParams()
+        self.lonTolFrac = let.TOL_FRAC
+        self.lonTolMin = let.TOL_MIN
+
     def __init__(self, mode="2D"):
         if mode == "2D":
             self.setDet2DParams()
@@ -203,6 +235,8 @@ class Omni3DParams:
             self.setDet3DParams()
         elif mode == "DIST":
             self.setDetDistParams()
+        elif mode == "LET":
+            self.setDetLetParams()
         else:
             raise Exception("mode %s not supported" % (mode))
         self.iouType = "bbox"
@@ -269,10 +303,34 @@ class Omni3Deval:
     this is the step rule above.  accumulate() fills `eval['tp_errors']` (K, A, 3) and `eval['tp_count']` (K, A); summarize() keeps
     the `stats` layout (slots 1..3: AP at 0.5, 1 and 2 m, looked up in distThrs), appends mATE / mASE / mAOE = the means over the
     categories with a value > -1 at range "all", and sets `tp_stats`.  No composite score: NDS needs velocity and attribute errors
-    one image does not give."""
+    one image does not give.
+
+    Mode "LET" (extension, LET-3D-AP / LET-3D-APL of Hung et al. 2022, the Waymo camera-only metric: is the detector wrong, or only
+    wrong in depth?).  Boxes as in mode "DIST": the eight `bbox3D` corners in the order of `boxgen.UNIT`, in camera coordinates, both
+    sides fitted by `cuboid_fit`; the sensor origin is the camera centre.
+    Pair: for a detection with fitted centre P and a ground truth with fitted centre G, u = P / |P| is the line of sight, lon =
+    (G - P) . u the signed longitudinal error (positive: predicted too near), T = max(lonTolFrac |G|, lonTolMin) (defaults 0.10 and
+    0.5 m, Waymo's values), aff = 1 - min(|lon| / T, 1) the longitudinal affinity; the aligned box is the detection with its centre
+    moved to P + lon u, the point of its ray closest to G; let_iou = the exact cuboid IoU3D (csrc/cuboid_exact.h, in double, stored
+    as float32) of the aligned box and the ground truth when aff > 0, exactly 0 when aff == 0.  An invalid box on either side or a
+    detection on the sensor (|P| <= 1e-8) gives (0, 0, NaN) and matches nothing.
+    Matching: the 3D protocol (iouThrs 0.05 .. 0.5, depth ranges, `ignore3D`, maxDets, eval_prox; `evaluate_groups` unchanged) on
+    let_iou; LET-AP is this evaluator's 101-point AP on those matches (`eval['precision']`, `stats`).  Departures from Waymo: Waymo
+    matches bipartitely on the longitudinal affinity, this is the greedy COCO matching by descending score on let_iou;
+    Waymo thresholds at one IoU per class and bins by difficulty level, here the ten IoU thresholds and the depth ranges of AP3D
+    apply; the exact IoU3D decides, not the pair algorithm AP3D keeps for comparability (a slid box is a near-aligned near-duplicate,
+    where that algorithm is off by up to 0.3).
+    LET-APL: on the same lists and recall axis the precision at a list position is (sum of aff over the true positives so far) /
+    (tp + fp + eps), aff of the pair (detection, its matched ground truth); made monotone from the right and sampled at recThrs like
+    precision: `eval['precision_l']` (T, R, K, A, M), -1 where precision is, never above precision.  `eval['tp_affinity']` and
+    `eval['tp_lon']` (T, K, A, M): the mean aff and the mean signed lon (metres; its sign tells whether a category is predicted
+    systematically near or far) of the true positives among the included detections, -1 without one.  summarize() keeps the `stats`
+    layout, sets `stats_l` (7,) = LET-APL overall, at 0.15 / 0.25 / 0.50, near / medium / far, and `let_stats` (2,) = mean affinity
+    and mean signed longitudinal error at range "all", the largest maxDets and IoU 0.25, as means over the categories with a true
+    positive (-1 without any), and prints those lines too."""
 
     def __init__(self, cocoGt=None, cocoDt=None, iouType="bbox", mode="2D", eval_prox=False, up=None):
-        if mode not in ["2D", "3D", "BEV", "DIST"]:
+        if mode not in ["2D", "3D", "BEV", "DIST", "LET"]:
             raise Exception("mode %s not supported" % (mode))
         self.mode, self.eval_prox = mode, eval_prox
         if mode == "DIST":                     # None: the full 3D distance
@@ -312,6 +370,11 @@ class Omni3Deval:
             if not 0.0 <= float(p.minRecall) <= 1.0:
                 raise ValueError("minRecall must lie in [0, 1]")
             p.iouThrs = 1.0 / (1.0 + p.distThrs)
+        if self.mode == "LET":
+            try:
+                p.lonTolFrac, p.lonTolMin = let.check_tolerance(p.lonTolFrac, p.lonTolMin)
+            except ValueError:
+                raise ValueError("lonTolFrac must be finite and >= 0, lonTolMin finite and > 0") from None
         maxDet = p.maxDets[-1]
         # group table in (category, image) order = the order evalImgs / accumulate walk (:1346-1351, :1230-1241)
         groups = []
@@ -336,6 +399,8 @@ class Omni3Deval:
             if self.mode == "DIST":
                 pair_err, _ = dist_errors_groups(b_d, b_g, dt_sizes, gt_sizes, up=self.up, warn=True)
                 flat = (1.0 / (1.0 + pair_err[:, 0])).float()                 # in double; +inf -> 0
+            elif self.mode == "LET":
+                flat, pair_aff, pair_lon, _ = let_overlap_groups(b_d, b_g, dt_sizes, gt_sizes, p.lonTolFrac, p.lonTolMin, warn=True)
             else:
                 mats = box3d_overlap_groups(b_d, b_g, dt_sizes, gt_sizes) if self.mode == "3D" else bev_overlap_groups(b_d, b_g, dt_sizes, gt_sizes, up=self.up)
                 flat = torch.cat([m.reshape(-1) for m in mats]) if mats else torch.zeros(0, device=device)
@@ -378,6 +443,8 @@ class Omni3Deval:
                      "dt_ids": np.array([x.get("id", 0) for x in all_d]), "gt_ids": np.array([x.get("id", 0) for x in all_g])}
         if self.mode == "DIST":
             self._dev["pair_err"] = pair_err
+        if self.mode == "LET":
+            self._dev["pair_aff"], self._dev["pair_lon"] = pair_aff, pair_lon
         self._paramsEval = copy.deepcopy(self.params)
         self._evalImgs = None
 
@@ -458,6 +525,12 @@ class Omni3Deval:
             tp_err, tp_cnt = tperr.tp_errors(t_order, t_off, dm[:, ti].contiguous(), dg[:, ti].contiguous(), tod(pair_row.astype(np.int64)),
                                              d["pair_err"], t_npig, t_has, t_thr, float(pe.minRecall))
             self.eval["tp_errors"], self.eval["tp_count"] = tp_err.cpu().numpy(), tp_cnt.cpu().numpy()
+        if self.mode == "LET":
+            pair_off = np.concatenate([[0], np.cumsum(dt_sizes * gt_sizes)])[:-1]
+            pair_row = np.repeat(pair_off, dt_sizes) + det_rank.astype(np.int64) * np.repeat(gt_sizes, dt_sizes)
+            prec_l, tp_aff, tp_lon = let.accumulate_let(t_order, t_off, t_rank, dm, dg, tod(pair_row.astype(np.int64)), d["pair_aff"],
+                                                        d["pair_lon"], t_npig, t_has, t_thr, t_md)
+            self.eval["precision_l"], self.eval["tp_affinity"], self.eval["tp_lon"] = prec_l.cpu().numpy(), tp_aff.cpu().numpy(), tp_lon.cpu().numpy()
 
     # ---- summarize (:1553-1704) ---------------------------------------------------------------------------------------
     def summarize(self):
@@ -466,7 +539,7 @@ class Omni3Deval:
         p, ev, mode = self.params, self.eval, self.mode
         lines = []
 
-        def one(ap=1, iouThr=None, areaRng="all", maxDets=100):
+        def one(ap=1, iouThr=None, areaRng="all", maxDets=100, table="precision"):
             fmt = (" {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}" if mode == "2D"
                    else " {:<18} {} @[ dist={:<9}| depth={:>6s} | maxDets={:>3d} ] = {:0.3f}" if mode == "DIST"
                    else " {:<18} {} @[ IoU={:<9} | depth={:>6s} | maxDets={:>3d} ] = {:0.3f}")
@@ -475,7 +548,7 @@ class Omni3Deval:
             aind = [i for i, a in enumerate(p.areaRngLbl) if a == areaRng]
             mind = [i for i, m in enumerate(p.maxDets) if m == maxDets]
             if ap == 1:
-                s = ev["precision"]
+                s = ev[table]
                 if iouThr is not None:
                     s = s[np.where(np.isclose(iouThr, np.asarray(shown).astype(float)))[0]]
                 s = s[:, :, :, aind, mind]
@@ -485,8 +558,8 @@ class Omni3Deval:
                     s = s[np.where(iouThr == np.asarray(shown))[0]]
                 s = s[:, :, aind, mind]
             mean_s = -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
-            lines.append("mode={} ".format(mode) + fmt.format("Average Precision" if ap == 1 else "Average Recall", "(AP)" if ap == 1 else "(AR)",
-                                                             iouStr, areaRng, maxDets, mean_s))
+            name, short = ("Average Recall", "(AR)") if ap != 1 else ("Average Precision", "(AP)") if table == "precision" else ("Longitudinal Prec.", "(APL)")
+            lines.append("mode={} ".format(mode) + fmt.format(name, short, iouStr, areaRng, maxDets, mean_s))
             return mean_s
 
         thres = [0.5, 0.75, 0.95] if mode == "2D" else [0.5, 1.0, 2.0] if mode == "DIST" else [0.15, 0.25, 0.50]
@@ -510,6 +583,23 @@ class Omni3Deval:
                 self.tp_stats[j] = np.mean(v[v > -1]) if (v > -1).any() else -1.0
                 lines.append("mode={} ".format(mode) + " {:<18} {} @[ dist={:<9}| depth={:>6s} | maxDets={:>3d} ] = {:0.3f}".format(
                     name, short, "{:0.2f}".format(float(p.tpDist)), "all", md[-1], self.tp_stats[j]))
+        if mode == "LET":
+            stats_l = np.zeros((7,))
+            stats_l[0] = one(1, table="precision_l")
+            for i in range(3):
+                stats_l[1 + i] = one(1, iouThr=thres[i], maxDets=md[2], table="precision_l")
+            for i in range(3):
+                stats_l[4 + i] = one(1, areaRng=L[1 + i], maxDets=md[2], table="precision_l")
+            self.stats_l = stats_l
+            aall, ti = p.areaRngLbl.index("all"), np.where(np.isclose(_LET_TP_IOU, np.asarray(p.iouThrs).astype(float)))[0]
+            self.let_stats = np.full((2,), -1.0)
+            for j, (name, short, key) in enumerate((("Long. Affinity", "(mAFF)", "tp_affinity"), ("Long. Error [m]", "(mLON)", "tp_lon"))):
+                if len(ti):                                             # tp_lon is signed: the affinity says where there is a value
+                    has = ev["tp_affinity"][ti[0], :, aall, -1] > -1
+                    if has.any():
+                        self.let_stats[j] = np.mean(ev[key][ti[0], :, aall, -1][has])
+                lines.append("mode={} ".format(mode) + " {:<18} {} @[ IoU={:<9} | depth={:>6s} | maxDets={:>3d} ] = {:0.3f}".format(
+                    name, short, "{:0.2f}".format(_LET_TP_IOU), "all", md[-1], self.let_stats[j]))
         return "\n".join(lines)
 
     def __str__(self):
@@ -560,6 +650,8 @@ def inference_on_dataset(model, data_loader):
 _METRICS = {"2D": ["AP", "AP50", "AP75", "AP95", "APs", "APm", "APl"], "3D": ["AP", "AP15", "AP25", "AP50", "APn", "APm", "APf"]}
 _METRICS["BEV"] = _METRICS["3D"]
 _METRICS["DIST"] = ["AP", "AP@0.5m", "AP@1m", "AP@2m", "APn", "APm", "APf"]
+_METRICS["LET"] = _METRICS["3D"]
+_LET_TP_IOU = 0.25                         # the threshold at which summarize() reports mean affinity and longitudinal error
 _TP_NAMES = ("ATE", "ASE", "AOE")          # metres, 1 - IoU of the aligned boxes, radians: not scaled by 100
 
 
@@ -569,6 +661,10 @@ def _derive_results(ev, mode, class_names):
     res = {name: float(ev.stats[i] * 100 if ev.stats[i] >= 0 else "nan") for i, name in enumerate(_METRICS[mode])}
     if mode == "DIST":
         res.update({"m" + n: float(ev.tp_stats[j] if ev.tp_stats[j] > -1 else "nan") for j, n in enumerate(_TP_NAMES)})
+    if mode == "LET":                      # the same seven slots on the longitudinal precision, and the two diagnostics (not x100)
+        res.update({name.replace("AP", "APL", 1): float(ev.stats_l[i] * 100 if ev.stats_l[i] >= 0 else "nan") for i, name in enumerate(_METRICS[mode])})
+        res["mAFF"] = float(ev.let_stats[0] if ev.let_stats[0] > -1 else "nan")
+        res["mLON"] = float(ev.let_stats[1] if ev.let_stats[0] > -1 else "nan")
     if class_names is None or len(class_names) <= 1:
         return res
     prec = ev.eval["precision"]
@@ -580,6 +676,10 @@ def _derive_results(ev, mode, class_names):
         if mode == "DIST":
             tp = ev.eval["tp_errors"][k, 0]
             res.update({n + "-" + name: float(tp[j] if tp[j] > -1 else "nan") for j, n in enumerate(_TP_NAMES)})
+        if mode == "LET":
+            vals = ev.eval["precision_l"][:, :, k, 0, -1]
+            vals = vals[vals > -1]
+            res["APL-" + name] = float(np.mean(vals) * 100) if vals.size else float("nan")
     return res
 
 
@@ -606,12 +706,28 @@ def _dist_params(params):
     return out
 
 
-def _make_eval(gt, dt, mode, eval_prox, bev_up, dist_up, dist_params):
+_LET_KEYS = ("lonTolFrac", "lonTolMin")
+
+
+def _let_params(params):
+    """None or a dict with some of lonTolFrac / lonTolMin -> a checked copy"""
+    if params is None:
+        return {}
+    if not isinstance(params, dict) or set(params) - set(_LET_KEYS):
+        raise ValueError("let_params must be a dict with keys out of %r" % (_LET_KEYS,))
+    frac, tmin = let.check_tolerance(params.get("lonTolFrac", let.TOL_FRAC), params.get("lonTolMin", let.TOL_MIN))
+    return {k: v for k, v in (("lonTolFrac", frac), ("lonTolMin", tmin)) if k in params}
+
+
+def _make_eval(gt, dt, mode, eval_prox, bev_up, dist_up, dist_params, let_params=None):
     """the Omni3Deval of one pass of the drivers: `up` is the BEV ground plane, except in mode DIST, which has its own"""
     ev = Omni3Deval(gt, dt, mode=mode, eval_prox=eval_prox, up=dist_up if mode == "DIST" else bev_up)
     if mode == "DIST":
         for key, value in dist_params.items():
             setattr(ev.params, key, np.asarray(value, dtype=np.float64) if key == "distThrs" else float(value))
+    if mode == "LET":
+        for key, value in (let_params or {}).items():
+            setattr(ev.params, key, float(value))
     return ev
 
 
@@ -635,12 +751,18 @@ class Omni3DEvaluator:
     eval_dist (extension, off by default; `dist_up` = None for the full 3D distance or the up vector of the ground plane; `dist_params`
     = optional dict of `distThrs` / `tpDist` / `minRecall` set on the pass's params): unless only_2d, one more pass in mode 'DIST'
     after 3D and BEV adds 'bbox_DIST' (the headline APs, 'AP-<name>', 'ATE-<name>', 'ASE-<name>', 'AOE-<name>', 'mATE', 'mASE',
-    'mAOE'), 'log_str_DIST', 'bbox_DIST_merge' (short form: 'APDIST', 'omni_eval_DIST'); nothing else changes."""
+    'mAOE'), 'log_str_DIST', 'bbox_DIST_merge' (short form: 'APDIST', 'omni_eval_DIST'); nothing else changes.
+
+    eval_let (extension, off by default; `let_params` = optional dict of `lonTolFrac` / `lonTolMin` set on the pass's params): unless
+    only_2d, one more pass in mode 'LET' after 3D, BEV and DIST adds 'bbox_LET' (LET-AP in the headline slots of the 3D protocol,
+    LET-APL as 'APL', 'APL15', ..., 'AP-<name>', 'APL-<name>', 'mAFF', 'mLON'), 'log_str_LET', 'bbox_LET_merge' (short form: 'APLET',
+    'omni_eval_LET'); nothing else changes."""
 
     def __init__(self, dataset_name, tasks=None, distributed=True, output_dir=None, *, max_dets_per_image=None, use_fast_impl=False,
                  eval_prox=False, only_2d=False, filter_settings=None, img_ids=None, cat_ids=None, eval_bev=False, bev_up=BEV_UP,
-                 eval_dist=False, dist_up=None, dist_params=None):
+                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None):
         self._only_2d, self._eval_prox, self._output_dir, self._distributed = only_2d, eval_prox, output_dir, distributed
+        self._eval_let, self._let_params = bool(eval_let), _let_params(let_params)
         self._eval_bev, self._bev_up = bool(eval_bev), tuple(float(v) for v in bev_up)
         self._eval_dist, self._dist_up, self._dist_params = bool(eval_dist), _dist_up(dist_up), _dist_params(dist_params)
         if not isinstance(dataset_name, str):                   # short form: (gt_annotations, img_ids, cat_ids, only_2d)
@@ -675,11 +797,12 @@ class Omni3DEvaluator:
                 self._predictions.append(pred)
 
     def _modes(self):
-        """2D, 3D unless only_2d, and -- extensions the reference does not have, off by default -- BEV and DIST after them"""
-        return ["2D"] if self._only_2d else ["2D", "3D"] + (["BEV"] if self._eval_bev else []) + (["DIST"] if self._eval_dist else [])
+        """2D, 3D unless only_2d, and -- extensions the reference does not have, off by default -- BEV, DIST and LET after them"""
+        return ["2D"] if self._only_2d else ["2D", "3D"] + (["BEV"] if self._eval_bev else []) + (["DIST"] if self._eval_dist else []) \
+            + (["LET"] if self._eval_let else [])
 
     def _make_eval(self, gt, dt, mode, eval_prox=False):
-        return _make_eval(gt, dt, mode, eval_prox, self._bev_up, self._dist_up, self._dist_params)
+        return _make_eval(gt, dt, mode, eval_prox, self._bev_up, self._dist_up, self._dist_params, self._let_params)
 
     def _evaluate_short(self):
         res = {}
@@ -757,7 +880,7 @@ class Omni3DEvaluationHelper:
     that use it."""
 
     def __init__(self, dataset_names, filter_settings, output_folder, iter_label="-", only_2d=False, eval_bev=False, bev_up=BEV_UP,
-                 eval_dist=False, dist_up=None, dist_params=None):
+                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None):
         from collections import OrderedDict
         from ...d2.data import MetadataCatalog
         from ..data.datasets import simple_register
@@ -770,6 +893,8 @@ class Omni3DEvaluationHelper:
         # extension (off by default): centre-distance AP and ATE / ASE / AOE per split and for <Concat>, in `results_dist`
         self.eval_dist, self.dist_up, self.dist_params = bool(eval_dist) and not only_2d, _dist_up(dist_up), _dist_params(dist_params)
         self.results_dist = OrderedDict()
+        # extension (off by default): LET-AP / LET-APL and the longitudinal diagnostics per split and for <Concat>, in `results_let`
+        self.eval_let, self.let_params, self.results_let = bool(eval_let) and not only_2d, _let_params(let_params), OrderedDict()
         self.overall_imgIds, self.overall_catIds = set(), set()
         self.output_folders = {n: os.path.join(output_folder, n) for n in self.dataset_names}
         for name in self.dataset_names:
@@ -777,7 +902,8 @@ class Omni3DEvaluationHelper:
                 simple_register(name, filter_settings, filter_empty=False)
             ev = Omni3DEvaluator(name, output_dir=self.output_folders[name], filter_settings=filter_settings, only_2d=only_2d,
                                  eval_prox=("Objectron" in name or "SUNRGBD" in name), distributed=False, eval_bev=self.eval_bev,
-                                 bev_up=self.bev_up, eval_dist=self.eval_dist, dist_up=self.dist_up, dist_params=self.dist_params)
+                                 bev_up=self.bev_up, eval_dist=self.eval_dist, dist_up=self.dist_up, dist_params=self.dist_params,
+                                 eval_let=self.eval_let, let_params=self.let_params)
             ev.reset()
             self.evaluators[name] = ev
             self.overall_imgIds.update(ev._omni_api.getImgIds())
@@ -807,6 +933,15 @@ class Omni3DEvaluationHelper:
                 "APDIST@0.5m": rd["AP@0.5m"], "APDIST@1m": rd["AP@1m"], "APDIST@2m": rd["AP@2m"], "APDIST-N": rd["APn"],
                 "APDIST-M": rd["APm"], "APDIST-F": rd["APf"], "mATE": rd["mATE"], "mASE": rd["mASE"], "mAOE": rd["mAOE"]}
 
+    def _let_row(self, rl, categories):
+        """the row of `results_let`: APLET / APLLET = means of the per-category LET-AP / LET-APL like AP3D, the headline columns of
+        both, the mean affinity and the mean signed longitudinal error (metres) of the true positives"""
+        return {"iters": self.iter_label, "APLET": self._mean(rl["AP-" + c] for c in categories if "AP-" + c in rl),
+                "APLET@15": rl["AP15"], "APLET@25": rl["AP25"], "APLET@50": rl["AP50"], "APLET-N": rl["APn"], "APLET-M": rl["APm"],
+                "APLET-F": rl["APf"], "APLLET": self._mean(rl["APL-" + c] for c in categories if "APL-" + c in rl),
+                "APLLET@15": rl["APL15"], "APLLET@25": rl["APL25"], "APLLET@50": rl["APL50"], "APLLET-N": rl["APLn"],
+                "APLLET-M": rl["APLm"], "APLLET-F": rl["APLf"], "mAFF": rl["mAFF"], "mLON": rl["mLON"]}
+
     def _aggregates(self, res2d, res3d, categories):
         nan = float("nan")
         out = {"AP2D": self._mean(res2d["AP-" + c] for c in categories), "AP3D": nan}
@@ -829,6 +964,8 @@ class Omni3DEvaluationHelper:
             log.info("\n" + res["log_str_BEV"].replace("mode=BEV", tag + "BEV"))
         if self.eval_dist and "log_str_DIST" in res:
             log.info("\n" + res["log_str_DIST"].replace("mode=DIST", tag + "DIST"))
+        if self.eval_let and "log_str_LET" in res:
+            log.info("\n" + res["log_str_LET"].replace("mode=LET", tag + "LET"))
         names = self.filter_settings["category_names"]
         r2, r3 = res["bbox_2D"], res.get("bbox_3D", {})
         present = {c for c in names if "AP-" + c in r2}
@@ -846,6 +983,8 @@ class Omni3DEvaluationHelper:
             self.results_bev[dataset_name] = self._bev_row(res["bbox_BEV"], present)
         if self.eval_dist and "bbox_DIST" in res:
             self.results_dist[dataset_name] = self._dist_row(res["bbox_DIST"], present)
+        if self.eval_let and "bbox_LET" in res:
+            self.results_let[dataset_name] = self._let_row(res["bbox_LET"], present)
         logperf.print_ap_category_histogram(dataset_name, self._per_category(r2, r3))
 
     def _per_category(self, r2, r3):
@@ -870,7 +1009,8 @@ class Omni3DEvaluationHelper:
         ordered = [meta.thing_classes[meta.thing_dataset_id_to_contiguous_id[c]] for c in cat_ids]
         categories = set(ordered)
         merged = {}
-        for mode in (["2D"] if self.only_2d else ["2D", "3D"] + (["BEV"] if self.eval_bev else []) + (["DIST"] if self.eval_dist else [])):
+        for mode in (["2D"] if self.only_2d else ["2D", "3D"] + (["BEV"] if self.eval_bev else []) + (["DIST"] if self.eval_dist else [])
+                     + (["LET"] if self.eval_let else [])):
             gts, dts, prox_imgs = [], [], set()
             for name in self.dataset_names:
                 rec = self.results[name].get("bbox_" + mode + "_merge")
@@ -882,7 +1022,7 @@ class Omni3DEvaluationHelper:
                     prox_imgs.update(rec["img_ids"])
             ev = _make_eval(AnnotationIndex(copy.deepcopy(gts), self.overall_imgIds, cat_ids),
                             AnnotationIndex(copy.deepcopy(dts), self.overall_imgIds, cat_ids), mode,
-                            (prox_imgs if prox_imgs else False), self.bev_up, self.dist_up, self.dist_params)
+                            (prox_imgs if prox_imgs else False), self.bev_up, self.dist_up, self.dist_params, self.let_params)
             ev.evaluate()
             ev.accumulate()
             ev.summarize()
@@ -891,11 +1031,15 @@ class Omni3DEvaluationHelper:
                 merged[mode]["AP-" + ordered[0]] = merged[mode]["AP"]
                 if mode == "DIST":
                     merged[mode].update({n + "-" + ordered[0]: merged[mode]["m" + n] for n in _TP_NAMES})
+                if mode == "LET":
+                    merged[mode]["APL-" + ordered[0]] = merged[mode]["APL"]
         r2, r3 = merged["2D"], merged.get("3D", {})
         if "BEV" in merged:
             self.results_bev["<Concat>"] = self._bev_row(merged["BEV"], categories)
         if "DIST" in merged:
             self.results_dist["<Concat>"] = self._dist_row(merged["DIST"], categories)
+        if "LET" in merged:
+            self.results_let["<Concat>"] = self._let_row(merged["LET"], categories)
         general = self._aggregates(r2, r3, categories)
         extras = {k: (r3[k] if not self.only_2d else float("nan")) for k in ("AP15", "AP25", "AP50", "APn", "APm", "APf")}
         self.results_analysis["<Concat>"] = {"iters": self.iter_label, "AP2D": general["AP2D"], "AP3D": general["AP3D"],

@@ -1,0 +1,130 @@
+"""Launchers of csrc/let_iou.hip: the longitudinal-error-tolerant IoU3D of a detection and a ground truth, and the longitudinal
+precision along the recall curve (LET-3D-AP / LET-3D-APL, Hung et al. 2022, the camera-only metric of the Waymo Open Dataset).  The
+reference has no counterpart; the interface follows `kernels/tperr.py`: a box set is the tuple ``(centre, axes, dims, valid)`` of
+`iou3d.cuboid_fit`, box 1 = detection (fitted centre P), box 2 = ground truth (fitted centre G), the sensor at the origin.
+
+Of a pair:
+  lon   float64  ``(G - P) . u`` with ``u = P / |P|``: the signed longitudinal error, positive when the detection is too near
+  aff   float64  ``1 - min(|lon| / T, 1)`` with ``T = max(tol_frac |G|, tol_min)``: the longitudinal affinity in [0, 1]
+  iou   float32  the exact IoU3D of the ground truth and the detection moved to ``P + lon u``, the point of its line of sight closest
+                 to G, when aff > 0; exactly 0 when aff == 0
+(0, 0, NaN) for a gated pair: an invalid box on either side, an index outside its set, or ``|P| <= 1e-8``.
+"""
+import math
+
+import torch
+
+from .. import lib as _lib
+from .iou3d import _check_fit, cuboid_fit
+from .tperr import _check, _empty
+
+TOL_FRAC, TOL_MIN = 0.1, 0.5       # Waymo's values: a convention, not tuned here
+
+
+def check_tolerance(tol_frac, tol_min):
+    """-> (tol_frac, tol_min) as floats; ValueError unless tol_frac is finite and >= 0 and tol_min finite and > 0"""
+    try:
+        f, m = float(tol_frac), float(tol_min)
+    except (TypeError, ValueError):
+        raise ValueError("tol_frac and tol_min must be numbers") from None
+    if not (math.isfinite(f) and f >= 0.0):
+        raise ValueError("tol_frac must be finite and >= 0")
+    if not (math.isfinite(m) and m > 0.0):
+        raise ValueError("tol_min must be finite and > 0")
+    return f, m
+
+
+def let_pairs(fit1, fit2, idx1, idx2, tol_frac=TOL_FRAC, tol_min=TOL_MIN):
+    """(iou (P,) float32, aff (P,) float64, lon (P,) float64) of fitted detection idx1[p] of fit1 against fitted ground truth idx2[p]
+    of fit2 (the tuples of `cuboid_fit`).  idx1 / idx2: 1-D int32 or int64 tensors of equal length.  (0, 0, NaN) for a gated pair;
+    NaN never leaves through iou or aff; two calls give the same bits; P == 0 launches nothing.  ValueError on a wrong argument
+    before anything is launched."""
+    n1, n2 = _check_fit(fit1, "fit1"), _check_fit(fit2, "fit2")
+    for i in (idx1, idx2):
+        if not isinstance(i, torch.Tensor) or i.dim() != 1 or i.dtype not in (torch.int32, torch.int64):
+            raise ValueError("idx1 / idx2 must be 1-D int32 or int64 tensors")
+    if idx1.shape != idx2.shape:
+        raise ValueError("idx1 / idx2 must be of equal length")
+    tol_frac, tol_min = check_tolerance(tol_frac, tol_min)
+    tensors = (*fit1, *fit2, idx1, idx2)
+    if len({t.device for t in tensors}) != 1:
+        raise ValueError("all inputs must live on one device")
+    idx1, idx2 = idx1.to(torch.int32).contiguous(), idx2.to(torch.int32).contiguous()
+    L = _lib.check_device(*tensors)
+    P = idx1.numel()
+    iou, aff, lon = _empty((P,), torch.float32, idx1), _empty((P,), torch.float64, idx1), _empty((P,), torch.float64, idx1)
+    if P > 0:
+        L.call("omni_let_pairs", *[_lib.ptr(t) for t in fit1], n1, *[_lib.ptr(t) for t in fit2], n2, _lib.ptr(idx1), _lib.ptr(idx2), P,
+               tol_frac, tol_min, _lib.ptr(iou), _lib.ptr(aff), _lib.ptr(lon), _lib.stream_of(idx1))
+    return iou, aff, lon
+
+
+def box3d_let(boxes_dt, boxes_gt, tol_frac=TOL_FRAC, tol_min=TOL_MIN):
+    """(N,8,3), (M,8,3) float32 corner lists in the order of `boxgen.UNIT` -> (iou, aff, lon), each (N, M), of every pair, both sides
+    fitted by `cuboid_fit` with its default eps_dim and fit_tol; the rows and columns of invalid boxes are (0, 0, NaN)."""
+    check_tolerance(tol_frac, tol_min)
+    fit1, fit2 = cuboid_fit(boxes_dt), cuboid_fit(boxes_gt)
+    N, M, dev = boxes_dt.shape[0], boxes_gt.shape[0], boxes_dt.device
+    idx1 = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(M)
+    idx2 = torch.arange(M, dtype=torch.int32, device=dev).repeat(N)
+    iou, aff, lon = let_pairs(fit1, fit2, idx1, idx2, tol_frac, tol_min)
+    return iou.view(N, M), aff.view(N, M), lon.view(N, M)
+
+
+def accumulate_let(order, cat_off, rank, dt_match, dt_ignore, pair_row, aff, lon, npig, has_e, rec_thrs, max_dets):
+    """The longitudinal precision along the recall curve, one wave per (category, depth range, maxDets, threshold) ->
+    (precision_l (T, R, K, A, M), tp_affinity (T, K, A, M), tp_lon (T, K, A, M)), all float64.
+
+    order (N,) int32 / cat_off (K+1,) int32 / rank (sumD,) int32: the merge order of `Omni3Deval.accumulate` (detections by category,
+    descending score) and the rank of a detection inside its (image, category) list; dt_match (A, T, sumD) int32 / dt_ignore
+    (A, T, sumD) uint8: the tables of `evaluate_groups`; pair_row (sumD,) int64: the row of `aff` / `lon` (P,) float64 of the pair
+    (detection, ground truth 0 of its group); npig (K, A) int32 the number of non-ignored ground truths, has_e (K,) int32, rec_thrs
+    (R,) float64 ascending, max_dets (M,) int32.
+    A detection with rank < max_dets[m] is included; one with dt_match >= 0 and dt_ignore == 0 is a true positive, its pair is row
+    pair_row[d] + dt_match[a, t, d].  At a list position prec_L = (sum of aff over the true positives so far) / (tp + fp + eps);
+    precision_l is prec_L made monotone from the right and sampled at rec_thrs as `precision` is, -1 in the same cells (npig == 0 or
+    has_e == 0); tp_affinity / tp_lon are the means of aff / lon over the true positives, -1 without one.  Two calls give the same
+    bits."""
+    _check(cat_off, "cat_off", torch.int32, (cat_off.numel() if isinstance(cat_off, torch.Tensor) else 0,))
+    K = cat_off.numel() - 1
+    if K < 0:
+        raise ValueError("cat_off must hold K + 1 offsets")
+    _check(order, "order", torch.int32, (order.numel() if isinstance(order, torch.Tensor) else 0,))
+    if not isinstance(dt_match, torch.Tensor) or dt_match.dim() != 3 or dt_match.shape[0] < 1 or dt_match.shape[1] < 1:
+        raise ValueError("dt_match must have shape (A, T, sumD) with A >= 1 and T >= 1")
+    A, T, sumD = dt_match.shape
+    _check(dt_match, "dt_match", torch.int32, (A, T, sumD))
+    _check(dt_ignore, "dt_ignore", torch.uint8, (A, T, sumD))
+    _check(rank, "rank", torch.int32, (sumD,))
+    _check(pair_row, "pair_row", torch.int64, (sumD,))
+    if not isinstance(aff, torch.Tensor) or aff.dim() != 1:
+        raise ValueError("aff must have shape (P,)")
+    P = aff.shape[0]
+    _check(aff, "aff", torch.float64, (P,))
+    _check(lon, "lon", torch.float64, (P,))
+    _check(npig, "npig", torch.int32, (K, A))
+    _check(has_e, "has_e", torch.int32, (K,))
+    if not isinstance(rec_thrs, torch.Tensor) or rec_thrs.dim() != 1 or rec_thrs.numel() < 1:
+        raise ValueError("rec_thrs must be 1-D and not empty")
+    _check(rec_thrs, "rec_thrs", torch.float64, (rec_thrs.numel(),))
+    if not isinstance(max_dets, torch.Tensor) or max_dets.dim() != 1 or max_dets.numel() < 1:
+        raise ValueError("max_dets must be 1-D and not empty")
+    _check(max_dets, "max_dets", torch.int32, (max_dets.numel(),))
+    tensors = (order, cat_off, rank, dt_match, dt_ignore, pair_row, aff, lon, npig, has_e, rec_thrs, max_dets)
+    if len({t.device for t in tensors}) != 1:
+        raise ValueError("all inputs must live on one device")
+    off = cat_off.tolist()
+    if off[0] != 0 or off[-1] != order.numel() or any(b < a for a, b in zip(off, off[1:])):
+        raise ValueError("cat_off must ascend from 0 to len(order)")
+    if order.numel() and (int(order.min()) < 0 or int(order.max()) >= sumD):
+        raise ValueError("order must index the sumD detections")
+    L = _lib.check_device(*tensors)
+    R, M, dev = rec_thrs.numel(), max_dets.numel(), order.device
+    prec_l = torch.full((T, R, K, A, M), -1.0, dtype=torch.float64, device=dev)
+    tp_aff = torch.full((T, K, A, M), -1.0, dtype=torch.float64, device=dev)
+    tp_lon = torch.full((T, K, A, M), -1.0, dtype=torch.float64, device=dev)
+    if K > 0:
+        L.call("omni_eval_accumulate_let", _lib.ptr(order), _lib.ptr(cat_off), _lib.ptr(rank), _lib.ptr(dt_match), _lib.ptr(dt_ignore),
+               _lib.ptr(pair_row), _lib.ptr(aff), _lib.ptr(lon), P, _lib.ptr(npig), _lib.ptr(has_e), _lib.ptr(rec_thrs), _lib.ptr(max_dets),
+               K, A, M, T, R, sumD, _lib.ptr(prec_l), _lib.ptr(tp_aff), _lib.ptr(tp_lon), _lib.stream_of(order))
+    return prec_l, tp_aff, tp_lon
