@@ -20,7 +20,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from omni3d_amd.cubercnn import util, vis  # noqa: E402
-from omni3d_amd.cubercnn.config import add_nms3d_exact_config, get_cfg_defaults  # noqa: E402
+from omni3d_amd.cubercnn.config import add_nms3d_exact_config, add_tta_config, build_tta_model, get_cfg_defaults  # noqa: E402
 from omni3d_amd.cubercnn.data.dataset_mapper import DatasetMapper3D  # noqa: E402
 from omni3d_amd.d2.checkpoint import DetectionCheckpointer  # noqa: E402
 from omni3d_amd.d2.config import get_cfg  # noqa: E402
@@ -88,6 +88,7 @@ def setup(args):
     cfg = get_cfg()
     get_cfg_defaults(cfg)
     add_nms3d_exact_config(cfg)                   # TEST.NMS_3D.* with IOU_TYPE: settable from the YAML file and from `opts`
+    add_tta_config(cfg)                           # TEST.AUG.*: test-time augmentation, likewise
     config_file = args.config_file
     if config_file.startswith(util.CubeRCNNHandler.PREFIX):
         config_file = util.CubeRCNNHandler._get_local_path(util.CubeRCNNHandler, config_file)
@@ -97,6 +98,8 @@ def setup(args):
         cfg.merge_from_list(["TEST.NMS_3D.ENABLED", True, "TEST.NMS_3D.IOU_THRESH", float(args.nms3d)])
     if getattr(args, "nms3d_iou", None) is not None:
         cfg.merge_from_list(["TEST.NMS_3D.IOU_TYPE", args.nms3d_iou])
+    if getattr(args, "tta", False):
+        cfg.merge_from_list(["TEST.AUG.ENABLED", True])
     cfg.freeze()
     default_setup(cfg, args)
     return cfg
@@ -111,7 +114,7 @@ def main(args):
     model = build_model(cfg)
     DetectionCheckpointer(model, save_dir=cfg.OUTPUT_DIR).resume_or_load(cfg.MODEL.WEIGHTS, resume=True)
     with torch.no_grad():
-        do_test(args, cfg, model)
+        do_test(args, cfg, build_tta_model(cfg, model))        # (the model itself unless TEST.AUG.ENABLED)
 
 
 def argument_parser():
@@ -126,6 +129,8 @@ def argument_parser():
                         help="drop duplicate cuboids across categories by IoU3D above THRESH (TEST.NMS_3D.ENABLED True + IOU_THRESH)")
     parser.add_argument("--nms3d-iou", choices=("evaluator", "exact"), default=None,
                         help="IoU3D --nms3d decides with: the evaluator's pair algorithm, or exact geometry (TEST.NMS_3D.IOU_TYPE)")
+    parser.add_argument("--tta", default=False, action="store_true",
+                        help="test-time augmentation with the defaults of TEST.AUG: the image and its mirror image, cuboids fused (TEST.AUG.ENABLED True)")
     parser.add_argument("--display", default=False, action="store_true", help="accepted and ignored (logged)")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="'KEY VALUE' pairs that override the config")
     return parser

@@ -111,6 +111,40 @@ int omni_nms3d_exact(const float* verts, const float* score, const int* cls, con
                      int class_agnostic, float eps_coplanar, float eps_nonzero, float* iou, int* keep, int* order, int* new_count,
                      int* invalid, void* stream);
 
+/* Weighted fusion of overlapping cuboids among the fixed (B, S) slots (csrc/nms3d.hip): the merge step of test-time augmentation,
+ * where the slots of one image hold the detections of several views in one camera frame.  Where omni_nms3d_exact keeps the best
+ * cuboid of a group and drops the rest, this turns the group into ONE cuboid: weighted-boxes-fusion carried over to oriented 3D
+ * boxes.  The reference has no counterpart (detectron2's GeneralizedRCNNWithTTA merges 2D boxes by NMS).
+ *   verts, score, cls, count, iou_thr, class_agnostic, eps_coplanar, eps_nonzero   as in omni_nms3d_exact
+ *   aux (B*S,A)       [null when A == 0] further columns that are averaged with the geometry (2D boxes, class scores, ...)
+ *   views             >= 1, the number of views the slots were gathered from
+ * Two launches.  (1) the pair-matrix launch of omni_nms3d_exact, unchanged: iou (B,S,S), every entry written.  (2) one 256-thread
+ * workgroup per image.  Ranking: that of omni_nms3d (descending score, ties to the lower slot); a slot takes part iff its score is
+ * finite, it passes the validity test and the fit of omni_cuboid_fit (eps_dim 1e-8, fit_tol 1e-3).  Clustering: the next candidate
+ * that is still live is a HEAD; its cluster is itself plus every later live candidate j with iou[head][j] > iou_thr (strict), which
+ * are then dead -- greedy, not transitive.  A slot < count[b] that takes no part is a cluster of its own.  Fusion, in double, members
+ * in rank order, w = max(score, 0): a member's fitted axes are first renamed to the head's -- the first permutation p of (0,1,2) in
+ * lexicographic order that maximises sum_k |h_k . x_p(k)|, each axis with the sign that makes h_k . x_p(k) >= 0, the dimensions
+ * permuted alike (the same body can be reported with its axes permuted and flipped) -- then centre and dimensions are the w-weighted
+ * means, the axes are the orthogonal polar factor of the w-weighted mean of the aligned axis matrices (8 Newton steps
+ * X <- (X + X^-T) / 2), and every aux column is the same weighted mean.  A cluster of one member, or of total weight 0, is its head
+ * bit for bit (corners and aux copied).  Out, per image in DESCENDING fused score (ties to the lower head slot; a score that is not
+ * finite sorts last, by slot), rows >= out_count[b] zeroed with out_head -1:
+ *   cluster (B,S) int32        head slot of the cluster of slot s < count[b], -1 behind the count
+ *   out_verts (B*S,8,3)        corners of the fused cuboid in the order of omni_iou_box3d, in the head's axis naming
+ *   out_centre (B*S,3), out_axes (B*S,3,3) (row k = unit axis k), out_dims (B*S,3)   what omni_cuboid_fit gives for out_verts
+ *                              (0 for a passed-through slot whose corners are no cuboid)
+ *   out_score (B*S)            sum of the members' raw scores / max(members, views): a cuboid seen in one of T views gets score / T
+ *   out_cls (B*S) int32        the head's class;  out_aux (B*S,A);  out_size (B*S) int32 members;  out_head (B*S) int32 head slot
+ *   out_count (B) int32        number of clusters
+ *   invalid (1) int32          [nullable] += slots < count[b] whose fit fails, as in omni_nms3d_exact (the caller zeroes it)
+ * No atomics but that one, no arrival order: one thread walks a cluster, so two runs give the same bits.  S > 1024, a negative size,
+ * views < 1 or a missing array return OMNI_ERR_ARG before any launch; B == 0 or S == 0 launches nothing. */
+int omni_fuse3d(const float* verts, const float* score, const int* cls, const int* count, const float* aux, int B, int S, int A, int views,
+                float iou_thr, int class_agnostic, float eps_coplanar, float eps_nonzero, float* iou, int* cluster, float* out_verts,
+                float* out_centre, float* out_axes, float* out_dims, float* out_score, int* out_cls, float* out_aux, int* out_size,
+                int* out_head, int* out_count, int* invalid, void* stream);
+
 /* IoU in the bird's-eye view (csrc/bev_iou.hip): the overlap of the cuboids' footprints on the ground plane, the matching criterion
  * of AP-BEV.  The reference has no counterpart: it EXTENDS `box3d_overlap` / omni_iou_box3d_pairs with a third kind of overlap next
  * to the 2D and 3D ones of Omni3Deval.computeIoU (omni3d_evaluation.py:1359-1431).

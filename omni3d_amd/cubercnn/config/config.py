@@ -170,3 +170,58 @@ def let_eval_args(cfg):
     if not (math.isfinite(tmin) and tmin > 0.0):
         raise ValueError("TEST.EVAL_LET.LON_TOL_MIN must be finite and > 0")
     return {"eval_let": bool(get("ENABLED")), "let_params": {"lonTolFrac": frac, "lonTolMin": tmin}}
+
+
+_TTA = {"MIN_SIZES": (), "MAX_SIZE": 4000, "FLIP": True, "FUSE_IOU_THRESH": 0.5, "CLASS_AGNOSTIC": False}
+
+
+def add_tta_config(cfg):
+    """TEST.AUG.*: test-time augmentation (`RCNN3DWithTTA`, meta_arch/tta.py): the image is run at several sizes and mirrored, the
+    views' cuboids are brought into one camera frame and overlapping ones are fused into one (csrc/nms3d.hip, omni_fuse3d).
+    detectron2 defines the node and its first three keys; `get_cfg_defaults` carries it as {"ENABLED": False}, so the keys are added to
+    the existing node by this call.  Idempotent: values already set are kept.
+    MIN_SIZES: the shorter sides of the views, capped by MAX_SIZE (detectron2's default 4000); () = the size the loader delivered only.
+    FLIP doubles the views.  FUSE_IOU_THRESH: cuboids of exact IoU3D above it are one object; 0.5 is a convention (the loosest
+    threshold at which two boxes are commonly called the same detection), not a tuned value.  CLASS_AGNOSTIC False: the views of one
+    object should agree on its class.  Whether any of this raises AP3D on real data has not been measured."""
+    if "AUG" not in cfg.TEST:
+        cfg.TEST.AUG = CN({"ENABLED": False})
+    cfg.TEST.AUG.setdefault("ENABLED", False)
+    for key, value in _TTA.items():
+        cfg.TEST.AUG.setdefault(key, value)
+    return cfg
+
+
+def tta_args(cfg):
+    """TEST.AUG -> the keyword arguments of `RCNN3DWithTTA`: `RCNN3DWithTTA(cfg, model)` reads them through this.  Keys the node does
+    not carry (a cfg without `add_tta_config`) take their defaults.  ValueError unless MIN_SIZES is a sequence of integers > 0,
+    MAX_SIZE an integer > 0 and FUSE_IOU_THRESH a finite number >= 0."""
+    import math
+    node = cfg.TEST.get("AUG")
+    have = dict(node) if node is not None else {}
+    get = lambda k: have.get(k, _TTA.get(k, False))       # noqa: E731
+    sizes = get("MIN_SIZES")
+    if isinstance(sizes, (str, bytes)) or not hasattr(sizes, "__iter__"):
+        raise ValueError("TEST.AUG.MIN_SIZES must be a sequence of integers")
+    sizes = tuple(sizes)
+    if any(isinstance(v, bool) or not isinstance(v, int) or v <= 0 for v in sizes):
+        raise ValueError("TEST.AUG.MIN_SIZES must hold integers > 0")
+    max_size = get("MAX_SIZE")
+    if isinstance(max_size, bool) or not isinstance(max_size, int) or max_size <= 0:
+        raise ValueError("TEST.AUG.MAX_SIZE must be an integer > 0")
+    try:
+        thr = float(get("FUSE_IOU_THRESH"))
+    except (TypeError, ValueError):
+        raise ValueError("TEST.AUG.FUSE_IOU_THRESH must be a number") from None
+    if not (math.isfinite(thr) and thr >= 0.0):
+        raise ValueError("TEST.AUG.FUSE_IOU_THRESH must be finite and >= 0")
+    return {"enabled": bool(get("ENABLED")), "min_sizes": sizes, "max_size": max_size, "flip": bool(get("FLIP")), "fuse_iou_thresh": thr,
+            "class_agnostic": bool(get("CLASS_AGNOSTIC"))}
+
+
+def build_tta_model(cfg, model):
+    """the model wrapped for test-time augmentation when TEST.AUG.ENABLED, else the model itself"""
+    if not tta_args(cfg)["enabled"]:
+        return model
+    from ..modeling.meta_arch.tta import RCNN3DWithTTA
+    return RCNN3DWithTTA(cfg, model)

@@ -273,8 +273,8 @@ class RCNN3D(nn.Module):
         proposals, _ = self.proposal_generator(images, features, None, targets=packed)
         return roi_heads_inference_device(self.roi_heads, [features[f] for f in self.roi_heads.in_features], proposals, packed)
 
-    def _replayed_inference(self, batched_inputs, do_postprocess):
-        """-> results of a pass replayed from its captured hipGraph, or None (meta_arch/infer_replay.py)"""
+    def _replayed_raw(self, batched_inputs):
+        """-> (device outputs, image sizes) of a pass replayed from its captured hipGraph, or None (meta_arch/infer_replay.py)"""
         if not (self._all_packed() and getattr(self.roi_heads, "replayable_inference", False)):
             return None
         rep = self.__dict__.get("_omni_infer")
@@ -289,7 +289,11 @@ class RCNN3D(nn.Module):
             st.enter_context(HF.wino_weight_scope(self))
             st.enter_context(_wino.f22_only())
             return st
-        got = rep.run(batched_inputs, context)
+        return rep.run(batched_inputs, context)
+
+    def _replayed_inference(self, batched_inputs, do_postprocess):
+        """-> results of a replayed pass, or None"""
+        got = self._replayed_raw(batched_inputs)
         if got is None:
             return None
         from ..roi_heads.inference import collect_detections, postprocess

@@ -1,5 +1,6 @@
 """Launchers for the detection-logic kernels: csrc/rpn_roi.hip, roi_align.hip, box_loss.hip,
 cube_head.hip, optim.hip.  Thin: allocate outputs, pass raw pointers + the current stream."""
+import collections
 import ctypes
 import math
 
@@ -397,6 +398,7 @@ def train_vis_pick(pred, head, uncert_off, rois, cls, nfg, K, weights=(10.0, 10.
 
 
 NMS3D_METHODS = ("evaluator", "exact")
+NMS3D_MAX_SLOTS = 1024     # NMS3D_MAXS of csrc/nms3d.hip: the slots per image the LDS arrays of its second launch hold
 
 
 def nms3d(verts, scores, cls, count, iou_thr, class_agnostic=True, eps_coplanar=1e-4, eps_nonzero=1e-8, method="evaluator"):
@@ -430,6 +432,49 @@ def nms3d(verts, scores, cls, count, iou_thr, class_agnostic=True, eps_coplanar=
            float(eps_coplanar), float(eps_nonzero), _lib.ptr(iou), _lib.ptr(keep), _lib.ptr(order), _lib.ptr(new_count), _lib.ptr(overflow),
            _lib.stream_of(verts))
     return keep, order, new_count, iou, overflow
+
+
+Fused3D = collections.namedtuple("Fused3D", "verts centre axes dims score cls aux size head count cluster iou invalid")
+
+
+def fuse3d(verts, scores, cls, count, iou_thr, views=1, aux=None, class_agnostic=False, eps_coplanar=1e-4, eps_nonzero=1e-8):
+    """Weighted fusion of overlapping cuboids among the fixed slots (csrc/nms3d.hip, omni_fuse3d): the inputs of `nms3d`, `views`
+    >= 1 and optionally aux (B*S, A) float32 columns that are averaged with the geometry -> Fused3D of verts (B*S, 8, 3), centre
+    (B*S, 3), axes (B*S, 3, 3), dims (B*S, 3), score (B*S,), cls (B*S,) int32, aux (B*S, A), size (B*S,) int32 members, head (B*S,) int32
+    head slot, count (B,) int32 clusters per image, cluster (B, S) int32 head slot of every slot, iou (B, S, S), invalid (1,) int32.
+    Rows of one image come in descending fused score and are zero (head -1) behind its count.  Two launches, no host synchronisation."""
+    if count.dim() != 1 or count.dtype != torch.int32:
+        raise ValueError(f"fuse3d: count must be int32 of shape (B,), got {count.dtype} {tuple(count.shape)}")
+    B = count.shape[0]
+    if verts.dim() != 3 or tuple(verts.shape[1:]) != (8, 3) or verts.dtype != torch.float32 or (B and verts.shape[0] % B) or (not B and verts.shape[0]):
+        raise ValueError(f"fuse3d: verts must be float32 of shape (B*S, 8, 3) for B = {B}, got {verts.dtype} {tuple(verts.shape)}")
+    N = verts.shape[0]
+    S = N // B if B else 0
+    if scores.dtype != torch.float32 or tuple(scores.shape) != (N,):
+        raise ValueError(f"fuse3d: scores must be float32 of shape ({N},), got {scores.dtype} {tuple(scores.shape)}")
+    if cls.dtype != torch.int32 or cls.numel() != N or tuple(cls.shape) not in ((N,), (B, S)):
+        raise ValueError(f"fuse3d: cls must be int32 of shape ({B}, {S}) or ({N},), got {cls.dtype} {tuple(cls.shape)}")
+    if int(views) != views or views < 1:
+        raise ValueError(f"fuse3d: views must be an integer >= 1, got {views!r}")
+    if aux is not None and (aux.dim() != 2 or aux.shape[0] != N or aux.dtype != torch.float32):
+        raise ValueError(f"fuse3d: aux must be float32 of shape ({N}, A), got {aux.dtype} {tuple(aux.shape)}")
+    if S > NMS3D_MAX_SLOTS:
+        raise ValueError(f"fuse3d: {S} slots per image, the kernel holds {NMS3D_MAX_SLOTS}")
+    for name, a in (("verts", verts), ("scores", scores), ("cls", cls), ("aux", aux)):
+        if a is not None and not a.is_contiguous():
+            raise ValueError(f"fuse3d: {name} must be contiguous")
+    A = 0 if aux is None else aux.shape[1]
+    L = _dev(verts, scores, cls, count, aux)
+    o = Fused3D(verts=_empty((N, 8, 3), torch.float32, verts), centre=_empty((N, 3), torch.float32, verts),
+                axes=_empty((N, 3, 3), torch.float32, verts), dims=_empty((N, 3), torch.float32, verts), score=_empty((N,), torch.float32, verts),
+                cls=_empty((N,), torch.int32, verts), aux=_empty((N, A), torch.float32, verts), size=_empty((N,), torch.int32, verts),
+                head=_empty((N,), torch.int32, verts), count=_empty((B,), torch.int32, verts), cluster=_empty((B, S), torch.int32, verts),
+                iou=_empty((B, S, S), torch.float32, verts), invalid=torch.zeros(1, dtype=torch.int32, device=verts.device))
+    L.call("omni_fuse3d", _lib.ptr(verts), _lib.ptr(scores), _lib.ptr(cls), _lib.ptr(count), _lib.ptr(aux) if A else None, B, S, A, int(views),
+           float(iou_thr), int(bool(class_agnostic)), float(eps_coplanar), float(eps_nonzero), _lib.ptr(o.iou), _lib.ptr(o.cluster),
+           _lib.ptr(o.verts), _lib.ptr(o.centre), _lib.ptr(o.axes), _lib.ptr(o.dims), _lib.ptr(o.score), _lib.ptr(o.cls),
+           _lib.ptr(o.aux) if A else None, _lib.ptr(o.size), _lib.ptr(o.head), _lib.ptr(o.count), _lib.ptr(o.invalid), _lib.stream_of(verts))
+    return o
 
 
 CUBE_MODE_BASE = 0xDC0     # configs/Base.yaml: z direct, dims priors 'exp', 6d pose, allocentric, virtual depth, chamfer, confidence, joint
