@@ -899,6 +899,32 @@ int omni_eval_accumulate(const int* order, const int* cat_off, const int* rank, 
                          const int* max_dets, int K, int A, int M, int T, int R, int sumD, double* precision, double* recall,
                          double* scores, void* stream);
 
+/* The image-level bootstrap of Omni3Deval.accumulate (csrc/eval_bootstrap.hip): AP and recall of B resampled data sets from one set of
+ * match tables, for `Omni3Deval.bootstrap`.  The reference has no counterpart.  Replicate b is the row weights[b] (I) of non-negative
+ * image multiplicities; its result is by definition what omni_eval_accumulate gives on the data set that holds image i weights[b][i]
+ * times (copies adjacent in the image order): a detection d counts as weights[b][det_img[d]] consecutive identical entries of the merge
+ * order.  max_weight: the largest weight of the table; a weight outside [0, max_weight] counts as 0.
+ * omni_eval_bootstrap_counts: the groups are the (image, category) groups in (category, image) order: grp_off (K+1) their ranges per
+ * category, grp_img (G) the index of the group's image in [0, I), grp_npig (G,A) the group's non-ignored ground truths per range,
+ * sumG an upper bound of every column sum of grp_npig (the number of ground truths).  npig_b (B,K,A) = the weighted sums over the groups
+ * of the category, has_e_b (B,K) = 1 when a group of the category has a positive weight.  One 64-lane wave per (b, k), integer sums.
+ * omni_eval_bootstrap: order, cat_off, rank, dt_match / dt_ignore (A,T,sumD), rec_thrs, max_dets as in omni_eval_accumulate; det_img
+ * (sumD) the index of a detection's image in [0, I) (a detection with another index has weight 0).  Out, doubles pre-filled with -1 by
+ * the caller: ap (B,T,K,A,M) = (the sum over r of the replicate's `precision`) / R, ar (B,T,K,A,M) its `recall`; both stay -1 where
+ * omni_eval_accumulate writes nothing (has_e_b 0 or npig_b 0).  ar is bit for bit the recall of the duplicated data set; the R
+ * precisions are bit for bit its precisions, summed in the order of the backward walk (not in ascending r: ap differs from that sum by
+ * rounding only).  One workgroup per (k, a, m, t) and 64 replicates: the list is staged in LDS once for all of them.  No atomics: two
+ * launches, and any split of the replicates over several calls, give the same bits.
+ * Both return OMNI_ERR_ARG before any launch on B <= 0, a non-positive A / M / T / R, a negative K / sumD / G / sumG / I / max_weight, a
+ * missing array, I >= 2^29, and when a weighted count could reach 2^31: sumD x max_weight >= 2^31 (omni_eval_bootstrap) or sumG x
+ * max_weight >= 2^31 (omni_eval_bootstrap_counts).  K == 0 launches nothing; sumD == 0 is valid (ap = ar = 0 where there is ground truth). */
+int omni_eval_bootstrap_counts(const int* grp_off, const int* grp_img, const int* grp_npig, const int* weights, int max_weight, int K,
+                               int A, int G, int sumG, int B, int I, int* npig_b, int* has_e_b, void* stream);
+int omni_eval_bootstrap(const int* order, const int* cat_off, const int* rank, const int* dt_match, const unsigned char* dt_ignore,
+                        const int* det_img, const int* weights, int max_weight, const int* npig_b, const int* has_e_b,
+                        const double* rec_thrs, const int* max_dets, int K, int A, int M, int T, int R, int sumD, int B, int I,
+                        double* ap, double* ar, void* stream);
+
 /* Drawing predicted cuboids (csrc/render.hip).  The reference renders them with pytorch3d's mesh rasteriser and paints the edges
  * with OpenCV; here every pixel casts its ray (through the pixel centre (x + 0.5, y + 0.5)) against the boxes themselves.
  *

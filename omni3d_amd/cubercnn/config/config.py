@@ -172,6 +172,44 @@ def let_eval_args(cfg):
     return {"eval_let": bool(get("ENABLED")), "let_params": {"lonTolFrac": frac, "lonTolMin": tmin}}
 
 
+_BOOTSTRAP = {"ENABLED": False, "NUM_REPLICATES": 1000, "SEED": 0, "CONFIDENCE": 0.95}
+
+
+def add_bootstrap_config(cfg):
+    """TEST.BOOTSTRAP.*: image-level bootstrap confidence intervals next to every AP the evaluation reports (`Omni3Deval.bootstrap`,
+    csrc/eval_bootstrap.hip): the test images are resampled with replacement NUM_REPLICATES times (generator seeded with SEED), AP is
+    recomputed for each replicate from the one set of match tables, and the percentile interval at CONFIDENCE is reported.  The
+    reference has no such option and `get_cfg_defaults` stays key for key what the reference defines, so, as with
+    `add_let_eval_config`, the node is absent until this call; without it no interval is computed.  Idempotent: values already set
+    are kept.  1000 replicates and 95 % are the customary choices, not tuned values."""
+    if "BOOTSTRAP" not in cfg.TEST:
+        cfg.TEST.BOOTSTRAP = CN()
+    for key, value in _BOOTSTRAP.items():
+        cfg.TEST.BOOTSTRAP.setdefault(key, value)
+    return cfg
+
+
+def bootstrap_eval_args(cfg):
+    """TEST.BOOTSTRAP -> the keyword argument of `Omni3DEvaluationHelper` / `Omni3DEvaluator`:
+    `Omni3DEvaluationHelper(names, filter_settings, folder, **bootstrap_eval_args(cfg))`.  A cfg without the node, or ENABLED False:
+    {"bootstrap": None}, the feature off.  ValueError unless NUM_REPLICATES is an integer >= 1, SEED an integer >= 0 and CONFIDENCE
+    lies in (0, 1)."""
+    node = cfg.TEST.get("BOOTSTRAP")
+    if node is None:
+        node = _BOOTSTRAP
+    get = (lambda k: node[k]) if isinstance(node, dict) else (lambda k: getattr(node, k))       # noqa: E731
+    n, seed, conf = get("NUM_REPLICATES"), get("SEED"), get("CONFIDENCE")
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError("TEST.BOOTSTRAP.NUM_REPLICATES must be an integer >= 1")
+    if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
+        raise ValueError("TEST.BOOTSTRAP.SEED must be an integer >= 0")
+    if isinstance(conf, bool) or not isinstance(conf, (int, float)) or not 0.0 < float(conf) < 1.0:
+        raise ValueError("TEST.BOOTSTRAP.CONFIDENCE must lie in (0, 1)")
+    if not bool(get("ENABLED")):
+        return {"bootstrap": None}
+    return {"bootstrap": {"n": n, "seed": seed, "confidence": float(conf)}}
+
+
 _TTA = {"MIN_SIZES": (), "MAX_SIZE": 4000, "FLIP": True, "FUSE_IOU_THRESH": 0.5, "CLASS_AGNOSTIC": False}
 
 

@@ -16,7 +16,12 @@ curve (ATE / ASE / AOE); `eval_dist` switches it on in the two drivers, off by d
 A third one: mode "LET" = the longitudinal-error-tolerant metrics of the Waymo camera-only benchmark (`let_overlap_groups`,
 csrc/let_iou.hip): a detection may slide along its own line of sight onto the ground truth within a tolerance that grows with range, the
 exact IoU3D of the slid box decides the match (LET-AP), and a second table scales precision by how little sliding was needed (LET-APL);
-`eval_let` switches it on in the two drivers, off by default.  See `Omni3Deval`."""
+`eval_let` switches it on in the two drivers, off by default.  See `Omni3Deval`.
+
+A fourth one, for every mode: `Omni3Deval.bootstrap` / `bootstrap_compare` = image-level bootstrap confidence intervals of AP / AR and
+the paired comparison of two prediction sets.  The match tables of evaluate() are kept and all replicates are accumulated in one launch
+from integer image multiplicities (`kernels.bootstrap`, csrc/eval_bootstrap.hip); `bootstrap` switches it on in the two drivers, off by
+default.  See `Omni3Deval.bootstrap`."""
 import copy
 import datetime
 import json
@@ -184,6 +189,170 @@ def evaluate_groups(ious_flat, dt_sizes, gt_sizes, gt_ignore, gt_range, dt_range
     L.call("omni_eval_match", _p(ious_flat), _p(iou_off), _p(dt_off), _p(gt_off), _p(gt_ignore), _p(gt_range), _p(dt_range), _p(areas),
            _p(thrs), ng, A, T, sumD, sumG, int(gt_sizes.max()) if ng else 0, _p(out["dt_match"]), _p(out["gt_match"]),
            _p(out["dt_ignore"]), _p(out["gt_order"]), _p(out["gt_ignore"]), iou3d._lib.stream_of(ious_flat))
+    return out
+
+
+# =====================================================================================================================
+# the headline slots of summarize(), shared with the bootstrap
+# =====================================================================================================================
+def _stat_thresholds(mode):
+    return [0.5, 0.75, 0.95] if mode == "2D" else [0.5, 1.0, 2.0] if mode == "DIST" else [0.15, 0.25, 0.50]
+
+
+def _stat_slots(p, mode):
+    """the 13 `stats` of summarize() as (ap, iouThr, areaRng label, maxDets): AP overall, at three thresholds, in three ranges; AR at
+    the three maxDets and in three ranges"""
+    thres, L, md = _stat_thresholds(mode), p.areaRngLbl, p.maxDets
+    return [(1, None, "all", 100)] + [(1, thres[i], "all", md[2]) for i in range(3)] + [(1, None, L[1 + i], md[2]) for i in range(3)] \
+        + [(0, None, "all", md[i]) for i in range(3)] + [(0, None, L[1 + i], md[2]) for i in range(3)]
+
+
+def _slot_indices(p, mode, ap, iouThr, areaRng, maxDets):
+    """-> (indices of the thresholds or None = all, of the ranges, of the maxDets) one slot of summarize() averages over"""
+    shown = p.distThrs if mode == "DIST" else p.iouThrs            # DIST: thresholds are named, and looked up, in metres
+    aind = [i for i, a in enumerate(p.areaRngLbl) if a == areaRng]
+    mind = [i for i, m in enumerate(p.maxDets) if m == maxDets]
+    tind = None
+    if iouThr is not None:
+        tind = np.where(np.isclose(iouThr, np.asarray(shown).astype(float)))[0] if ap == 1 else np.where(iouThr == np.asarray(shown))[0]
+    return tind, aind, mind
+
+
+BOOTSTRAP_CHUNK = 256       # replicates per launch of `Omni3Deval.bootstrap`
+
+
+def _check_confidence(confidence):
+    try:
+        c = float(confidence)
+    except (TypeError, ValueError):
+        raise ValueError("confidence must be a number") from None
+    if not 0.0 < c < 1.0:
+        raise ValueError("confidence must lie in (0, 1)")
+    return c
+
+
+def bootstrap_weights(img_ids, n=1000, seed=0, weights=None, strata=None):
+    """The (n, I) int32 replicate table of `Omni3Deval.bootstrap`: `weights` checked (columns in the order of img_ids), or n rows drawn
+    by np.random.default_rng(seed), one multinomial per stratum in sorted label order."""
+    I = len(img_ids)
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.shape[0] < 1 or w.shape[1] != I:
+            raise ValueError("weights must have shape (n, %d): one column per image of params.imgIds" % I)
+        if not np.issubdtype(w.dtype, np.integer):
+            if not np.issubdtype(w.dtype, np.floating) or not np.isfinite(w).all() or (w != np.round(w)).any():
+                raise ValueError("weights must be integers")
+        if (w < 0).any():
+            raise ValueError("weights must be >= 0")
+        if w.size and w.max() > np.iinfo(np.int32).max:
+            raise ValueError("weights must fit 32 bits")
+        return np.ascontiguousarray(w.astype(np.int32))
+    if int(n) != n or n < 1:
+        raise ValueError("n must be a positive integer")
+    if strata is None:
+        labels = [0] * I
+    else:
+        try:
+            labels = [strata[i] for i in img_ids]
+        except KeyError as e:
+            raise ValueError("strata has no label for image %r" % (e.args[0],)) from None
+    g = np.random.default_rng(seed)
+    w = np.zeros((int(n), I), np.int32)
+    for label in sorted(set(labels)):
+        cols = np.flatnonzero(np.array([lb == label for lb in labels], dtype=bool))
+        w[:, cols] = g.multinomial(len(cols), np.full(len(cols), 1.0 / len(cols)), size=int(n))
+    return w
+
+
+def _replicate_summary(values, confidence):
+    """values (n, S), -1 = no value -> mean, se (ddof=1), ci (S, 2), n_valid over the replicates with a value, per column"""
+    S = values.shape[1]
+    mean, se, ci, n_valid = np.full(S, np.nan), np.full(S, np.nan), np.full((S, 2), np.nan), np.zeros(S, np.int64)
+    for j in range(S):
+        v = values[:, j][values[:, j] > -1]
+        n_valid[j] = v.size
+        if v.size:
+            mean[j] = v.mean()
+            ci[j] = np.quantile(v, [(1.0 - confidence) / 2.0, (1.0 + confidence) / 2.0])
+        if v.size > 1:
+            se[j] = v.std(ddof=1)
+    return mean, se, ci, n_valid
+
+
+def _masked_mean(vals, axes):
+    """mean over `axes` of the entries > -1, -1 where there is none"""
+    valid = vals > -1
+    cnt = valid.sum(axis=axes)
+    tot = np.where(valid, vals, 0.0).sum(axis=axes)
+    return np.where(cnt > 0, tot / np.maximum(cnt, 1), -1.0)
+
+
+def _bootstrap_stats(p, mode, ap, ar):
+    """ap, ar (n, T, K, A, M) -> (n, 13): the slots of summarize() per replicate.  `one()` averages a slot's (T', R, K) block of
+    `precision` over the entries > -1, and for fixed (k, a) all (t, r) hold a value or none does: the mean over the valid (t, k) of the
+    R-means is the same number."""
+    out = np.full((ap.shape[0], 13), -1.0)
+    for i, (is_ap, iouThr, areaRng, maxDets) in enumerate(_stat_slots(p, mode)):
+        tind, aind, mind = _slot_indices(p, mode, is_ap, iouThr, areaRng, maxDets)
+        s = ap if is_ap == 1 else ar
+        if tind is not None:
+            s = s[:, tind]
+        if len(aind) and len(mind) and s.shape[1]:
+            out[:, i] = _masked_mean(s[:, :, :, aind[0], mind[0]], (1, 2))
+    return out
+
+
+def _bootstrap_result(p, mode, W, ap, ar, confidence):
+    """the dict of `Omni3Deval.bootstrap` from the tables of [the all-ones replicate] + W"""
+    stats = _bootstrap_stats(p, mode, ap, ar)
+    mean, se, ci, n_valid = _replicate_summary(stats[1:], confidence)
+    aall = p.areaRngLbl.index("all") if "all" in p.areaRngLbl else 0
+    cat = _masked_mean(ap[:, :, :, aall, -1], (1,))                                   # (n + 1, K)
+    cmean, cse, cci, cn = _replicate_summary(cat[1:], confidence)
+    return {"weights": W, "ap": ap[1:], "ar": ar[1:], "stats": stats[1:], "point": stats[0], "mean": mean, "se": se, "ci": ci,
+            "n_valid": n_valid, "confidence": confidence,
+            "per_category": {"point": cat[0], "values": cat[1:], "mean": cmean, "se": cse, "ci": cci, "n_valid": cn}}
+
+
+def bootstrap_compare(ev_a, ev_b, n=1000, seed=0, confidence=0.95, weights=None, strata=None, chunk=None):
+    """Paired bootstrap of two prediction sets on the same images: both `Omni3Deval` must have been evaluated with equal imgIds, catIds,
+    areaRng, maxDets, iouThrs and recThrs (ValueError otherwise).  ONE weight table (given, or drawn as in `Omni3Deval.bootstrap`) is
+    used for both, so every replicate compares the two on the same resampled test set.
+    -> dict: `a`, `b` the two `bootstrap` dicts; `delta` (n, 13) = a - b per stats slot, NaN where either side has no value;
+    `delta_point` (13,); `delta_ci` (13, 2) the percentile interval and `p_le0` (13,) the share of the replicates with delta <= 0,
+    both over the replicates valid on both sides (NaN without any); `n_valid` (13,); `per_category`: the same (`delta` (n, K),
+    `delta_point`, `delta_ci`, `p_le0`, `n_valid`) for the per-category AP."""
+    for ev in (ev_a, ev_b):
+        if ev._dev is None:
+            raise Exception("Please run evaluate() first")
+    pa, pb = ev_a._paramsEval, ev_b._paramsEval
+    same = list(pa.imgIds) == list(pb.imgIds) and list(pa.catIds) == list(pb.catIds) and list(pa.maxDets) == list(pb.maxDets) \
+        and np.array_equal(np.asarray(pa.areaRng, dtype=np.float64), np.asarray(pb.areaRng, dtype=np.float64)) \
+        and np.array_equal(np.asarray(ev_a.params.iouThrs), np.asarray(ev_b.params.iouThrs)) \
+        and np.array_equal(np.asarray(ev_a.params.recThrs), np.asarray(ev_b.params.recThrs))
+    if not same:
+        raise ValueError("the two evaluations differ in imgIds, catIds, areaRng, maxDets, iouThrs or recThrs")
+    confidence = _check_confidence(confidence)
+    W = bootstrap_weights(pa.imgIds, n, seed, weights, strata)
+    a = ev_a.bootstrap(confidence=confidence, weights=W, chunk=chunk)
+    b = ev_b.bootstrap(confidence=confidence, weights=W, chunk=chunk)
+
+    def paired(va, vb, pa_, pb_):
+        both = (va > -1) & (vb > -1)
+        delta = np.where(both, va - vb, np.nan)
+        S = va.shape[1]
+        dci, ple0, nv = np.full((S, 2), np.nan), np.full(S, np.nan), both.sum(axis=0)
+        for j in range(S):
+            v = delta[both[:, j], j]
+            if v.size:
+                dci[j] = np.quantile(v, [(1.0 - confidence) / 2.0, (1.0 + confidence) / 2.0])
+                ple0[j] = float((v <= 0).mean())
+        return {"delta": delta, "delta_point": np.where((pa_ > -1) & (pb_ > -1), pa_ - pb_, np.nan), "delta_ci": dci, "p_le0": ple0,
+                "n_valid": nv}
+
+    out = {"a": a, "b": b, "weights": W, "confidence": confidence}
+    out.update(paired(a["stats"], b["stats"], a["point"], b["point"]))
+    out["per_category"] = paired(a["per_category"]["values"], b["per_category"]["values"], a["per_category"]["point"], b["per_category"]["point"])
     return out
 
 
@@ -479,17 +648,10 @@ class Omni3Deval:
             self._evalImgs = out
         return self._evalImgs
 
-    # ---- accumulate (:1172-1313) --------------------------------------------------------------------------------------
-    def accumulate(self, p=None):
-        assert self._dev is not None, "Please run evaluate() first"
-        if p is None:
-            p = self.params
-        pe, d = self._paramsEval, self._dev
-        if list(p.catIds) != list(pe.catIds) or list(map(tuple, p.areaRng)) != list(map(tuple, pe.areaRng)) or list(p.maxDets) != list(pe.maxDets) \
-                or list(p.imgIds) != list(pe.imgIds):
-            raise NotImplementedError("accumulate() with parameters other than evaluate()'s is not built on the device path")
-        T, R, K, A, M = len(p.iouThrs), len(p.recThrs), len(p.catIds), len(p.areaRng), len(p.maxDets)
-        dev = d["device"]
+    def _merge_tables(self, K, A):
+        """the host tables accumulate() and bootstrap() hand to the device: the merge order, the rank of a detection in its image's
+        list, the ground-truth counts; per (image, category) group its category, image index and non-ignored ground truths per range"""
+        d = self._dev
         groups, dt_sizes, gt_sizes = d["groups"], d["dt_sizes"], d["gt_sizes"]
         sumD = int(dt_sizes.sum())
         cat_of_group = np.array([g[0] for g in groups], dtype=np.int64)
@@ -504,6 +666,24 @@ class Omni3Deval:
         for a in range(A):
             npig[:, a] = np.bincount(gcat[gt_ig[a] == 0], minlength=K)
         has_e = np.bincount(cat_of_group, minlength=K).astype(np.int32).clip(max=1)
+        return {"cat_of_group": cat_of_group, "det_rank": det_rank, "order": order, "cat_off": cat_off, "gt_ig": gt_ig, "npig": npig,
+                "has_e": has_e}
+
+    # ---- accumulate (:1172-1313) --------------------------------------------------------------------------------------
+    def accumulate(self, p=None):
+        assert self._dev is not None, "Please run evaluate() first"
+        if p is None:
+            p = self.params
+        pe, d = self._paramsEval, self._dev
+        if list(p.catIds) != list(pe.catIds) or list(map(tuple, p.areaRng)) != list(map(tuple, pe.areaRng)) or list(p.maxDets) != list(pe.maxDets) \
+                or list(p.imgIds) != list(pe.imgIds):
+            raise NotImplementedError("accumulate() with parameters other than evaluate()'s is not built on the device path")
+        T, R, K, A, M = len(p.iouThrs), len(p.recThrs), len(p.catIds), len(p.areaRng), len(p.maxDets)
+        dev = d["device"]
+        dt_sizes, gt_sizes = d["dt_sizes"], d["gt_sizes"]
+        sumD = int(dt_sizes.sum())
+        tb = self._merge_tables(K, A)
+        det_rank, order, cat_off, npig, has_e = tb["det_rank"], tb["order"], tb["cat_off"], tb["npig"], tb["has_e"]
         tod = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)               # noqa: E731
         prec = torch.full((T, R, K, A, M), -1.0, dtype=torch.float64, device=dev)
         rec = torch.full((T, K, A, M), -1.0, dtype=torch.float64, device=dev)
@@ -545,35 +725,21 @@ class Omni3Deval:
                    else " {:<18} {} @[ IoU={:<9} | depth={:>6s} | maxDets={:>3d} ] = {:0.3f}")
             shown = p.distThrs if mode == "DIST" else p.iouThrs            # DIST: thresholds are named, and looked up, in metres
             iouStr = "{:0.2f}:{:0.2f}".format(shown[0], shown[-1]) if iouThr is None else "{:0.2f}".format(iouThr)
-            aind = [i for i, a in enumerate(p.areaRngLbl) if a == areaRng]
-            mind = [i for i, m in enumerate(p.maxDets) if m == maxDets]
-            if ap == 1:
-                s = ev[table]
-                if iouThr is not None:
-                    s = s[np.where(np.isclose(iouThr, np.asarray(shown).astype(float)))[0]]
-                s = s[:, :, :, aind, mind]
-            else:
-                s = ev["recall"]
-                if iouThr is not None:
-                    s = s[np.where(iouThr == np.asarray(shown))[0]]
-                s = s[:, :, aind, mind]
+            tind, aind, mind = _slot_indices(p, mode, ap, iouThr, areaRng, maxDets)
+            s = ev[table] if ap == 1 else ev["recall"]
+            if tind is not None:
+                s = s[tind]
+            s = s[:, :, :, aind, mind] if ap == 1 else s[:, :, aind, mind]
             mean_s = -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
             name, short = ("Average Recall", "(AR)") if ap != 1 else ("Average Precision", "(AP)") if table == "precision" else ("Longitudinal Prec.", "(APL)")
             lines.append("mode={} ".format(mode) + fmt.format(name, short, iouStr, areaRng, maxDets, mean_s))
             return mean_s
 
-        thres = [0.5, 0.75, 0.95] if mode == "2D" else [0.5, 1.0, 2.0] if mode == "DIST" else [0.15, 0.25, 0.50]
+        thres = _stat_thresholds(mode)
         L, md = p.areaRngLbl, p.maxDets
         stats = np.zeros((13,))
-        stats[0] = one(1)
-        for i in range(3):
-            stats[1 + i] = one(1, iouThr=thres[i], maxDets=md[2])
-        for i in range(3):
-            stats[4 + i] = one(1, areaRng=L[1 + i], maxDets=md[2])
-        for i in range(3):
-            stats[7 + i] = one(0, maxDets=md[i])
-        for i in range(3):
-            stats[10 + i] = one(0, areaRng=L[1 + i], maxDets=md[2])
+        for i, (ap, iouThr, areaRng, maxDets) in enumerate(_stat_slots(p, mode)):
+            stats[i] = one(ap, iouThr=iouThr, areaRng=areaRng, maxDets=maxDets)
         self.stats = stats
         if mode == "DIST":
             aall = p.areaRngLbl.index("all")
@@ -604,6 +770,79 @@ class Omni3Deval:
 
     def __str__(self):
         self.summarize()
+
+    # ---- bootstrap (extension) ----------------------------------------------------------------------------------------
+    def _bootstrap_tables(self, weights, chunk=None):
+        """weights (n, I) int32 -> (ap, ar) (n, T, K, A, M) float64 on the host: `kernels.bootstrap` on the tables of evaluate(),
+        `chunk` rows of `weights` at a time"""
+        from ...kernels import bootstrap as kb
+        p, pe, d = self.params, self._paramsEval, self._dev
+        if list(p.catIds) != list(pe.catIds) or list(map(tuple, p.areaRng)) != list(map(tuple, pe.areaRng)) or list(p.maxDets) != list(pe.maxDets) \
+                or list(p.imgIds) != list(pe.imgIds):
+            raise NotImplementedError("bootstrap() with parameters other than evaluate()'s is not built on the device path")
+        chunk = BOOTSTRAP_CHUNK if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        T, K, A, M = len(p.iouThrs), len(p.catIds), len(p.areaRng), len(p.maxDets)
+        dev, groups, dt_sizes, gt_sizes = d["device"], d["groups"], d["dt_sizes"], d["gt_sizes"]
+        tb = self._merge_tables(K, A)
+        G = len(groups)
+        grp_img = np.array([g[1] for g in groups], dtype=np.int32)
+        grp_off = np.concatenate([[0], np.cumsum(np.bincount(tb["cat_of_group"], minlength=K))]).astype(np.int32)
+        gid = np.repeat(np.arange(G), gt_sizes)
+        grp_npig = np.zeros((G, A), np.int32)
+        for a in range(A):
+            grp_npig[:, a] = np.bincount(gid[tb["gt_ig"][a] == 0], minlength=G)
+        tod = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)               # noqa: E731
+        t_order, t_off, t_rank, t_img = tod(tb["order"]), tod(tb["cat_off"]), tod(tb["det_rank"]), tod(np.repeat(grp_img, dt_sizes).astype(np.int32))
+        t_goff, t_gimg, t_gnpig = tod(grp_off), tod(grp_img), tod(grp_npig)
+        t_thr, t_md = tod(np.asarray(p.recThrs, dtype=np.float64)), tod(np.asarray(p.maxDets, dtype=np.int32))
+        dm, dg = d["match"]["dt_match"].contiguous(), d["match"]["dt_ignore"].contiguous()
+        n = weights.shape[0]
+        ap, ar = np.empty((n, T, K, A, M), np.float64), np.empty((n, T, K, A, M), np.float64)
+        for c0 in range(0, n, chunk):
+            w = tod(weights[c0:c0 + chunk])
+            npig_b, has_e_b = kb.bootstrap_counts(t_goff, t_gimg, t_gnpig, w, sum_gt=int(gt_sizes.sum()))
+            a1, a2 = kb.bootstrap_accumulate(t_order, t_off, t_rank, dm, dg, t_img, w, npig_b, has_e_b, t_thr, t_md)
+            ap[c0:c0 + chunk], ar[c0:c0 + chunk] = a1.cpu().numpy(), a2.cpu().numpy()
+        return ap, ar
+
+    def bootstrap(self, n=1000, seed=0, confidence=0.95, weights=None, strata=None, chunk=None):
+        """Image-level bootstrap of the AP / AR this evaluator reports (extension; call after evaluate()): is a difference in AP more
+        than the luck of the test set?
+
+        Definition.  A replicate is a vector w of len(params.imgIds) non-negative integers; its result is BY DEFINITION what this
+        evaluator returns on the data set in which image i is present w[i] times, each copy with copies of its ground truths and
+        detections (w[i] = 0: absent), the copies adjacent in the image order.  evaluate() matches per (image, category), so the match
+        tables stay; only accumulate() is redone, for all replicates in one launch (`omni_eval_bootstrap`, csrc/eval_bootstrap.hip): in
+        the merge order of accumulate() a detection counts as w consecutive identical entries; npig and "has an evaluated image" are the
+        weighted sums over the (image, category) groups; precision at the last copy of a true positive is TP / (FP + TP + eps) on the
+        weighted inclusive sums, and it serves the recall thresholds in ((TP - w) / npig, TP / npig].  When several detections of a
+        category tie in score this weighted order is the definition (a physically duplicated data set would interleave them).
+        Scope: `precision` (as its mean over the recall thresholds) and `recall` of all five modes, which share the match tables.  Out
+        of scope: the true-positive errors of mode "DIST" and `precision_l` / the affinity tables of mode "LET".
+
+        weights: explicit replicates, (n, I) integers >= 0, columns in the order of params.imgIds (ValueError otherwise).  Without
+        them n rows are drawn: g = np.random.default_rng(seed); the strata in sorted label order; a stratum of n_s images fills its
+        columns with g.multinomial(n_s, np.full(n_s, 1 / n_s), size=n), so every row sums to I.  strata: None = one stratum, or a
+        mapping image id -> label: images are resampled within their label.  chunk: the replicates go to the device `chunk` rows at a
+        time (default BOOTSTRAP_CHUNK = 256: the weight table and the two result tables of a chunk take 256 x (4 I + 16 T K A M)
+        bytes there); the result does not depend on it, bit for bit.  ValueError when (number of detections or of ground truths) x
+        (largest weight) >= 2^31: the weighted counts are 32-bit.
+
+        -> dict: `weights` (n, I) int32; `ap`, `ar` (n, T, K, A, M) float64, -1 where accumulate() leaves -1; `stats` (n, 13) the
+        slots of summarize() per replicate (each the mean over the thresholds and categories with a value of `ap` or `ar`); `point`
+        (13,) the same from the all-ones replicate = the data set itself; `mean`, `se` (std, ddof=1) and `n_valid` (13,) over the
+        replicates whose slot is > -1, `ci` (13, 2) = np.quantile of those at (1 - confidence) / 2 and (1 + confidence) / 2 (NaN
+        without a valid replicate, `se` NaN with fewer than two); `per_category`: a dict of the same (`point`, `values` (n, K),
+        `mean`, `se`, `n_valid` (K,), `ci` (K, 2)) for the per-category AP at range "all" and the largest maxDets, averaged over the
+        thresholds."""
+        if self._dev is None:
+            raise Exception("Please run evaluate() first")
+        confidence = _check_confidence(confidence)
+        W = bootstrap_weights(self._paramsEval.imgIds, n, seed, weights, strata)
+        ap, ar = self._bootstrap_tables(np.concatenate([np.ones((1, W.shape[1]), np.int32), W]), chunk)      # row 0: the point estimate
+        return _bootstrap_result(self.params, self.mode, W, ap, ar, confidence)
 
 
 # =====================================================================================================================
@@ -719,6 +958,35 @@ def _let_params(params):
     return {k: v for k, v in (("lonTolFrac", frac), ("lonTolMin", tmin)) if k in params}
 
 
+_BOOTSTRAP_KEYS = ("n", "seed", "confidence")
+
+
+def _bootstrap_params(params):
+    """None (off) or a dict with some of n / seed / confidence -> None or the checked, completed dict"""
+    if params is None:
+        return None
+    if not isinstance(params, dict) or set(params) - set(_BOOTSTRAP_KEYS):
+        raise ValueError("bootstrap must be None or a dict with keys out of %r" % (_BOOTSTRAP_KEYS,))
+    n, seed = params.get("n", 1000), params.get("seed", 0)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError("bootstrap n must be a positive integer")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+        raise ValueError("bootstrap seed must be a non-negative integer")
+    return {"n": int(n), "seed": int(seed), "confidence": _check_confidence(params.get("confidence", 0.95))}
+
+
+def _bootstrap_ci(ev, mode, class_names, params, strata=None):
+    """the percentile intervals of `ev.bootstrap(**params, strata=strata)` in the layout of `_derive_results`: the seven headline
+    numbers and 'AP-<name>' per category, each (lo, hi) x 100 (NaN, NaN without a valid replicate)"""
+    bs = ev.bootstrap(strata=strata, **params)
+    pair = lambda row: (float(row[0] * 100), float(row[1] * 100))                      # noqa: E731
+    res = {name: pair(bs["ci"][i]) for i, name in enumerate(_METRICS[mode])}
+    if class_names is not None and len(class_names) > 1:
+        assert len(class_names) == bs["per_category"]["ci"].shape[0], (len(class_names), bs["per_category"]["ci"].shape)
+        res.update({"AP-" + name: pair(bs["per_category"]["ci"][k]) for k, name in enumerate(class_names)})
+    return res
+
+
 def _make_eval(gt, dt, mode, eval_prox, bev_up, dist_up, dist_params, let_params=None):
     """the Omni3Deval of one pass of the drivers: `up` is the BEV ground plane, except in mode DIST, which has its own"""
     ev = Omni3Deval(gt, dt, mode=mode, eval_prox=eval_prox, up=dist_up if mode == "DIST" else bev_up)
@@ -756,12 +1024,17 @@ class Omni3DEvaluator:
     eval_let (extension, off by default; `let_params` = optional dict of `lonTolFrac` / `lonTolMin` set on the pass's params): unless
     only_2d, one more pass in mode 'LET' after 3D, BEV and DIST adds 'bbox_LET' (LET-AP in the headline slots of the 3D protocol,
     LET-APL as 'APL', 'APL15', ..., 'AP-<name>', 'APL-<name>', 'mAFF', 'mLON'), 'log_str_LET', 'bbox_LET_merge' (short form: 'APLET',
-    'omni_eval_LET'); nothing else changes."""
+    'omni_eval_LET'); nothing else changes.
+
+    bootstrap (extension, off by default; None or a dict with some of `n` (1000), `seed` (0), `confidence` (0.95)): every evaluated
+    mode also gets 'bbox_<mode>_ci': the image-level bootstrap percentile intervals (`Omni3Deval.bootstrap`) of the seven headline
+    numbers of 'bbox_<mode>' and of 'AP-<name>' per category, each (lo, hi) x 100 (short form: 'AP<mode>_ci'); nothing else changes."""
 
     def __init__(self, dataset_name, tasks=None, distributed=True, output_dir=None, *, max_dets_per_image=None, use_fast_impl=False,
                  eval_prox=False, only_2d=False, filter_settings=None, img_ids=None, cat_ids=None, eval_bev=False, bev_up=BEV_UP,
-                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None):
+                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None):
         self._only_2d, self._eval_prox, self._output_dir, self._distributed = only_2d, eval_prox, output_dir, distributed
+        self._bootstrap = _bootstrap_params(bootstrap)
         self._eval_let, self._let_params = bool(eval_let), _let_params(let_params)
         self._eval_bev, self._bev_up = bool(eval_bev), tuple(float(v) for v in bev_up)
         self._eval_dist, self._dist_up, self._dist_params = bool(eval_dist), _dist_up(dist_up), _dist_params(dist_params)
@@ -814,6 +1087,8 @@ class Omni3DEvaluator:
             ev.summarize()
             res["AP" + mode] = float(ev.stats[0] * 100)
             res["omni_eval_" + mode] = ev
+            if self._bootstrap is not None:
+                res["AP" + mode + "_ci"] = _bootstrap_ci(ev, mode, None, self._bootstrap)["AP"]
         return {"bbox": res}
 
     def evaluate(self, img_ids=None):
@@ -865,6 +1140,8 @@ class Omni3DEvaluator:
             ev.accumulate()
             self._results["log_str_" + mode] = ev.summarize()
             self._results["bbox_" + mode] = _derive_results(ev, mode, split_classes)
+            if self._bootstrap is not None:
+                self._results["bbox_" + mode + "_ci"] = _bootstrap_ci(ev, mode, split_classes, self._bootstrap)
             self._results["bbox_" + mode + "_merge"] = {"gt": self._omni_api, "dt": kept, "eval_prox": self._eval_prox,
                                                         "img_ids": list(ev.params.imgIds), "cat_ids": list(ev.params.catIds)}
         return copy.deepcopy({k: v for k, v in self._results.items() if not k.endswith("_merge")}) | \
@@ -877,10 +1154,15 @@ class Omni3DEvaluationHelper:
     `MetadataCatalog.get('omni3d_model').{thing_classes, thing_dataset_id_to_contiguous_id}`.  The union is scored by one
     evaluation over the concatenated ground truth and detections (images of different splits are disjoint, so this equals the
     reference's concatenation of cached per-image match tables), with proximity evaluation applied to the images of the splits
-    that use it."""
+    that use it.
+
+    bootstrap (extension, off by default; None or the dict `Omni3DEvaluator` takes): every split's result gets 'bbox_<mode>_ci', and
+    `results_ci[name]` = {'iters', 'AP2D': (lo, hi), 'AP3D': (lo, hi)}: the bootstrap intervals (x 100) of the evaluator's AP in modes
+    2D and 3D, i.e. of the mean of the per-category APs the AP2D / AP3D columns show.  For <Concat> the images are resampled within
+    the split they come from (strata), so every replicate keeps the splits' sizes.  The printed tables do not change."""
 
     def __init__(self, dataset_names, filter_settings, output_folder, iter_label="-", only_2d=False, eval_bev=False, bev_up=BEV_UP,
-                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None):
+                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None):
         from collections import OrderedDict
         from ...d2.data import MetadataCatalog
         from ..data.datasets import simple_register
@@ -895,6 +1177,8 @@ class Omni3DEvaluationHelper:
         self.results_dist = OrderedDict()
         # extension (off by default): LET-AP / LET-APL and the longitudinal diagnostics per split and for <Concat>, in `results_let`
         self.eval_let, self.let_params, self.results_let = bool(eval_let) and not only_2d, _let_params(let_params), OrderedDict()
+        # extension (off by default): bootstrap intervals of AP2D / AP3D per split and for <Concat>, in `results_ci`
+        self.bootstrap, self.results_ci = _bootstrap_params(bootstrap), OrderedDict()
         self.overall_imgIds, self.overall_catIds = set(), set()
         self.output_folders = {n: os.path.join(output_folder, n) for n in self.dataset_names}
         for name in self.dataset_names:
@@ -903,7 +1187,7 @@ class Omni3DEvaluationHelper:
             ev = Omni3DEvaluator(name, output_dir=self.output_folders[name], filter_settings=filter_settings, only_2d=only_2d,
                                  eval_prox=("Objectron" in name or "SUNRGBD" in name), distributed=False, eval_bev=self.eval_bev,
                                  bev_up=self.bev_up, eval_dist=self.eval_dist, dist_up=self.dist_up, dist_params=self.dist_params,
-                                 eval_let=self.eval_let, let_params=self.let_params)
+                                 eval_let=self.eval_let, let_params=self.let_params, bootstrap=self.bootstrap)
             ev.reset()
             self.evaluators[name] = ev
             self.overall_imgIds.update(ev._omni_api.getImgIds())
@@ -941,6 +1225,11 @@ class Omni3DEvaluationHelper:
                 "APLET-F": rl["APf"], "APLLET": self._mean(rl["APL-" + c] for c in categories if "APL-" + c in rl),
                 "APLLET@15": rl["APL15"], "APLLET@25": rl["APL25"], "APLLET@50": rl["APL50"], "APLLET-N": rl["APLn"],
                 "APLLET-M": rl["APLm"], "APLLET-F": rl["APLf"], "mAFF": rl["mAFF"], "mLON": rl["mLON"]}
+
+    def _ci_row(self, c2, c3):
+        """the row of `results_ci`: the intervals of the evaluator's AP in modes 2D and 3D"""
+        nan2 = (float("nan"), float("nan"))
+        return {"iters": self.iter_label, "AP2D": c2["AP"] if c2 else nan2, "AP3D": c3["AP"] if c3 and not self.only_2d else nan2}
 
     def _aggregates(self, res2d, res3d, categories):
         nan = float("nan")
@@ -985,6 +1274,10 @@ class Omni3DEvaluationHelper:
             self.results_dist[dataset_name] = self._dist_row(res["bbox_DIST"], present)
         if self.eval_let and "bbox_LET" in res:
             self.results_let[dataset_name] = self._let_row(res["bbox_LET"], present)
+        if self.bootstrap is not None and "bbox_2D_ci" in res:
+            self.results_ci[dataset_name] = self._ci_row(res["bbox_2D_ci"], res.get("bbox_3D_ci"))
+            log.info("{} iter={} bootstrap {:g} % intervals (n={}): {}".format(dataset_name, self.iter_label, 100 * self.bootstrap["confidence"],
+                                                                            self.bootstrap["n"], self.results_ci[dataset_name]))
         logperf.print_ap_category_histogram(dataset_name, self._per_category(r2, r3))
 
     def _per_category(self, r2, r3):
@@ -1008,10 +1301,10 @@ class Omni3DEvaluationHelper:
         cat_ids = sorted(self.overall_catIds)
         ordered = [meta.thing_classes[meta.thing_dataset_id_to_contiguous_id[c]] for c in cat_ids]
         categories = set(ordered)
-        merged = {}
+        merged, merged_ci = {}, {}
         for mode in (["2D"] if self.only_2d else ["2D", "3D"] + (["BEV"] if self.eval_bev else []) + (["DIST"] if self.eval_dist else [])
                      + (["LET"] if self.eval_let else [])):
-            gts, dts, prox_imgs = [], [], set()
+            gts, dts, prox_imgs, strata = [], [], set(), {}
             for name in self.dataset_names:
                 rec = self.results[name].get("bbox_" + mode + "_merge")
                 if rec is None:
@@ -1020,6 +1313,7 @@ class Omni3DEvaluationHelper:
                 dts += rec["dt"]
                 if rec["eval_prox"]:
                     prox_imgs.update(rec["img_ids"])
+                strata.update({i: name for i in rec["img_ids"]})
             ev = _make_eval(AnnotationIndex(copy.deepcopy(gts), self.overall_imgIds, cat_ids),
                             AnnotationIndex(copy.deepcopy(dts), self.overall_imgIds, cat_ids), mode,
                             (prox_imgs if prox_imgs else False), self.bev_up, self.dist_up, self.dist_params, self.let_params)
@@ -1027,6 +1321,9 @@ class Omni3DEvaluationHelper:
             ev.accumulate()
             ev.summarize()
             merged[mode] = _derive_results(ev, mode, ordered if len(ordered) > 1 else None)
+            if self.bootstrap is not None and mode in ("2D", "3D"):
+                # an image no split lists (it has no prediction record) is a stratum of its own kind
+                merged_ci[mode] = _bootstrap_ci(ev, mode, None, self.bootstrap, strata={i: strata.get(i, "") for i in ev.params.imgIds})
             if len(ordered) == 1:       # _derive_results skips the per-category part for a single class
                 merged[mode]["AP-" + ordered[0]] = merged[mode]["AP"]
                 if mode == "DIST":
@@ -1040,6 +1337,8 @@ class Omni3DEvaluationHelper:
             self.results_dist["<Concat>"] = self._dist_row(merged["DIST"], categories)
         if "LET" in merged:
             self.results_let["<Concat>"] = self._let_row(merged["LET"], categories)
+        if "2D" in merged_ci:
+            self.results_ci["<Concat>"] = self._ci_row(merged_ci["2D"], merged_ci.get("3D"))
         general = self._aggregates(r2, r3, categories)
         extras = {k: (r3[k] if not self.only_2d else float("nan")) for k in ("AP15", "AP25", "AP50", "APn", "APm", "APf")}
         self.results_analysis["<Concat>"] = {"iters": self.iter_label, "AP2D": general["AP2D"], "AP3D": general["AP3D"],
