@@ -925,6 +925,29 @@ int omni_eval_bootstrap(const int* order, const int* cat_off, const int* rank, c
                         const double* rec_thrs, const int* max_dets, int K, int A, int M, int T, int R, int sumD, int B, int I,
                         double* ap, double* ar, void* stream);
 
+/* The error decomposition of `Omni3Deval.errors` (csrc/eval_errors.hip): which mistake every false positive and every unfound ground
+ * truth is, after TIDE (Bolya et al., ECCV 2020).  The reference has no counterpart and no call site.  Rows are ragged by IMAGE:
+ * detections of image i are rows dt_off[i] .. dt_off[i + 1] - 1, ground truths gt_off[i] .. gt_off[i + 1] - 1 (both (I + 1) int32,
+ * starting at 0, non-decreasing, ending at sumD / sumG; not checked here), over all categories; sim holds image i's (D_i, G_i) row-major
+ * similarity matrix at sim_off[i] ((I + 1) int64).  Per detection: dt_cat, dt_matched (dt_match >= 0), dt_ignore, dt_score; per ground
+ * truth: gt_cat, gt_matched, gt_ignore (`_ignore` at the analysed range; such a row is no candidate): the tables of omni_eval_match at
+ * one (range, threshold).  0 < t_bg < t_fg.  Out, per detection: type (sumD) int8 = 0 true positive (matched, not ignored), 1 ignored,
+ * and for every other one, with s_free / s_used / s_other = its largest similarity to an unmatched / a matched candidate of its own
+ * category / a candidate of another category (-inf for an empty set, the later row among equal values), in this order: 3 Loc (s_free
+ * >= t_bg), 2 Cls (s_other >= t_fg), 5 Dupe (s_used >= t_fg), 6 Bkg (all three < t_bg), 4 Both (the rest); similarities are compared
+ * with the thresholds as doubles.  attr (sumD) = the global row of the arg-max of the deciding set for Loc / Cls / Dupe, -1 otherwise;
+ * smax (sumD,3) = (s_free, s_used, s_other); win_loc (sumD) = 1 for the Loc detection with the highest score among those attributed to
+ * the same ground truth (the lower row among equal scores); win_cls (sumD) = the same among the Cls detections, and only when that
+ * ground truth is unmatched.  Per ground truth: gt_missed (sumG) = 1 for an unmatched candidate that is the attributed ground truth of
+ * no Loc or Cls detection.  One 256-thread workgroup per image, one detection per thread; integer LDS atomics only: two runs give the
+ * same bits.  max_gt = the largest G_i: above 1024 (the LDS capacity), as on negative sizes, thresholds out of order or a missing array,
+ * OMNI_ERR_ARG before any launch; nothing is truncated.  I == 0 launches nothing; images without detections or ground truths are valid. */
+int omni_eval_error_types(const float* sim, const long long* sim_off, const int* dt_off, const int* gt_off, const int* dt_cat,
+                          const unsigned char* dt_matched, const unsigned char* dt_ignore, const double* dt_score, const int* gt_cat,
+                          const unsigned char* gt_matched, const unsigned char* gt_ignore, double t_fg, double t_bg, int I, int sumD,
+                          int sumG, int max_gt, signed char* type, int* attr, float* smax, unsigned char* win_loc,
+                          unsigned char* win_cls, unsigned char* gt_missed, void* stream);
+
 /* Drawing predicted cuboids (csrc/render.hip).  The reference renders them with pytorch3d's mesh rasteriser and paints the edges
  * with OpenCV; here every pixel casts its ray (through the pixel centre (x + 0.5, y + 0.5)) against the boxes themselves.
  *

@@ -210,6 +210,48 @@ def bootstrap_eval_args(cfg):
     return {"bootstrap": {"n": n, "seed": seed, "confidence": float(conf)}}
 
 
+_ERRORS = {"ENABLED": False, "T_FG": [], "T_BG": []}
+
+
+def add_error_analysis_config(cfg):
+    """TEST.ERRORS.*: the error decomposition next to every AP the evaluation reports (`Omni3Deval.errors`, csrc/eval_errors.hip; after
+    TIDE, Bolya et al., ECCV 2020): every false positive is typed as wrong class, poor box, both, duplicate or background, every unfound
+    ground truth is a miss, and each type is priced by the AP an oracle repairing it alone would gain.  The reference has no such option
+    and `get_cfg_defaults` stays key for key what the reference defines, so, as with `add_bootstrap_config`, the node is absent until
+    this call; without it nothing is analysed.  Idempotent: values already set are kept.
+    T_FG / T_BG: empty = the defaults of each mode (0.5 / 0.1 in 2D, 0.25 / 0.05 in the modes of the 3D protocol: conventions, not
+    tuned values); otherwise one number each, applied to every mode of the 3D protocol -- mode 2D keeps its own."""
+    if "ERRORS" not in cfg.TEST:
+        cfg.TEST.ERRORS = CN()
+    for key, value in _ERRORS.items():
+        cfg.TEST.ERRORS.setdefault(key, list(value) if isinstance(value, list) else value)
+    return cfg
+
+
+def error_eval_args(cfg):
+    """TEST.ERRORS -> the keyword argument of `Omni3DEvaluationHelper` / `Omni3DEvaluator`:
+    `Omni3DEvaluationHelper(names, filter_settings, folder, **error_eval_args(cfg))`.  A cfg without the node, or ENABLED False:
+    {"errors": None}, the feature off.  ValueError unless T_FG / T_BG are empty or hold one number in (0, 1) each, T_BG below T_FG."""
+    import math
+    node = cfg.TEST.get("ERRORS")
+    if node is None:
+        node = _ERRORS
+    get = (lambda k: node[k]) if isinstance(node, dict) else (lambda k: getattr(node, k))       # noqa: E731
+    out = {}
+    for key, name in (("T_FG", "t_fg"), ("T_BG", "t_bg")):
+        try:
+            values = [float(v) for v in get(key)]
+        except (TypeError, ValueError):
+            raise ValueError("TEST.ERRORS.%s must be empty or hold one number" % key) from None
+        if len(values) > 1 or any(not (math.isfinite(v) and 0.0 < v < 1.0) for v in values):
+            raise ValueError("TEST.ERRORS.%s must be empty or hold one number in (0, 1)" % key)
+        if values:
+            out[name] = values[0]
+    if "t_fg" in out and "t_bg" in out and not out["t_bg"] < out["t_fg"]:
+        raise ValueError("TEST.ERRORS.T_BG must be below T_FG")
+    return {"errors": out if bool(get("ENABLED")) else None}
+
+
 _TTA = {"MIN_SIZES": (), "MAX_SIZE": 4000, "FLIP": True, "FUSE_IOU_THRESH": 0.5, "CLASS_AGNOSTIC": False}
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from .bootstrap_stats import _bootstrap_ci, _bootstrap_params
+from .error_types import _error_params, error_summary
 from .modes import MODES, _mean, _percent, _table_ap, check_options, enabled_modes
 from .omni3d_evaluation import AnnotationIndex, Omni3Deval
 from .pairs import BEV_UP
@@ -105,13 +106,18 @@ class Omni3DEvaluator:
 
     bootstrap (extension, off by default; None or a dict with some of `n` (1000), `seed` (0), `confidence` (0.95)): every evaluated
     mode also gets 'bbox_<mode>_ci': the image-level bootstrap percentile intervals (`Omni3Deval.bootstrap`) of the seven headline
-    numbers of 'bbox_<mode>' and of 'AP-<name>' per category, each (lo, hi) x 100 (short form: 'AP<mode>_ci'); nothing else changes."""
+    numbers of 'bbox_<mode>' and of 'AP-<name>' per category, each (lo, hi) x 100 (short form: 'AP<mode>_ci'); nothing else changes.
+
+    errors (extension, off by default; None or a dict with some of `t_fg`, `t_bg`, applied to the modes of the 3D protocol -- mode 2D
+    keeps its own): every evaluated mode except DIST also gets 'bbox_<mode>_errors' = the error decomposition of
+    `Omni3Deval.errors`: {'t_fg', 't_bg', 'counts': {type: n}, 'dAP': {oracle: mean dAP x 100}, 'loc_errors': {'trans', 'scale',
+    'orient'} or None in 2D} (short form: 'errors_<mode>'); nothing else changes."""
 
     def __init__(self, dataset_name, tasks=None, distributed=True, output_dir=None, *, max_dets_per_image=None, use_fast_impl=False,
                  eval_prox=False, only_2d=False, filter_settings=None, img_ids=None, cat_ids=None, eval_bev=False, bev_up=BEV_UP,
-                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None):
+                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None, errors=None):
         self._only_2d, self._eval_prox, self._output_dir, self._distributed = only_2d, eval_prox, output_dir, distributed
-        self._bootstrap = _bootstrap_params(bootstrap)
+        self._bootstrap, self._errors = _bootstrap_params(bootstrap), _error_params(errors)
         self._opts = check_options(let_params=let_params, bev_up=bev_up, dist_up=dist_up, dist_params=dist_params)
         self._switches = {"eval_bev": bool(eval_bev), "eval_dist": bool(eval_dist), "eval_let": bool(eval_let)}
         if not isinstance(dataset_name, str):                   # short form: (gt_annotations, img_ids, cat_ids, only_2d)
@@ -163,6 +169,8 @@ class Omni3DEvaluator:
             res["omni_eval_" + mode] = ev
             if self._bootstrap is not None:
                 res["AP" + mode + "_ci"] = _bootstrap_ci(ev, mode, None, self._bootstrap)["AP"]
+            if self._errors is not None and MODES[mode].error_thrs is not None:
+                res["errors_" + mode] = error_summary(ev, self._errors)
         return {"bbox": res}
 
     def evaluate(self, img_ids=None):
@@ -216,6 +224,8 @@ class Omni3DEvaluator:
             self._results["bbox_" + mode] = _derive_results(ev, mode, split_classes)
             if self._bootstrap is not None:
                 self._results["bbox_" + mode + "_ci"] = _bootstrap_ci(ev, mode, split_classes, self._bootstrap)
+            if self._errors is not None and MODES[mode].error_thrs is not None:
+                self._results["bbox_" + mode + "_errors"] = error_summary(ev, self._errors)
             self._results["bbox_" + mode + "_merge"] = {"gt": self._omni_api, "dt": kept, "eval_prox": self._eval_prox,
                                                         "img_ids": list(ev.params.imgIds), "cat_ids": list(ev.params.catIds)}
         return copy.deepcopy({k: v for k, v in self._results.items() if not k.endswith("_merge")}) | \
@@ -233,10 +243,14 @@ class Omni3DEvaluationHelper:
     bootstrap (extension, off by default; None or the dict `Omni3DEvaluator` takes): every split's result gets 'bbox_<mode>_ci', and
     `results_ci[name]` = {'iters', 'AP2D': (lo, hi), 'AP3D': (lo, hi)}: the bootstrap intervals (x 100) of the evaluator's AP in modes
     2D and 3D, i.e. of the mean of the per-category APs the AP2D / AP3D columns show.  For <Concat> the images are resampled within
-    the split they come from (strata), so every replicate keeps the splits' sizes.  The printed tables do not change."""
+    the split they come from (strata), so every replicate keeps the splits' sizes.  The printed tables do not change.
+
+    errors (extension, off by default; None or the dict `Omni3DEvaluator` takes): every split's result gets 'bbox_<mode>_errors' for
+    every evaluated mode except DIST, `results_errors[name]` = {'iters', '<mode>': {oracle: mean dAP x 100}, ...}, and one log line
+    per split.  The printed tables do not change."""
 
     def __init__(self, dataset_names, filter_settings, output_folder, iter_label="-", only_2d=False, eval_bev=False, bev_up=BEV_UP,
-                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None):
+                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None, errors=None):
         from collections import OrderedDict
         from ...d2.data import MetadataCatalog
         from ..data.datasets import simple_register
@@ -254,6 +268,8 @@ class Omni3DEvaluationHelper:
         self.results_bev, self.results_dist, self.results_let = OrderedDict(), OrderedDict(), OrderedDict()
         # extension (off by default): bootstrap intervals of AP2D / AP3D per split and for <Concat>, in `results_ci`
         self.bootstrap, self.results_ci = _bootstrap_params(bootstrap), OrderedDict()
+        # extension (off by default): the error decomposition of every mode but DIST per split, in `results_errors`
+        self.errors, self.results_errors = _error_params(errors), OrderedDict()
         self.overall_imgIds, self.overall_catIds = set(), set()
         self.output_folders = {n: os.path.join(output_folder, n) for n in self.dataset_names}
         for name in self.dataset_names:
@@ -261,7 +277,7 @@ class Omni3DEvaluationHelper:
                 simple_register(name, filter_settings, filter_empty=False)
             ev = Omni3DEvaluator(name, output_dir=self.output_folders[name], filter_settings=filter_settings, only_2d=only_2d,
                                  eval_prox=("Objectron" in name or "SUNRGBD" in name), distributed=False, eval_bev=self.eval_bev,
-                                 eval_dist=self.eval_dist, eval_let=self.eval_let, bootstrap=self.bootstrap, **self._opts)
+                                 eval_dist=self.eval_dist, eval_let=self.eval_let, bootstrap=self.bootstrap, errors=self.errors, **self._opts)
             ev.reset()
             self.evaluators[name] = ev
             self.overall_imgIds.update(ev._omni_api.getImgIds())
@@ -323,6 +339,11 @@ class Omni3DEvaluationHelper:
             self.results_ci[dataset_name] = self._ci_row(res["bbox_2D_ci"], res.get("bbox_3D_ci"))
             log.info("{} iter={} bootstrap {:g} % intervals (n={}): {}".format(dataset_name, self.iter_label, 100 * self.bootstrap["confidence"],
                                                                             self.bootstrap["n"], self.results_ci[dataset_name]))
+        if self.errors is not None and "bbox_2D_errors" in res:
+            self.results_errors[dataset_name] = {"iters": self.iter_label, **{mode: res["bbox_" + mode + "_errors"]["dAP"] for mode in self.modes
+                                                                               if "bbox_" + mode + "_errors" in res}}
+            log.info("{} iter={} error decomposition, dAP per oracle: {}".format(dataset_name, self.iter_label, {
+                mode: {k: round(v, 2) for k, v in row.items()} for mode, row in self.results_errors[dataset_name].items() if mode != "iters"}))
         logperf.print_ap_category_histogram(dataset_name, self._per_category(r2, r3))
 
     def _per_category(self, r2, r3):

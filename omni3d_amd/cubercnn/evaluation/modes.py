@@ -49,6 +49,8 @@ class Mode2D:
     metrics = ["AP", "AP50", "AP75", "AP95", "APs", "APm", "APl"]
     switch, up_option, extension, results, concat_ci = None, "bev_up", False, None, True
     options = {"bev_up": lambda up: tuple(float(v) for v in up)}
+    # `Omni3Deval.errors`: the default (t_fg, t_bg) -- conventions, not tuned values: TIDE's -- and whether `loc_errors` applies
+    error_thrs, loc_errors = (0.5, 0.1), False
 
     def set_params(self, p):
         lo, hi = self.iou_range
@@ -85,6 +87,7 @@ class Mode3D(Mode2D):
     thresholds = [0.15, 0.25, 0.50]
     fmt = " {:<18} {} @[ IoU={:<9} | depth={:>6s} | maxDets={:>3d} ] = {:0.3f}"
     metrics = ["AP", "AP15", "AP25", "AP50", "APn", "APm", "APf"]
+    error_thrs, loc_errors = (0.25, 0.05), True           # the middle and the bottom of the AP3D threshold range
 
     def groups(self, E, ev, b_d, b_g, dt_sizes, gt_sizes, pairs):
         return E.box3d_overlap_groups(b_d, b_g, dt_sizes, gt_sizes, pairs=pairs)
@@ -139,6 +142,7 @@ class ModeDIST(Mode3D):
     metrics = ["AP", "AP@0.5m", "AP@1m", "AP@2m", "APn", "APm", "APf"]
     switch, up_option, extension, results, concat_ci = "eval_dist", "dist_up", True, "results_dist", False
     options = {"dist_up": _dist_up, "dist_params": _dist_params}
+    error_thrs, loc_errors = None, False                  # matched by distance: no background overlap, no error analysis
 
     def set_params(self, p):
         Mode3D.set_params(self, p)

@@ -20,7 +20,12 @@ exact IoU3D of the slid box decides the match (LET-AP), and a second table scale
 A fourth one, for every mode: `Omni3Deval.bootstrap` / `bootstrap_compare` = image-level bootstrap confidence intervals of AP / AR and
 the paired comparison of two prediction sets.  The match tables of evaluate() are kept and all replicates are accumulated in one launch
 from integer image multiplicities (`kernels.bootstrap`, csrc/eval_bootstrap.hip); `bootstrap` switches it on in the two drivers, off by
-default.  See `Omni3Deval.bootstrap`."""
+default.  See `Omni3Deval.bootstrap`.
+
+A fifth one, for every mode but DIST: `Omni3Deval.errors` / `summarize_errors` = the error decomposition after TIDE: every false positive
+is typed (wrong class, poor box, both, duplicate, background), every unfound ground truth is a miss, and each type is priced by the AP an
+oracle repairing it alone would gain (error_types.py, `kernels.errtypes`, csrc/eval_errors.hip); `errors` switches it on in the two
+drivers, off by default.  See `Omni3Deval.errors`."""
 import copy
 import datetime
 
@@ -29,6 +34,7 @@ import torch
 
 from ...kernels import iou3d
 from .bootstrap_stats import BOOTSTRAP_CHUNK, _bootstrap_result, _check_confidence, bootstrap_compare, bootstrap_weights  # noqa: F401
+from .error_types import ERROR_TYPES, ORACLES, error_analysis, error_lines  # noqa: F401
 from .modes import _METRICS, MODES, _slot_indices, _stat_slots  # noqa: F401
 from .pairs import (BEV_UP, _pair_index, _ragged_pairs, _xywh_iou, bev_overlap_groups, box3d_overlap, box3d_overlap_groups,  # noqa: F401
                     dist_errors_groups, evaluate_groups, let_overlap_groups)
@@ -403,6 +409,59 @@ class Omni3Deval:
         W = bootstrap_weights(self._paramsEval.imgIds, n, seed, weights, strata)
         ap, ar = self._bootstrap_tables(np.concatenate([np.ones((1, W.shape[1]), np.int32), W]), chunk)      # row 0: the point estimate
         return _bootstrap_result(self.params, self.mode, W, ap, ar, confidence)
+
+    # ---- error decomposition (extension) ------------------------------------------------------------------------------
+    def errors(self, t_fg=None, t_bg=None, area="all"):
+        """What is the AP lost to?  (Extension, after TIDE: Bolya et al., ECCV 2020; call after evaluate(); modes 2D, 3D, BEV, LET.)
+        Every false positive is wrong class, right object but poor box, duplicate or detection on nothing, every unfound ground truth is
+        a miss, and each type is priced by the AP gained if an oracle repaired it alone.  Mode DIST raises ValueError: it matches by
+        distance, a background overlap has no meaning there.
+
+        Thresholds.  t_fg must be one of params.iouThrs (np.isclose; ValueError otherwise): the analysis reuses the match tables of
+        evaluate() at (area, t_fg, the largest maxDets); 0 < t_bg < t_fg.  Defaults, conventions and not tuned values: 0.5 / 0.1 in 2D
+        (TIDE's), 0.25 / 0.05 in 3D / BEV / LET (the middle and the bottom of the AP3D threshold range).  area: one label of
+        params.areaRngLbl.
+        Image-level similarity.  Per image, rows = all detections that took part in evaluate() (every category's list cut to maxDets),
+        category-major in params.catIds order and by descending score inside a category, the order of the group table of evaluate();
+        columns = all ground truths of the image in the same category-major order.  One more pass of the mode's own similarity over these
+        image groups; the raw similarity also under eval_prox (a detection eval_prox made ignored stays ignored, the proximity mask is not
+        applied across categories).
+        Candidates: the ground truths that are not `_ignore` at the range.  Types (one code per detection, `kernels.errtypes`): TP =
+        matched and not ignored; IGN = ignored; every other detection is a false positive of its category c with s_free / s_used /
+        s_other = its largest similarity to an unmatched / a matched candidate of category c / a candidate of another category (-inf for
+        an empty set; the later row among equal values, eval_match's rule), and is, in TIDE's precedence, Loc if s_free >= t_bg, else Cls
+        if s_other >= t_fg, else Dupe if s_used >= t_fg, else Bkg if all three < t_bg (an image without candidates is all Bkg), else
+        Both.  The float32 similarities are compared with the thresholds as doubles.  Attributed ground truth: the arg-max of the
+        deciding set for Loc / Cls / Dupe, -1 otherwise.  Miss: an unmatched candidate no Loc or Cls detection is attributed to.
+        Departures from TIDE, whose precedence this is: a Loc points to an UNMATCHED candidate of the category only (so its oracle can
+        always make it a true positive); a ground truth is spared from Miss by a Loc / Cls attribution only; `>=` / `<` at the thresholds
+        are as written here; ignored detections and ground truths follow this evaluator's `_ignore` rules instead of COCO crowds; AP is
+        this evaluator's 101-point AP at one threshold and one range, not COCO's mean over thresholds.
+        Oracles, each alone on a copy of the tables and followed by an unchanged accumulation (T = A = M = 1): Loc: among the Loc
+        detections attributed to one ground truth the highest score wins (the lower row among equal scores) and becomes its true
+        positive, the others are removed (set ignored); Cls: the same contest; if the ground truth is matched already all are removed,
+        otherwise the winner becomes a true positive IN THE GROUND TRUTH'S CATEGORY (the merge order is rebuilt for it); Both, Dupe, Bkg:
+        removed; Miss: npig loses the missed ground truths; FP: every false positive removed; FN: npig = the matched candidates.
+
+        -> dict: `t_fg`, `t_bg`, `area`; `names` = the eight oracles (Cls, Loc, Both, Dupe, Bkg, Miss, FP, FN); in the detection order
+        of evaluate() (all detections of category 0 image by image, then category 1, ...): `dt_ids`, `type` (sumD,) int8, `attributed_gt`
+        (sumD,) annotation id or -1, `s_free` / `s_used` / `s_other` (sumD,) float32; `missed_gt_ids`; `counts` (K, 6) per category the
+        numbers of Cls, Loc, Both, Dupe, Bkg detections and missed ground truths, `counts_total` (6,); `ap` (K,) = the mean of
+        precision[t_fg, :, k, area, -1] over the recall thresholds from the unmodified tables (-1 as there); `ap_fixed` (8, K) the same
+        under each oracle; `dap` (8, K) = ap_fixed - ap where both are > -1, NaN elsewhere; `dap_mean` (8,) its mean over those
+        categories (NaN without one); `dropped` (8,) the categories with an ap that an oracle emptied (Miss / FN: npig 0).  In the
+        cuboid modes `loc_errors` (K, 3) = the mean (translation in metres, 1 - aligned IoU, orientation in radians; `kernels.tperr`) over
+        the Loc detections of a category and their attributed ground truths -- whether "poor box" means depth, size or rotation --, NaN
+        without one, `loc_errors_mean` (3,) over the categories with a value and `loc_skipped` the pairs left out because a fit failed;
+        None in mode 2D.  The result is kept for `summarize_errors()`."""
+        self.error_eval = error_analysis(self, t_fg, t_bg, area)
+        return self.error_eval
+
+    def summarize_errors(self):
+        """the table of the last errors(): one line per type with its count and dAP x 100, then the mean Loc pair errors"""
+        if getattr(self, "error_eval", None) is None:
+            raise Exception("Please run errors() first")
+        return "\n".join(error_lines(self._mode, self.params, self.error_eval))
 
 
 from .drivers import (Omni3DEvaluationHelper, Omni3DEvaluator, _derive_results, inference_on_dataset,  # noqa: F401,E402
