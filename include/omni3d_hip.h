@@ -460,6 +460,10 @@ int omni_topk_segments(const float* keys, int rows, long long pitch, int estride
  * mask_ws: Q*nmax*ceil(nmax/64) 64-bit words scratch. nmax <= 8192. */
 int omni_nms_sorted(const float* boxes, const int* counts, const int* valid, int Q, int nmax, float iou_thr,
                     unsigned long long* mask_ws, int* keep, void* stream);
+/* The same, and the scan also writes masked (Q,nmax) = keep ? scores : -inf (every element), the input of the post-NMS
+ * top-k of find_top_rpn_proposals.  scores / masked are nullable, together: omni_nms_sorted forwards here with both null. */
+int omni_nms_sorted_masked(const float* boxes, const int* counts, const int* valid, int Q, int nmax, float iou_thr,
+                           unsigned long long* mask_ws, int* keep, const float* scores, float* masked, void* stream);
 
 /* ---------------------------------------------- RPN / ROI-head box logic (index-exact parts) */
 

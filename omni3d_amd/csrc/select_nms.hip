@@ -9,15 +9,28 @@
 // Top-k: one 1024-thread workgroup per row.  Keys become order-preserving 64-bit integers
 // (float bits, then ~index so that equal scores resolve to the LOWER index = a stable descending
 // sort); an 8-pass MSB-first radix select finds the k-th largest key exactly, survivors are
-// compacted into LDS and bitonic-sorted there.  k <= 8192.  Rows of up to 65536 elements (every row of the training step:
+// compacted into LDS and bitonic-sorted.  k <= 8192.  Rows of up to 65536 elements (every row of the training step:
 // 49152 anchors of the finest level, 65472 sampling keys per image) are read from memory ONCE: each thread keeps the score bits
-// of its <= 64 elements in registers and the radix passes and the compaction run on those (round 3; the passes used to re-read
-// the row, up to 8 x 64 dependent L2 round trips per thread -- 132 / 118 / 48 us for the three launches of a step).
+// of its <= 64 elements in registers and the radix passes and the compaction run on those.
+// Up to 2048 keys are sorted two per thread in registers: strides below 128 are shuffles inside a wave, only the 10 passes of a
+// 2048-key sort whose partner sits in another wave go through LDS and a barrier (all 66 did before).
+// What bounds it (MI355X, the step's 4 x [49152 .. 192] -> 2000 launch, 60.8 us in the kernel trace, 66.8 before): about 23 us are
+// there for a 3072-element row with k = 64 (the two radix selections: up to 8 passes of 4 barriers each), about 10 us more for
+// k = 2000 (compaction, sort, output), and about 28 us more for the 49152-element row (load, the per-thread top 4 over 48
+// elements, the compaction loop); the launch lasts as long as that one row.  Splitting the long row over workgroups does not
+// pay while the fixed part is this large: by the timings per row length a 16384-element slice still costs ~45 us and a
+// finishing selection over 3 x 2000 candidates ~35 us more.
+// The compactions need no hand-written wave aggregation: the compiler already turns the per-lane LDS atomicAdd(.., 1) into one
+// add of the active-lane count per wave (v_mbcnt + s_bcnt1 in the ISA).
 //
-// NMS: boxes arrive sorted by descending score.  A 64x64-bit suppression matrix tile per
-// workgroup (strict IoU > thr, areas (x2-x1)*(y2-y1), no +1), then one wave per problem walks the
-// rows in 64-box chunks: intra-chunk resolution from the diagonal word, then the kept rows OR their
-// mask rows into the running `removed` words (one 64-bit word per lane).
+// NMS: boxes arrive sorted by descending score.  nms_mask_kernel writes a 64x64-bit suppression tile per wave (strict
+// IoU > thr, areas (x2-x1)*(y2-y1), no +1; the quotient is only evaluated in a band of 2^-20 around the threshold), then
+// nms_scan_kernel, one workgroup per problem, walks the rows in 64-box chunks: the chunk is resolved from its diagonal words by a
+// fixed-point iteration of ballots, then the kept rows OR their mask rows into the running `removed` words (one 64-bit word
+// per lane), with the rows of two chunks in flight.  Measured for the step's 20 x 2000 problems at 0.7: mask 70.6 -> 56.1 us
+// (instruction issue: ~23 vector instructions per column and row block, 37 before), scan 115.4 -> 37.0 us (it was a chain of
+// exposed load latencies and 64 cross-lane steps per chunk); with the per-problem counts the proposal path now passes, the
+// padding of the two coarse levels is not visited and both together take 70 us (187 before).  profiles/r07_select_breakdown.log.
 #include <device_rt.h>
 
 namespace {
@@ -358,18 +371,45 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_rows_kernel(const float* __
         }
     }
     __syncthreads();
-    // bitonic sort, descending, kpad a power of two
-    for (int size = 2; size <= kpad; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = t; i < (kpad >> 1); i += TOPK_THREADS) {
-                const int lo = 2 * i - (i & (stride - 1));
-                const int hi = lo + stride;
-                const bool desc = ((lo & size) == 0);
-                const unsigned long long a = sel[lo], b = sel[hi];
-                if ((a < b) == desc) { sel[lo] = b; sel[hi] = a; }
-            }
-            __syncthreads();
+    // bitonic sort, descending, kpad a power of two.  The keys are unique, so the order (ties -> lower index) is fixed by them.
+    auto lds_pass = [&](int size, int stride) {      // one compare-exchange pass through LDS, ends with a barrier
+        for (int i = t; i < (kpad >> 1); i += TOPK_THREADS) {
+            const int lo = 2 * i - (i & (stride - 1));
+            const int hi = lo + stride;
+            const bool desc = ((lo & size) == 0);
+            const unsigned long long a = sel[lo], b = sel[hi];
+            if ((a < b) == desc) { sel[lo] = b; sel[hi] = a; }
         }
+        __syncthreads();
+    };
+    if (kpad <= 2 * TOPK_THREADS) {
+        // up to 2048 keys: thread t keeps elements 2t and 2t + 1 in registers.  Stride 1 is inside the thread, strides 2 .. 64 have
+        // the partner in lane ^ (stride / 2) of the same wave (shuffles, no barrier); only strides >= 128 cross waves and go
+        // through LDS: 10 of the 66 passes of a 2048-key sort.  Slots at and beyond kpad hold zeros and sort among themselves.
+        const int e0 = 2 * t;
+        unsigned long long a0 = e0 < kpad ? sel[e0] : 0ull, a1 = e0 + 1 < kpad ? sel[e0 + 1] : 0ull;
+        for (int size = 2; size <= kpad; size <<= 1) {
+            const bool desc = ((e0 & size) == 0);
+            if (size >= 256) {
+                if (e0 < kpad) { sel[e0] = a0; sel[e0 + 1] = a1; }
+                __syncthreads();
+                for (int stride = size >> 1; stride >= 128; stride >>= 1) lds_pass(size, stride);
+                if (e0 < kpad) { a0 = sel[e0]; a1 = sel[e0 + 1]; }
+            }
+            for (int stride = (size >> 1) < 64 ? (size >> 1) : 64; stride >= 2; stride >>= 1) {
+                const int lm = stride >> 1;                                  // partner lane = lane ^ lm
+                const unsigned long long b0 = __shfl_xor(a0, lm, 64), b1 = __shfl_xor(a1, lm, 64);
+                const bool want_max = ((t & lm) == 0) == desc;               // the lower element of a descending pair keeps the larger key
+                a0 = ((a0 < b0) == want_max) ? b0 : a0;
+                a1 = ((a1 < b1) == want_max) ? b1 : a1;
+            }
+            if ((a0 < a1) == desc) { const unsigned long long s = a0; a0 = a1; a1 = s; }
+        }
+        if (e0 < kpad) { sel[e0] = a0; sel[e0 + 1] = a1; }                  // (own slots: nobody else reads them before the barrier)
+        __syncthreads();
+    } else {
+        for (int size = 2; size <= kpad; size <<= 1)
+            for (int stride = size >> 1; stride > 0; stride >>= 1) lds_pass(size, stride);
     }
     for (int i = t; i < k; i += TOPK_THREADS) {
         const long o = (long)blockIdx.x * k + i;
@@ -381,22 +421,39 @@ __global__ void __launch_bounds__(TOPK_THREADS) topk_rows_kernel(const float* __
 // ---- NMS ---------------------------------------------------------------------------------------
 // problem q: boxes[q*nmax .. q*nmax + count[q]) sorted by descending score; valid[] == 0 marks boxes
 // that take no part (empty / non-finite).  mask: (Q, nmax, words) 64-bit, words = ceil(nmax/64).
-// One 4-wave workgroup = 4 row blocks x one column block (the 64 column boxes are staged in LDS once for the four); round 3:
-// one wave per workgroup before, 20 000 tiny workgroups for the 20 problems of a training step.
+// One 4-wave workgroup = 4 row blocks x one column block: the 64 column boxes AND their areas are staged in LDS once for the four.
+// The loop over the column boxes is wave-uniform, so the column box is one broadcast 16-byte LDS read and the bit to set is a
+// scalar.  The diagonal tile computes all 64 columns too and clears only a row's own bit: the bits below a row's own lane say
+// which boxes AHEAD of it overlap it (the expression is symmetric in the two boxes, bit for bit: min / max, the product, the
+// commutative sum ai + aj), which is what the scan's chunk resolution reads.
+//
+// The decision is iou = inter / (ai + aj - inter) > thr.  The division (scale, reciprocal, refinement, fix-up: 11 of the 37
+// instructions of the old loop body) is only evaluated where it can matter: with u = ai + aj - inter and t = fl(thr * u) in
+// [2^-100, 2^100] and thr > 0 (so u > 0, and t carries a relative error of at most 2^-24),
+//     inter > fl(t * (1 + 2^-20))  =>  inter / u > thr * (1 + 2^-20)(1 - 2^-24)^2 > thr * (1 + 2^-21)  =>  fl(inter / u) > thr
+//     inter < fl(t * (1 - 2^-20))  =>  inter / u < thr * (1 - 2^-20)(1 + 2^-24)^2 < thr * (1 - 2^-21)  =>  fl(inter / u) <= thr
+// (thr * (1 +- 2^-21) lies more than one ulp from thr, and rounding is monotonic).  Every other pair -- the band around the threshold, u <= 0, a non-finite or NaN operand (all
+// comparisons false), a non-positive thr -- evaluates the original expression, so the bits equal the plain quotient's everywhere.
+constexpr float NMS_MARGIN = 9.5367431640625e-07f;          // 2^-20
+constexpr unsigned NMS_T_LO = 0x0D800000u, NMS_T_HI = 0x71800000u;      // float bits of 2^-100 and 2^100
 __global__ void __launch_bounds__(256) nms_mask_kernel(const float* __restrict__ boxes, const int* __restrict__ counts,
                                                        int nmax, int words, float thr,
                                                        unsigned long long* __restrict__ mask) {
+    // every product and sum below rounds on its own, like the reference's: no fused multiply-add may form (ai + aj - w * h)
+#pragma clang fp contract(off)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int q = blockIdx.z, rb = blockIdx.y * 4 + wave, cb = blockIdx.x;
-    const int n = counts ? counts[q] : nmax;
+    const int n = counts ? min(max(counts[q], 0), nmax) : nmax;      // (never past the problem's slots, whatever the caller passes)
     if ((int)blockIdx.y * 4 > cb || cb * 64 >= n) return;            // (uniform) nothing above the diagonal / past the count here
-    __shared__ float cbx[64 * 4];
+    __shared__ float4 cbx[64];
+    __shared__ float car[64];
     const float* B = boxes + (long)q * nmax * 4;
     if (wave == 0) {
         const int j = cb * 64 + lane;
         if (j < n) {
-            cbx[lane * 4 + 0] = B[j * 4 + 0]; cbx[lane * 4 + 1] = B[j * 4 + 1];
-            cbx[lane * 4 + 2] = B[j * 4 + 2]; cbx[lane * 4 + 3] = B[j * 4 + 3];
+            const float u1 = B[j * 4 + 0], v1 = B[j * 4 + 1], u2 = B[j * 4 + 2], v2 = B[j * 4 + 3];
+            cbx[lane] = make_float4(u1, v1, u2, v2);
+            car[lane] = (u2 - u1) * (v2 - v1);
         }
     }
     __syncthreads();
@@ -405,89 +462,148 @@ __global__ void __launch_bounds__(256) nms_mask_kernel(const float* __restrict__
     if (i >= n) return;
     const float x1 = B[i * 4 + 0], y1 = B[i * 4 + 1], x2 = B[i * 4 + 2], y2 = B[i * 4 + 3];
     const float ai = (x2 - x1) * (y2 - y1);
-    unsigned long long bits = 0ull;
+    const bool shortcut = thr > 0.f;                                  // (uniform)
+    const float khi = 1.f + NMS_MARGIN, klo = 1.f - NMS_MARGIN;
     const int jmax = (n - cb * 64) < 64 ? (n - cb * 64) : 64;
-    for (int jj = (rb == cb ? lane + 1 : 0); jj < jmax; ++jj) {
-        const float u1 = cbx[jj * 4 + 0], v1 = cbx[jj * 4 + 1], u2 = cbx[jj * 4 + 2], v2 = cbx[jj * 4 + 3];
-        const float w = fmaxf(fminf(x2, u2) - fmaxf(x1, u1), 0.f);
-        const float h = fmaxf(fminf(y2, v2) - fmaxf(y1, v1), 0.f);
+    unsigned long long bits = 0ull;
+#pragma unroll 4
+    for (int jj = 0; jj < jmax; ++jj) {
+        const float4 c = cbx[jj];
+        const float aj = car[jj];
+        const float w = fmaxf(fminf(x2, c.z) - fmaxf(x1, c.x), 0.f);
+        const float h = fmaxf(fminf(y2, c.w) - fmaxf(y1, c.y), 0.f);
         const float inter = w * h;
-        const float aj = (u2 - u1) * (v2 - v1);
-        const float iou = inter / (ai + aj - inter);
-        if (iou > thr) bits |= (1ull << jj);
+        const float u = ai + aj - inter;
+        const float t = thr * u;
+        const bool ranged = shortcut & ((__float_as_uint(t) - NMS_T_LO) <= (NMS_T_HI - NMS_T_LO));
+        bool over = inter > t * khi;
+        const bool under = inter < t * klo;
+        if (!(ranged & (over | under))) over = inter / u > thr;     // (a branch: a wave skips the division unless a lane needs it)
+        if (over) bits |= (1ull << jj);
     }
+    if (rb == cb) bits &= ~(1ull << lane);                            // a box does not suppress itself
     mask[((long)q * nmax + i) * words + cb] = bits;
 }
 
-constexpr int SCAN_WAVES = 16;      // waves per problem of the scan (4 / 8 measured slower: 250 / 230 against 189 us for mask + scan, profiles/HISTORY.md)
-template <int NMS_SCAN_WAVES>
+// One workgroup of NMS_SCAN_WAVES waves per problem walks the rows in 64-box chunks.  Per chunk: wave 0 resolves the chunk greedily
+// from the diagonal words, then every wave ORs the mask rows of the kept boxes among ITS 64 / NMS_SCAN_WAVES rows of the chunk into a
+// running per-wave `removed` set that lives in registers (lane l holds words l and 64 + l: <= 128 words = 8192 boxes).  The only
+// word anybody needs next is word c + 1, so each wave publishes that one word and wave 0 ORs them -- two barriers per chunk.
+//  * Resolution.  Lane j knows `below` = the boxes ahead of it in the chunk that overlap it (the low bits of its own diagonal
+//    word: the relation is symmetric).  The greedy keep set K is the only set with  j in K  <=>  j starts alive and no box of
+//    `below` is in K  (induction over j), and iterating K <- ballot(alive_j && !(below_j & K)) from K = alive fixes one more lane
+//    per round at the least, so it is reached after at most 64 rounds -- in practice after as many rounds as the longest
+//    chain "a suppresses b, which would have suppressed c" is long.  A round is a ballot and a handful of scalar instructions;
+//    the 64-step walk over the lanes cost two cross-lane reads per lane, whatever the boxes.
+//  * Prefetch.  The mask rows, diagonal words included, of TWO chunks are in flight (register sets A and B, the chunk loop is
+//    unrolled by two): the rows of chunk c + 2 are requested after the OR of chunk c and consumed two resolutions later.  They are
+//    buffer loads whose offset is out of range where a guard fails, not branches around loads: every wave issues the same
+//    number of loads per chunk, so the compiler can wait for "all but the youngest set" (a load in a branch forces a wait for
+//    everything outstanding, which is what the single-set version did at every resolution).  All 64 rows of a chunk are fetched
+//    before its resolution decides which are needed, and selected by the `alive` bits afterwards.
+//  * The valid flags become one bit mask in LDS before the first chunk, and the kept bits collect in LDS and are written as keep
+//    (and, for the proposal path, masked = keep ? score : -inf) after the last one: the chunk loop has no load that is consumed
+//    where it is issued and no store.
+// Only entries the mask kernel wrote are ever selected (row < n, word > chunk, word * 64 < n), and nothing outside the problem's
+// scratch is loaded (the buffer resource ends with it; word < words, chunk < nchunks), so the scratch needs no zeroing.
+constexpr int SCAN_WAVES = 16;      // waves per problem of the scan
+// WIDE: more than 64 words per row (nmax > 4096), the second register word of the removed set is in use
+template <int NMS_SCAN_WAVES, bool WIDE>
 __global__ void __launch_bounds__(64 * NMS_SCAN_WAVES) nms_scan_kernel(const unsigned long long* __restrict__ mask,
                                                                        const int* __restrict__ counts, const int* __restrict__ valid,
-                                                                       int nmax, int words, int* __restrict__ keep) {
-    // One workgroup of NMS_SCAN_WAVES waves per problem.  Per 64-box chunk: wave 0 resolves the chunk greedily (64 shuffle steps),
-    // then every wave ORs the mask rows of the kept boxes among ITS 64 / NMS_SCAN_WAVES rows of the chunk into a running per-wave
-    // `removed` set that lives in registers (lane l holds words l and 64 + l: <= 128 words = 8192 boxes).  The only word anybody
-    // needs next is word c + 1, so each wave publishes that one word and wave 0 ORs them -- two barriers per chunk.
-    // Round 3: (1) the mask rows of a chunk are fetched BEFORE its resolution decides which are needed (all 64, selected by the
-    // `alive` bits afterwards): the loads of chunk c + 1 fly under the work of chunk c instead of sitting between two barriers;
-    // (2) 2 barriers per chunk instead of 3 and no LDS pass over the partial sets.  Measured for the 20 x 2000-box problems of a
-    // training step: 138 us before, 119 us with (1), 181 us with (1) + (2) on 4 waves (16 rows = 32 loads per lane and chunk queue up
-    // behind each other), 16 waves: see profiles/README.md.  Only entries the mask kernel wrote are ever selected (row < n, word >
-    // chunk, word * 64 < n), so the scratch needs no zeroing.
+                                                                       int nmax, int words, int* __restrict__ keep,
+                                                                       const float* __restrict__ scores, float* __restrict__ masked) {
     constexpr int RPW = 64 / NMS_SCAN_WAVES;            // rows of a chunk per wave
+    constexpr int NT = 64 * NMS_SCAN_WAVES;
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = counts ? counts[q] : nmax;
+    const int n = counts ? min(max(counts[q], 0), nmax) : nmax;      // (never past the problem's slots, whatever the caller passes)
     __shared__ unsigned long long s_alive;
     __shared__ unsigned long long s_next[NMS_SCAN_WAVES];
-    for (int i = n + tid; i < nmax; i += 64 * NMS_SCAN_WAVES) keep[(long)q * nmax + i] = 0;      // boxes beyond the count are never kept
+    __shared__ unsigned long long s_valid[128], s_keep[128];
     const int nchunks = (n + 63) / 64;
-    unsigned long long rw0[RPW], rw1[RPW], diag = 0ull, acc0 = 0ull, acc1 = 0ull, removed_c = 0ull;
-    int okv = 0;
-    auto fetch = [&](int c) {
+    const omni_rsrc_t mr = omni_make_rsrc(mask + (long)q * nmax * words, (unsigned)nmax * (unsigned)words * 8u);
+    auto load64 = [&](bool ok, int word_index) -> unsigned long long {
+        const int off = ok ? word_index * 8 : OMNI_OOB;                 // (word_index < nmax * words <= 2^20)
+        const unsigned lo = omni_bufld1(mr, off), hi = omni_bufld1(mr, ok ? off + 4 : OMNI_OOB);
+        return ((unsigned long long)hi << 32) | lo;
+    };
+    struct Rows { unsigned long long w0[RPW], w1[RPW], diag; };
+    Rows A, B;
+    auto fetch = [&](int c, Rows& R) {
+        const bool live = c < nchunks;
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
             const int row = c * 64 + wave * RPW + rr;
-            const long rowbase = ((long)q * nmax + row) * words;
             const int w0 = lane, w1 = 64 + lane;
-            rw0[rr] = (row < n && w0 > c && w0 < words && w0 * 64 < n) ? mask[rowbase + w0] : 0ull;
-            rw1[rr] = (words > 64 && row < n && w1 > c && w1 < words && w1 * 64 < n) ? mask[rowbase + w1] : 0ull;
+            R.w0[rr] = load64(live && row < n && w0 > c && w0 < words && w0 * 64 < n, row * words + w0);
+            R.w1[rr] = WIDE ? load64(live && row < n && w1 > c && w1 < words && w1 * 64 < n, row * words + w1) : 0ull;
         }
-        if (wave == 0) {
-            const int i = c * 64 + lane;
-            diag = i < n ? mask[((long)q * nmax + i) * words + c] : 0ull;
-            okv = (i < n && (valid == nullptr || valid[(long)q * nmax + i] != 0)) ? 1 : 0;
-        }
+        const int i = c * 64 + lane;
+        R.diag = load64(wave == 0 && live && i < n, i * words + c);
     };
-    if (nchunks > 0) fetch(0);
-    for (int c = 0; c < nchunks; ++c) {
+    fetch(0, A);
+    fetch(1, B);
+    {
+        // valid flags -> one bit per box.  Buffer loads again, and a fixed trip count (128 chunks at the most): a load under a
+        // branch here would be younger than the two fetches above and make the first resolution wait for all three.
+        const omni_rsrc_t vr = omni_make_rsrc(valid ? valid + (long)q * nmax : nullptr, valid ? (unsigned)nmax * 4u : 0u);
+        unsigned flag[128 / NMS_SCAN_WAVES];
+#pragma unroll
+        for (int j = 0; j < 128 / NMS_SCAN_WAVES; ++j) {
+            const int i = (j * NMS_SCAN_WAVES + wave) * 64 + lane;
+            flag[j] = omni_bufld1(vr, i < n ? i * 4 : OMNI_OOB);
+        }
+#pragma unroll
+        for (int j = 0; j < 128 / NMS_SCAN_WAVES; ++j) {             // (whole waves: the ballot)
+            const int c = j * NMS_SCAN_WAVES + wave, i = c * 64 + lane;
+            const unsigned long long ok = __ballot(i < n && (valid == nullptr || flag[j] != 0u));
+            if (lane == 0 && c < nchunks) s_valid[c] = ok;
+        }
+    }
+    __syncthreads();
+    unsigned long long acc0 = 0ull, acc1 = 0ull, removed_c = 0ull;
+    auto step = [&](int c, Rows& R) {
         if (wave == 0) {
-            const int i = c * 64 + lane;
-            // start state of this chunk: not removed by earlier keeps, and a valid box
-            unsigned long long alive = __ballot(okv != 0) & ~removed_c;
-            for (int r = 0; r < 64; ++r) {
-                const unsigned long long d = __shfl(diag, r, 64);
-                if ((alive >> r) & 1ull) alive &= ~d;
-            }
-            if (i < n) keep[(long)q * nmax + i] = (int)((alive >> lane) & 1ull);
-            if (lane == 0) s_alive = alive;
+            // start state of this chunk: a valid box that no earlier keep removed
+            const bool ok = (((s_valid[c] & ~removed_c) >> lane) & 1ull) != 0ull;
+            const unsigned long long below = R.diag & ((1ull << lane) - 1ull);
+            unsigned long long alive = __ballot(ok), prev;
+            do {
+                prev = alive;
+                alive = __ballot(ok && (below & prev) == 0ull);
+            } while (alive != prev);
+            if (lane == 0) { s_alive = alive; s_keep[c] = alive; }
         }
         __syncthreads();
         const unsigned long long alive = s_alive;
 #pragma unroll
         for (int rr = 0; rr < RPW; ++rr) {
-            if ((alive >> (wave * RPW + rr)) & 1ull) { acc0 |= rw0[rr]; acc1 |= rw1[rr]; }
+            if ((alive >> (wave * RPW + rr)) & 1ull) { acc0 |= R.w0[rr]; acc1 |= R.w1[rr]; }
         }
         // word c + 1 of this wave's removed set sits in lane (c + 1) % 64 of acc0 (c + 1 < 64) or acc1
         const int nw = c + 1;
         const unsigned long long mine = __shfl(nw < 64 ? acc0 : acc1, nw & 63, 64);
         if (lane == 0) s_next[wave] = mine;
-        if (c + 1 < nchunks) fetch(c + 1);
+        fetch(c + 2, R);
         __syncthreads();
         if (wave == 0) {
             removed_c = 0ull;
 #pragma unroll
             for (int k = 0; k < NMS_SCAN_WAVES; ++k) removed_c |= s_next[k];
         }
+    };
+    // (no branch inside the loop body: on a path around step B the loads of set A would be the youngest at the next resolution,
+    // and the compiler would have to wait for everything there)
+    for (int c = 0; c + 1 < nchunks; c += 2) {
+        step(c, A);
+        step(c + 1, B);
+    }
+    if (nchunks & 1) step(nchunks - 1, A);
+    // every element of keep (and masked) is written; boxes beyond the count are never kept
+    for (int i = tid; i < nmax; i += NT) {
+        const bool kept = i < n && ((s_keep[i >> 6] >> (i & 63)) & 1ull) != 0ull;
+        keep[(long)q * nmax + i] = kept ? 1 : 0;
+        if (masked != nullptr) masked[(long)q * nmax + i] = kept ? scores[(long)q * nmax + i] : -INFINITY;
     }
 }
 
@@ -545,17 +661,28 @@ int omni_topk_segments(const float* keys, int rows, long long pitch, int estride
 // counts [nullable] (Q) active boxes per problem; valid [nullable] (Q, nmax) 0 = box takes no part.
 // mask_ws: Q * nmax * ceil(nmax/64) 64-bit words of scratch (need not be zeroed: only entries the mask kernel writes are read).
 // keep (Q, nmax) int32 out (0/1), every element written.
-int omni_nms_sorted(const float* boxes, const int* counts, const int* valid, int Q, int nmax, float iou_thr,
-                    unsigned long long* mask_ws, int* keep, void* stream) {
-    if (Q < 0 || nmax < 0 || nmax > 8192) return OMNI_ERR_ARG;
+// scores / masked [both nullable, together] (Q, nmax): masked = keep ? scores : -inf, every element written by the scan itself
+// (the input of the post-NMS top-k of the proposal path).
+int omni_nms_sorted_masked(const float* boxes, const int* counts, const int* valid, int Q, int nmax, float iou_thr,
+                           unsigned long long* mask_ws, int* keep, const float* scores, float* masked, void* stream) {
+    if (Q < 0 || nmax < 0 || nmax > 8192 || (scores == nullptr) != (masked == nullptr)) return OMNI_ERR_ARG;
     if (Q == 0 || nmax == 0) return OMNI_OK;
     const int words = (nmax + 63) / 64;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(nms_mask_kernel, dim3(words, (words + 3) / 4, Q), dim3(256), 0, st, boxes, counts, nmax, words, iou_thr,
                        mask_ws);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(nms_scan_kernel<SCAN_WAVES>), dim3(Q), dim3(64 * SCAN_WAVES), 0, st, (const unsigned long long*)mask_ws,
-                       counts, valid, nmax, words, keep);
+    if (words > 64)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(nms_scan_kernel<SCAN_WAVES, true>), dim3(Q), dim3(64 * SCAN_WAVES), 0, st,
+                           (const unsigned long long*)mask_ws, counts, valid, nmax, words, keep, scores, masked);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(nms_scan_kernel<SCAN_WAVES, false>), dim3(Q), dim3(64 * SCAN_WAVES), 0, st,
+                           (const unsigned long long*)mask_ws, counts, valid, nmax, words, keep, scores, masked);
     return omni_launch_status();
+}
+
+int omni_nms_sorted(const float* boxes, const int* counts, const int* valid, int Q, int nmax, float iou_thr,
+                    unsigned long long* mask_ws, int* keep, void* stream) {
+    return omni_nms_sorted_masked(boxes, counts, valid, Q, nmax, iou_thr, mask_ws, keep, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

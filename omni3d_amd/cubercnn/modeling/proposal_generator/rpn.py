@@ -179,10 +179,20 @@ class RPNWithIgnore(nn.Module):
         if getattr(self, "_slot_key", None) != key:
             self._slot_level = torch.arange(L, dtype=torch.int32, device=idx.device).repeat_interleave(kmax).contiguous()
             self._slot_key = key
+        # real candidates per (image, level) problem: a level with fewer than kmax anchors fills the rest of its slots with padding
+        # (index -1, decoded as an invalid zero box), which the NMS kernels then need not visit at all.  One tensor per input
+        # shape, and none is ever dropped: a captured step of another shape bucket still reads the one it was captured with.
+        ckey = (B, tuple(seg_n), kmax, str(idx.device))
+        counts = self.__dict__.setdefault("_slot_counts", {}).get(ckey)
+        if counts is None:
+            per_level = torch.cat([torch.full((1,), min(kmax, n), dtype=torch.int32, device=idx.device) for n in seg_n])
+            counts = self._slot_counts[ckey] = per_level.repeat(B).contiguous()
         boxes, valid = det.rpn_decode(pack, self._slot_level, idx, anchors, image_hw, self.min_box_size)
-        keep = select.nms_sorted(boxes.view(B * L, kmax, 4), self.nms_thresh, None, valid.view(B * L, kmax)).view(B, L * kmax)
-        masked = det.rpn_mask_scores(scores.contiguous(), keep.contiguous())     # suppressed / invalid candidates -> -inf
-        top_v, top_i = select.topk_rows(masked, post)                             # keep[:post_nms_topk], score order
+        # the scan writes keep and masked = keep ? score : -inf (suppressed / invalid candidates and padding -> -inf)
+        keep, masked = select.nms_sorted_masked(boxes.view(B * L, kmax, 4), scores.contiguous().view(B * L, kmax), self.nms_thresh,
+                                                counts, valid.view(B * L, kmax))
+        keep = keep.view(B, L * kmax)
+        top_v, top_i = select.topk_rows(masked.view(B, L * kmax), post)           # keep[:post_nms_topk], score order
         prop, count = det.rpn_collect(boxes, top_v, top_i)                        # boxes of the real entries, zeros behind; #real
         if getattr(self, "keep_candidates", False):      # parity tests: the pre-NMS candidate lists behind the proposal set
             self.last_candidates = {"boxes": boxes, "scores": scores, "keep": keep, "valid": valid.view(B, L * kmax), "slots_per_level": kmax}

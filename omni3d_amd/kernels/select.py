@@ -42,18 +42,38 @@ def topk_segments(keys, seg_off, seg_n, k):
     return vals, idx
 
 
-def nms_sorted(boxes, iou_thr, counts=None, valid=None, _poison=False):
-    """boxes (Q, nmax, 4) sorted by descending score -> keep (Q, nmax) int32.  (_poison: tests fill the scratch and the output
-    with garbage first -- the kernels must not depend on their previous contents.)"""
+def _nms(boxes, iou_thr, counts, valid, scores, _poison, _ws_out=None):
     boxes = boxes.contiguous()
     Q, nmax, _ = boxes.shape
-    L = _lib.check_device(boxes, counts, valid)
+    L = _lib.check_device(boxes, counts, valid, scores)
     words = (nmax + 63) // 64
     ws = torch.empty(max(Q * nmax * words, 1), dtype=torch.int64, device=boxes.device)
     keep = torch.empty((Q, nmax), dtype=torch.int32, device=boxes.device)
+    masked = None if scores is None else torch.empty((Q, nmax), dtype=torch.float32, device=boxes.device)
     if _poison:
         ws.fill_(-1)
         keep.fill_(7)
-    L.call("omni_nms_sorted", _lib.ptr(boxes), _lib.ptr(counts), _lib.ptr(valid), Q, nmax, float(iou_thr), _lib.ptr(ws),
-           _lib.ptr(keep), _lib.stream_of(boxes))
-    return keep
+        if masked is not None:
+            masked.fill_(7.0)
+    if scores is None:
+        L.call("omni_nms_sorted", _lib.ptr(boxes), _lib.ptr(counts), _lib.ptr(valid), Q, nmax, float(iou_thr), _lib.ptr(ws),
+               _lib.ptr(keep), _lib.stream_of(boxes))
+    else:
+        L.call("omni_nms_sorted_masked", _lib.ptr(boxes), _lib.ptr(counts), _lib.ptr(valid), Q, nmax, float(iou_thr), _lib.ptr(ws),
+               _lib.ptr(keep), _lib.ptr(scores), _lib.ptr(masked), _lib.stream_of(boxes))
+    if _ws_out is not None:
+        _ws_out.append(ws)
+    return keep, masked
+
+
+def nms_sorted(boxes, iou_thr, counts=None, valid=None, _poison=False, _ws_out=None):
+    """boxes (Q, nmax, 4) sorted by descending score -> keep (Q, nmax) int32.  (_poison: tests fill the scratch and the output
+    with garbage first -- the kernels must not depend on their previous contents; _ws_out: a list that receives the mask scratch.)"""
+    return _nms(boxes, iou_thr, counts, valid, None, _poison, _ws_out)[0]
+
+
+def nms_sorted_masked(boxes, scores, iou_thr, counts=None, valid=None, _poison=False):
+    """nms_sorted that also returns masked (Q, nmax) = where(keep, scores, -inf), written by the scan kernel itself."""
+    if scores.shape != boxes.shape[:2] or scores.dtype != torch.float32:
+        raise ValueError("scores must be float32 of shape (Q, nmax)")
+    return _nms(boxes, iou_thr, counts, valid, scores, _poison)
