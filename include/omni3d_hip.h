@@ -903,6 +903,20 @@ int omni_eval_accumulate(const int* order, const int* cat_off, const int* rank, 
                          const int* max_dets, int K, int A, int M, int T, int R, int sumD, double* precision, double* recall,
                          double* scores, void* stream);
 
+/* omni_eval_accumulate over many workgroups per list (csrc/eval_accumulate_par.hip), for lists too long for one wave: with useCats = 0
+ * there is one list of all detections.  The arguments of omni_eval_accumulate, plus `block` = the elements of `order` per workgroup (a
+ * multiple of 64) and a workspace of the caller of at least omni_eval_accumulate_par_workspace(...) bytes, 8-byte aligned, contents
+ * irrelevant before and after.  No list may be longer than sumD.  Three plain launches on `stream` (per block: counts; the prefix of the
+ * counts and the block's largest precision; the carry of the later blocks and the backward sweep); no atomics, no grid-wide barrier.
+ * precision / recall / scores are bit for bit those of omni_eval_accumulate, the -1 of the caller and the 0.0 fills included.
+ * OMNI_ERR_ARG before any launch: the conditions of omni_eval_accumulate, a block that is no positive multiple of 64, a missing,
+ * misaligned or short workspace, K x A x M x T x ceil(sumD / block) >= 2^31. */
+int omni_eval_accumulate_par_workspace(int K, int A, int M, int T, int sumD, int block, long long* bytes);
+int omni_eval_accumulate_par(const int* order, const int* cat_off, const int* rank, const double* score, const int* dt_match,
+                             const unsigned char* dt_ignore, const int* npig, const int* has_e, const double* rec_thrs,
+                             const int* max_dets, int K, int A, int M, int T, int R, int sumD, int block, void* workspace,
+                             long long workspace_bytes, double* precision, double* recall, double* scores, void* stream);
+
 /* The image-level bootstrap of Omni3Deval.accumulate (csrc/eval_bootstrap.hip): AP and recall of B resampled data sets from one set of
  * match tables, for `Omni3Deval.bootstrap`.  The reference has no counterpart.  Replicate b is the row weights[b] (I) of non-negative
  * image multiplicities; its result is by definition what omni_eval_accumulate gives on the data set that holds image i weights[b][i]

@@ -252,6 +252,29 @@ def error_eval_args(cfg):
     return {"errors": out if bool(get("ENABLED")) else None}
 
 
+_EVAL_AGNOSTIC = {"ENABLED": False}
+
+
+def add_agnostic_eval_config(cfg):
+    """TEST.EVAL_AGNOSTIC.*: class-agnostic AP and AR next to every AP the evaluation reports (`Omni3Deval` with `params.useCats = 0`,
+    csrc/eval_accumulate_par.hip): every enabled mode is evaluated a second time with one group per image and the categories ignored --
+    is the cuboid wrong, or only its label?  The reference's evaluator has the switch but no config key, and `get_cfg_defaults` stays key
+    for key what the reference defines, so, as with `add_bev_eval_config`, the node is absent until this call; without it nothing is
+    evaluated class-agnostically.  Idempotent: values already set are kept."""
+    if "EVAL_AGNOSTIC" not in cfg.TEST:
+        cfg.TEST.EVAL_AGNOSTIC = CN()
+    for key, value in _EVAL_AGNOSTIC.items():
+        cfg.TEST.EVAL_AGNOSTIC.setdefault(key, value)
+    return cfg
+
+
+def agnostic_eval_args(cfg):
+    """TEST.EVAL_AGNOSTIC -> the keyword argument of `Omni3DEvaluationHelper` / `Omni3DEvaluator`:
+    `Omni3DEvaluationHelper(names, filter_settings, folder, **agnostic_eval_args(cfg))`.  A cfg without the node: the feature off."""
+    node = cfg.TEST.get("EVAL_AGNOSTIC")
+    return {"eval_agnostic": False if node is None else bool(node.ENABLED)}
+
+
 _TTA = {"MIN_SIZES": (), "MAX_SIZE": 4000, "FLIP": True, "FUSE_IOU_THRESH": 0.5, "CLASS_AGNOSTIC": False}
 
 

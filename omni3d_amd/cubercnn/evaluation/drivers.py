@@ -77,6 +77,18 @@ def _make_eval(gt, dt, mode, eval_prox, opts):
     return ev
 
 
+def _agnostic_pass(ev):
+    """the class-agnostic pass of a mode (`params.useCats = 0`) on a freshly made evaluator -> (the mode's seven headline APs under
+    their usual names and AR1 / AR10 / AR100, all x100 and NaN when undefined; the summary text)"""
+    ev.params.useCats = 0
+    ev.evaluate()
+    ev.accumulate()
+    text = ev.summarize()
+    res = {name: _percent(ev.stats[i]) for i, name in enumerate(ev._mode.metrics)}
+    res.update({"AR%d" % m: _percent(ev.stats[7 + i]) for i, m in enumerate((1, 10, 100))})
+    return res, text
+
+
 class Omni3DEvaluator:
     """Per-dataset evaluator (reference :643-935, a detectron2 COCOEvaluator subclass).
 
@@ -111,12 +123,19 @@ class Omni3DEvaluator:
     errors (extension, off by default; None or a dict with some of `t_fg`, `t_bg`, applied to the modes of the 3D protocol -- mode 2D
     keeps its own): every evaluated mode except DIST also gets 'bbox_<mode>_errors' = the error decomposition of
     `Omni3Deval.errors`: {'t_fg', 't_bg', 'counts': {type: n}, 'dAP': {oracle: mean dAP x 100}, 'loc_errors': {'trans', 'scale',
-    'orient'} or None in 2D} (short form: 'errors_<mode>'); nothing else changes."""
+    'orient'} or None in 2D} (short form: 'errors_<mode>'); nothing else changes.
+
+    eval_agnostic (the reference evaluator's `useCats = 0`, off by default): every evaluated mode gets a second pass with
+    `params.useCats = 0` after its ordinary one -- one group per image, the categories ignored -- which adds 'bbox_<mode>_agnostic' =
+    the mode's seven headline APs under their usual names plus 'AR1', 'AR10', 'AR100', and 'log_str_<mode>_agnostic' (short form:
+    'agnostic_<mode>'); nothing else changes."""
 
     def __init__(self, dataset_name, tasks=None, distributed=True, output_dir=None, *, max_dets_per_image=None, use_fast_impl=False,
                  eval_prox=False, only_2d=False, filter_settings=None, img_ids=None, cat_ids=None, eval_bev=False, bev_up=BEV_UP,
-                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None, errors=None):
+                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None, errors=None,
+                 eval_agnostic=False):
         self._only_2d, self._eval_prox, self._output_dir, self._distributed = only_2d, eval_prox, output_dir, distributed
+        self._eval_agnostic = bool(eval_agnostic)
         self._bootstrap, self._errors = _bootstrap_params(bootstrap), _error_params(errors)
         self._opts = check_options(let_params=let_params, bev_up=bev_up, dist_up=dist_up, dist_params=dist_params)
         self._switches = {"eval_bev": bool(eval_bev), "eval_dist": bool(eval_dist), "eval_let": bool(eval_let)}
@@ -171,6 +190,9 @@ class Omni3DEvaluator:
                 res["AP" + mode + "_ci"] = _bootstrap_ci(ev, mode, None, self._bootstrap)["AP"]
             if self._errors is not None and MODES[mode].error_thrs is not None:
                 res["errors_" + mode] = error_summary(ev, self._errors)
+            if self._eval_agnostic:
+                res["agnostic_" + mode] = _agnostic_pass(self._make_eval(AnnotationIndex(copy.deepcopy(self._gt), self._img_ids, self._cat_ids),
+                                                                         AnnotationIndex(copy.deepcopy(self._predictions), self._img_ids, self._cat_ids), mode))[0]
         return {"bbox": res}
 
     def evaluate(self, img_ids=None):
@@ -228,6 +250,11 @@ class Omni3DEvaluator:
                 self._results["bbox_" + mode + "_errors"] = error_summary(ev, self._errors)
             self._results["bbox_" + mode + "_merge"] = {"gt": self._omni_api, "dt": kept, "eval_prox": self._eval_prox,
                                                         "img_ids": list(ev.params.imgIds), "cat_ids": list(ev.params.catIds)}
+            if self._eval_agnostic:
+                ev = self._make_eval(self._omni_api, omni_dt, mode, self._eval_prox)
+                if img_ids is not None:
+                    ev.params.imgIds = img_ids
+                self._results["bbox_" + mode + "_agnostic"], self._results["log_str_" + mode + "_agnostic"] = _agnostic_pass(ev)
         return copy.deepcopy({k: v for k, v in self._results.items() if not k.endswith("_merge")}) | \
             {k: v for k, v in self._results.items() if k.endswith("_merge")}
 
@@ -247,10 +274,15 @@ class Omni3DEvaluationHelper:
 
     errors (extension, off by default; None or the dict `Omni3DEvaluator` takes): every split's result gets 'bbox_<mode>_errors' for
     every evaluated mode except DIST, `results_errors[name]` = {'iters', '<mode>': {oracle: mean dAP x 100}, ...}, and one log line
-    per split.  The printed tables do not change."""
+    per split.  The printed tables do not change.
+
+    eval_agnostic (off by default; the switch `Omni3DEvaluator` takes): every split's result gets 'bbox_<mode>_agnostic' and
+    'log_str_<mode>_agnostic', `results_agnostic[name]` = {'iters', '<mode>': {the seven headline APs, 'AR1', 'AR10', 'AR100'}, ...}
+    per split and for <Concat>, and one log line per split.  The printed tables do not change."""
 
     def __init__(self, dataset_names, filter_settings, output_folder, iter_label="-", only_2d=False, eval_bev=False, bev_up=BEV_UP,
-                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None, errors=None):
+                 eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None, errors=None,
+                 eval_agnostic=False):
         from collections import OrderedDict
         from ...d2.data import MetadataCatalog
         from ..data.datasets import simple_register
@@ -270,6 +302,8 @@ class Omni3DEvaluationHelper:
         self.bootstrap, self.results_ci = _bootstrap_params(bootstrap), OrderedDict()
         # extension (off by default): the error decomposition of every mode but DIST per split, in `results_errors`
         self.errors, self.results_errors = _error_params(errors), OrderedDict()
+        # the reference evaluator's useCats = 0 (off by default): class-agnostic AP / AR of every mode per split and for <Concat>
+        self.eval_agnostic, self.results_agnostic = bool(eval_agnostic), OrderedDict()
         self.overall_imgIds, self.overall_catIds = set(), set()
         self.output_folders = {n: os.path.join(output_folder, n) for n in self.dataset_names}
         for name in self.dataset_names:
@@ -277,7 +311,8 @@ class Omni3DEvaluationHelper:
                 simple_register(name, filter_settings, filter_empty=False)
             ev = Omni3DEvaluator(name, output_dir=self.output_folders[name], filter_settings=filter_settings, only_2d=only_2d,
                                  eval_prox=("Objectron" in name or "SUNRGBD" in name), distributed=False, eval_bev=self.eval_bev,
-                                 eval_dist=self.eval_dist, eval_let=self.eval_let, bootstrap=self.bootstrap, errors=self.errors, **self._opts)
+                                 eval_dist=self.eval_dist, eval_let=self.eval_let, bootstrap=self.bootstrap, errors=self.errors,
+                                 **({"eval_agnostic": True} if self.eval_agnostic else {}), **self._opts)
             ev.reset()
             self.evaluators[name] = ev
             self.overall_imgIds.update(ev._omni_api.getImgIds())
@@ -344,6 +379,11 @@ class Omni3DEvaluationHelper:
                                                                                if "bbox_" + mode + "_errors" in res}}
             log.info("{} iter={} error decomposition, dAP per oracle: {}".format(dataset_name, self.iter_label, {
                 mode: {k: round(v, 2) for k, v in row.items()} for mode, row in self.results_errors[dataset_name].items() if mode != "iters"}))
+        if self.eval_agnostic and "bbox_2D_agnostic" in res:
+            self.results_agnostic[dataset_name] = {"iters": self.iter_label, **{mode: res["bbox_" + mode + "_agnostic"] for mode in self.modes
+                                                                                 if "bbox_" + mode + "_agnostic" in res}}
+            log.info("{} iter={} class-agnostic AP / AR100: {}".format(dataset_name, self.iter_label, {
+                mode: (round(row["AP"], 2), round(row["AR100"], 2)) for mode, row in self.results_agnostic[dataset_name].items() if mode != "iters"}))
         logperf.print_ap_category_histogram(dataset_name, self._per_category(r2, r3))
 
     def _per_category(self, r2, r3):
@@ -367,7 +407,7 @@ class Omni3DEvaluationHelper:
         cat_ids = sorted(self.overall_catIds)
         ordered = [meta.thing_classes[meta.thing_dataset_id_to_contiguous_id[c]] for c in cat_ids]
         categories = set(ordered)
-        merged, merged_ci = {}, {}
+        merged, merged_ci, merged_agnostic = {}, {}, {}
         for mode in self.modes:
             gts, dts, prox_imgs, strata = [], [], set(), {}
             for name in self.dataset_names:
@@ -390,10 +430,16 @@ class Omni3DEvaluationHelper:
                 merged_ci[mode] = _bootstrap_ci(ev, mode, None, self.bootstrap, strata={i: strata.get(i, "") for i in ev.params.imgIds})
             if len(ordered) == 1:
                 MODES[mode].single_class(merged[mode], ordered[0])
+            if self.eval_agnostic:
+                merged_agnostic[mode] = _agnostic_pass(_make_eval(
+                    AnnotationIndex(copy.deepcopy(gts), self.overall_imgIds, cat_ids), AnnotationIndex(copy.deepcopy(dts), self.overall_imgIds, cat_ids),
+                    mode, (prox_imgs if prox_imgs else False), self._opts))[0]
         r2, r3 = merged["2D"], merged.get("3D", {})
         self._mode_rows("<Concat>", merged.get, categories)
         if "2D" in merged_ci:
             self.results_ci["<Concat>"] = self._ci_row(merged_ci["2D"], merged_ci.get("3D"))
+        if self.eval_agnostic:
+            self.results_agnostic["<Concat>"] = {"iters": self.iter_label, **merged_agnostic}
         self.results_analysis["<Concat>"] = self._analysis_row(r2, r3, categories)
         for label, key in (("Omni3D_Out", "omni3d_out"), ("Omni3D_In", "omni3d_in"), ("Omni3D", "omni3d")):
             want = get_omni3d_categories(key)

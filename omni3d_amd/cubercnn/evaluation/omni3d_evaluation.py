@@ -25,13 +25,18 @@ default.  See `Omni3Deval.bootstrap`.
 A fifth one, for every mode but DIST: `Omni3Deval.errors` / `summarize_errors` = the error decomposition after TIDE: every false positive
 is typed (wrong class, poor box, both, duplicate, background), every unfound ground truth is a miss, and each type is priced by the AP an
 oracle repairing it alone would gain (error_types.py, `kernels.errtypes`, csrc/eval_errors.hip); `errors` switches it on in the two
-drivers, off by default.  See `Omni3Deval.errors`."""
+drivers, off by default.  See `Omni3Deval.errors`.
+
+The reference's `params.useCats = 0` (class-agnostic evaluation: one group per image, K = 1) is built for every mode; its accumulation
+over one long list has a kernel of its own (`kernels.accumulate`, csrc/eval_accumulate_par.hip); `eval_agnostic` adds such a pass per mode
+in the two drivers, off by default, and `proposal_recall` (proposals.py) scores region proposals with it.  See `Omni3Deval`."""
 import copy
 import datetime
 
 import numpy as np
 import torch
 
+from ...kernels import accumulate as kacc
 from ...kernels import iou3d
 from .bootstrap_stats import BOOTSTRAP_CHUNK, _bootstrap_result, _check_confidence, bootstrap_compare, bootstrap_weights  # noqa: F401
 from .error_types import ERROR_TYPES, ORACLES, error_analysis, error_lines  # noqa: F401
@@ -43,6 +48,9 @@ from .pairs import (BEV_UP, _pair_index, _ragged_pairs, _xywh_iou, bev_overlap_g
 # =====================================================================================================================
 # Omni3Deval: evaluate -> accumulate -> summarize on the device (reference :1019-1704)
 # =====================================================================================================================
+MAX_GROUP_GT = 1024                            # ground truths per group `eval_match_kernel` holds (csrc/eval_match.hip EVAL_MAXG)
+
+
 class Omni3DParams:
     """omni3d_evaluation.py:1019-1088; the defaults of each mode are its `set_params` in modes.py"""
 
@@ -94,6 +102,17 @@ class Omni3Deval:
     only match ground truths whose 2D box overlaps its own by more than `params.proximity_thresh`, and a detection with no
     ground truth in proximity is ignored.  True / False like the reference, or a collection of image ids (extension: the
     helper evaluates the union of several datasets of which only some use proximity evaluation).
+
+    `params.useCats = 0` (class-agnostic evaluation, the reference's switch :1147-1153, :1188-1203, :1328-1336, :1368-1374, :1441-1447;
+    every mode): all records of `imgIds` are loaded whatever `catIds` says; there is ONE group per image, its ground truths and its
+    detections gathered category-major in the order of `params.catIds` (not made unique; records of a category that is not in it take
+    no part) and then in record order, the detections stably sorted by descending score and cut to `maxDets[-1]`; matching, ignore
+    rules, ranges and eval_prox apply to those groups unchanged, and K = 1 in every table (`tp_errors`, `precision_l`, ... and
+    `bootstrap()` included).  An image with more than 1024 ground truths raises ValueError before any launch (the matching kernel holds
+    that many per group); `errors()` raises ValueError.  Departure from the reference: its accumulate() overwrites `params.catIds` with
+    [-1], after which its own evaluate() cannot run again; here `params.catIds` stays what the user set and `evalImgs` reports
+    `category_id` -1.  accumulate() then takes `omni_eval_accumulate_par` (csrc/eval_accumulate_par.hip: the one list of all detections
+    cut into blocks over many workgroups, the same bits) from `kernels.accumulate.PAR_MIN_LIST` detections on.
 
     Mode "DIST" (extension, the centre-distance protocol of nuScenes; `up` = None or the up vector of the ground plane).
     Boxes: both sides are the eight `bbox3D` corners in the order of `boxgen.UNIT`, fitted by `cuboid_fit` (default eps_dim, fit_tol);
@@ -158,10 +177,9 @@ class Omni3Deval:
         p.imgIds = list(np.unique(p.imgIds))
         p.catIds = list(np.unique(p.catIds)) if p.useCats else p.catIds
         p.maxDets = sorted(p.maxDets)
-        if not p.useCats:
-            raise NotImplementedError("useCats = 0 is not built on the device path")
-        gts = self.cocoGt.loadAnns(self.cocoGt.getAnnIds(imgIds=p.imgIds, catIds=p.catIds))
-        dts = self.cocoDt.loadAnns(self.cocoDt.getAnnIds(imgIds=p.imgIds, catIds=p.catIds))
+        load = {"catIds": p.catIds} if p.useCats else {}      # useCats = 0: all records of the images, whatever catIds says (:1151-1153)
+        gts = self.cocoGt.loadAnns(self.cocoGt.getAnnIds(imgIds=p.imgIds, **load))
+        dts = self.cocoDt.loadAnns(self.cocoDt.getAnnIds(imgIds=p.imgIds, **load))
         M = self._mode
         flag, key, rng_key = M.ignore_key, M.box_key, M.range_key
         g_by, d_by = {}, {}
@@ -174,9 +192,15 @@ class Omni3Deval:
         maxDet = p.maxDets[-1]
         # group table in (category, image) order = the order evalImgs / accumulate walk (:1346-1351, :1230-1241)
         groups = []
-        for ki, cat in enumerate(p.catIds):
+        for ki, cat in enumerate(p.catIds if p.useCats else [-1]):
             for ii, img in enumerate(p.imgIds):
-                g, d = g_by.get((img, cat), []), d_by.get((img, cat), [])
+                if p.useCats:
+                    g, d = g_by.get((img, cat), []), d_by.get((img, cat), [])
+                else:                                          # one group per image: category-major in catIds order, then record order (:1373-1374)
+                    g = [x for c in p.catIds for x in g_by.get((img, c), [])]
+                    d = [x for c in p.catIds for x in d_by.get((img, c), [])]
+                    if len(g) > MAX_GROUP_GT:
+                        raise ValueError("image %s has %d ground truths; the matching kernel holds %d per group" % (img, len(g), MAX_GROUP_GT))
                 if not g and not d:
                     continue
                 order = np.argsort([-x["score"] for x in d], kind="mergesort")
@@ -228,7 +252,7 @@ class Omni3Deval:
             doff, goff = np.concatenate([[0], np.cumsum(d["dt_sizes"])]), np.concatenate([[0], np.cumsum(d["gt_sizes"])])
             where = {(ki, ii): n for n, (ki, ii, _, _) in enumerate(d["groups"])}
             out = []
-            for ki, cat in enumerate(p.catIds):
+            for ki, cat in enumerate(p.catIds if p.useCats else [-1]):
                 for ai, aRng in enumerate(p.areaRng):
                     for ii, img in enumerate(p.imgIds):
                         n = where.get((ki, ii))
@@ -280,33 +304,45 @@ class Omni3Deval:
                 "has_e": tod(tb["has_e"]), "rec_thrs": tod(np.asarray(p.recThrs, dtype=np.float64)), "max_dets": tod(np.asarray(p.maxDets, dtype=np.int32)),
                 "dt_match": m["dt_match"].contiguous(), "dt_ignore": m["dt_ignore"].contiguous(), "pair_row": tb["pair_row"]}
 
+    @staticmethod
+    def _num_cats(p):
+        return len(p.catIds) if p.useCats else 1
+
     def _check_same_params(self, p, what):
         pe = self._paramsEval
-        if list(p.catIds) != list(pe.catIds) or list(map(tuple, p.areaRng)) != list(map(tuple, pe.areaRng)) or list(p.maxDets) != list(pe.maxDets) \
+        if list(p.catIds) != list(pe.catIds) or bool(p.useCats) != bool(pe.useCats) or list(map(tuple, p.areaRng)) != list(map(tuple, pe.areaRng)) or list(p.maxDets) != list(pe.maxDets) \
                 or list(p.imgIds) != list(pe.imgIds):
             raise NotImplementedError(what + " with parameters other than evaluate()'s is not built on the device path")
 
     # ---- accumulate (:1172-1313) --------------------------------------------------------------------------------------
-    def accumulate(self, p=None):
+    def accumulate(self, p=None, parallel=None, block=None):
+        """parallel / block: which accumulation kernel (`kernels.accumulate.accumulate`); None = `omni_eval_accumulate_par` only under
+        useCats = 0 with at least PAR_MIN_LIST detections, else the one-wave kernel.  Both give the same bits."""
         assert self._dev is not None, "Please run evaluate() first"
         if p is None:
             p = self.params
         pe, d = self._paramsEval, self._dev
         self._check_same_params(p, "accumulate()")
-        T, R, K, A, M = len(p.iouThrs), len(p.recThrs), len(p.catIds), len(p.areaRng), len(p.maxDets)
+        T, R, K, A, M = len(p.iouThrs), len(p.recThrs), self._num_cats(p), len(p.areaRng), len(p.maxDets)
         dev = d["device"]
         sumD = int(d["dt_sizes"].sum())
         tb = self._merge_tables(K, A)
         tod = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)               # noqa: E731
-        prec = torch.full((T, R, K, A, M), -1.0, dtype=torch.float64, device=dev)
-        rec = torch.full((T, K, A, M), -1.0, dtype=torch.float64, device=dev)
-        scr = torch.full((T, R, K, A, M), -1.0, dtype=torch.float64, device=dev)
-        L = iou3d._lib.get()
-        _p = iou3d._lib.ptr
         t = self._device_tables(p, tb, tod)
         t_sc = tod(d["scores"])
-        L.call("omni_eval_accumulate", _p(t["order"]), _p(t["cat_off"]), _p(t["rank"]), _p(t_sc), _p(t["dt_match"]), _p(t["dt_ignore"]), _p(t["npig"]),
-               _p(t["has_e"]), _p(t["rec_thrs"]), _p(t["max_dets"]), K, A, M, T, R, sumD, _p(prec), _p(rec), _p(scr), iou3d._lib.stream_of(prec))
+        if parallel is None:                                   # the one list of all detections, when it is long enough to pay
+            parallel = not p.useCats and sumD >= kacc.PAR_MIN_LIST
+        if not parallel:
+            prec = torch.full((T, R, K, A, M), -1.0, dtype=torch.float64, device=dev)
+            rec = torch.full((T, K, A, M), -1.0, dtype=torch.float64, device=dev)
+            scr = torch.full((T, R, K, A, M), -1.0, dtype=torch.float64, device=dev)
+            L = iou3d._lib.get()
+            _p = iou3d._lib.ptr
+            L.call("omni_eval_accumulate", _p(t["order"]), _p(t["cat_off"]), _p(t["rank"]), _p(t_sc), _p(t["dt_match"]), _p(t["dt_ignore"]), _p(t["npig"]),
+                   _p(t["has_e"]), _p(t["rec_thrs"]), _p(t["max_dets"]), K, A, M, T, R, sumD, _p(prec), _p(rec), _p(scr), iou3d._lib.stream_of(prec))
+        else:
+            prec, rec, scr = kacc.accumulate(t["order"], t["cat_off"], t["rank"], t_sc, t["dt_match"], t["dt_ignore"], t["npig"], t["has_e"],
+                                             t["rec_thrs"], t["max_dets"], parallel=True, block=block)
         self.eval = {"params": p, "counts": [T, R, K, A, M], "date": datetime.datetime.now().strftime("%Y-%m-%d %H:%M:%S"),
                      "precision": prec.cpu().numpy(), "recall": rec.cpu().numpy(), "scores": scr.cpu().numpy()}
         self.eval.update(self._mode.accumulate(self, pe, t, tod))
@@ -350,7 +386,7 @@ class Omni3Deval:
         chunk = BOOTSTRAP_CHUNK if chunk is None else int(chunk)
         if chunk < 1:
             raise ValueError("chunk must be >= 1")
-        T, K, A, M = len(p.iouThrs), len(p.catIds), len(p.areaRng), len(p.maxDets)
+        T, K, A, M = len(p.iouThrs), self._num_cats(p), len(p.areaRng), len(p.maxDets)
         dev, groups, dt_sizes, gt_sizes = d["device"], d["groups"], d["dt_sizes"], d["gt_sizes"]
         tb = self._merge_tables(K, A)
         G = len(groups)
@@ -379,7 +415,7 @@ class Omni3Deval:
 
         Definition.  A replicate is a vector w of len(params.imgIds) non-negative integers; its result is BY DEFINITION what this
         evaluator returns on the data set in which image i is present w[i] times, each copy with copies of its ground truths and
-        detections (w[i] = 0: absent), the copies adjacent in the image order.  evaluate() matches per (image, category), so the match
+        detections (w[i] = 0: absent), the copies adjacent in the image order.  evaluate() matches per (image, category) -- per image under useCats = 0 --, so the match
         tables stay; only accumulate() is redone, for all replicates in one launch (`omni_eval_bootstrap`, csrc/eval_bootstrap.hip): in
         the merge order of accumulate() a detection counts as w consecutive identical entries; npig and "has an evaluated image" are the
         weighted sums over the (image, category) groups; precision at the last copy of a true positive is TP / (FP + TP + eps) on the
@@ -415,7 +451,7 @@ class Omni3Deval:
         """What is the AP lost to?  (Extension, after TIDE: Bolya et al., ECCV 2020; call after evaluate(); modes 2D, 3D, BEV, LET.)
         Every false positive is wrong class, right object but poor box, duplicate or detection on nothing, every unfound ground truth is
         a miss, and each type is priced by the AP gained if an oracle repaired it alone.  Mode DIST raises ValueError: it matches by
-        distance, a background overlap has no meaning there.
+        distance, a background overlap has no meaning there.  So does `params.useCats = 0`: without categories there is no wrong class.
 
         Thresholds.  t_fg must be one of params.iouThrs (np.isclose; ValueError otherwise): the analysis reuses the match tables of
         evaluate() at (area, t_fg, the largest maxDets); 0 < t_bg < t_fg.  Defaults, conventions and not tuned values: 0.5 / 0.1 in 2D
@@ -454,6 +490,8 @@ class Omni3Deval:
         the Loc detections of a category and their attributed ground truths -- whether "poor box" means depth, size or rotation --, NaN
         without one, `loc_errors_mean` (3,) over the categories with a value and `loc_skipped` the pairs left out because a fit failed;
         None in mode 2D.  The result is kept for `summarize_errors()`."""
+        if not self.params.useCats:
+            raise ValueError("errors() under useCats = 0: a 'wrong class' type has no meaning without categories")
         self.error_eval = error_analysis(self, t_fg, t_bg, area)
         return self.error_eval
 
