@@ -527,6 +527,19 @@ int omni_rpn_loss_plain_bwd(const void* const* level_ptrs, const void* const* dl
                             const float* gt, const int* gt_off, const float* g_cls, const float* g_loc, float inv_norm,
                             void* stream);
 
+/* Both of the above with the localisation term MODEL.RPN.BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA name instead of L1 (plain == 0:
+ * IoUness, rpn.py:258-271 -- smooth-L1 with beta, IoU-weighted, every other type is OMNI_ERR_ARG as it is a ValueError there;
+ * plain != 0: 'none', detectron2's _dense_box_regression_loss called at rpn.py:181-195 -- also giou / diou / ciou (fvcore) on
+ * Box2BoxTransform.apply_deltas(deltas, anchor), weights (1,1,1,1), dw / dh bounded by scale_clamp, summed over the positives).
+ * reg_type: 0 smooth_l1, 1 giou, 2 diou, 3 ciou; beta >= 0 (< 1e-5: L1).  Same sums layout, same gradient arguments. */
+int omni_rpn_reg_loss_fwd(const void* const* level_ptrs, const int* level_hw, int nlev, int B, const float* anchors,
+                          const signed char* labels, const int* matched_idx, const float* gt, const int* gt_off, int plain,
+                          int reg_type, float beta, float scale_clamp, double* sums, void* stream);
+int omni_rpn_reg_loss_bwd(const void* const* level_ptrs, const void* const* dlevel_ptrs, const int* level_hw, int nlev,
+                          int B, const float* anchors, const signed char* labels, const int* matched_idx,
+                          const float* gt, const int* gt_off, int plain, int reg_type, float beta, float scale_clamp,
+                          const float* g_cls, const float* g_loc, float inv_norm, void* stream);
+
 /* detectron2 RPN._decode_proposals + Boxes.clip + nonempty filter of find_top_rpn_proposals, applied
  * to the selected per-level top-k anchors only.  slot_level (Ktot), idx (B,Ktot), image_hw (B,2) are
  * device arrays; boxes (B,Ktot,4), valid (B,Ktot) out. */
@@ -625,6 +638,19 @@ int omni_box_loss_fwd(const float* pred, int ldp, int R, int K, const int* cls, 
 int omni_box_loss_bwd(const float* pred, int ldp, int R, int K, const int* cls, const float* prop, const float* gt,
                       const int* gt_row, float wx, float wy, float ww, float wh, const double* sums,
                       const float* g_cls, const float* g_reg, float* dpred, void* stream);
+
+/* The same with the regression term MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA name instead of L1: smooth-L1 with
+ * beta (cubercnn/modeling/roi_heads/fast_rcnn.py:245-252), or giou / diou / ciou (fvcore) of
+ * Box2BoxTransform.apply_deltas(GT-class deltas, proposal) against the ground-truth box, summed over the foreground rows
+ * (detectron2 FastRCNNOutputLayers.box_reg_loss; the reference's own box head stops at fast_rcnn.py:253-254 for these).
+ * reg_type: 0 smooth_l1, 1 giou, 2 diou, 3 ciou; beta >= 0 (< 1e-5: L1); scale_clamp bounds dw / dh (IoU types).  Same sums. */
+int omni_box_reg_loss_fwd(const float* pred, int ldp, int R, int K, const int* cls, const float* prop, const float* gt,
+                          const int* gt_row, float wx, float wy, float ww, float wh, int reg_type, float beta,
+                          float scale_clamp, double* sums, void* stream);
+int omni_box_reg_loss_bwd(const float* pred, int ldp, int R, int K, const int* cls, const float* prop, const float* gt,
+                          const int* gt_row, float wx, float wy, float ww, float wh, int reg_type, float beta,
+                          float scale_clamp, const double* sums, const float* g_cls, const float* g_reg, float* dpred,
+                          void* stream);
 
 /* FastRCNNOutputLayers.predict_boxes_for_gt_classes (detectron2), called at cubercnn/modeling/roi_heads/roi_heads.py:276-289
  * (MODEL.ROI_BOX_HEAD.TRAIN_ON_PRED_BOXES): out (R,4) = Box2BoxTransform.apply_deltas of each row's GT-class deltas

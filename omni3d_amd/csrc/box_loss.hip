@@ -1,5 +1,5 @@
-// box_loss.hip -- Fast R-CNN box-head losses (softmax cross-entropy + per-class L1 box regression),
-// forward statistics and the gradient wrt the fused prediction tensor.
+// box_loss.hip -- Fast R-CNN box-head losses (softmax cross-entropy + per-class box regression: L1, or smooth-L1 with beta / GIoU /
+// DIoU / CIoU from box_reg_loss.h), forward statistics and the gradient wrt the fused prediction tensor.
 //
 // Reference: FastRCNNOutputs.losses / box_reg_loss
 //   /root/reference/cubercnn/modeling/roi_heads/fast_rcnn.py:145-194, 196-260
@@ -14,6 +14,7 @@
 // 7 doubles -- ~6000 serialised atomics for 2048 ROIs -- were 72 us).
 #include <device_rt.h>
 #include "box_decode.h"
+#include "box_reg_loss.h"
 
 namespace {
 
@@ -28,13 +29,15 @@ __device__ __forceinline__ void gt_deltas(const float* pb, const float* gb, floa
 
 // MODE 0: forward sums.  sums: [ce, reg, n_rows, n_fg, n_accurate, n_fg_accurate, n_false_negative]
 // MODE 1: dpred (R, ldp) = g_cls * dCE/n + g_reg * dL1/n   (whole row written, zeros elsewhere)
-template <int MODE>
+// REG 0: the L1 regression of the default configuration (reg_type, beta, scale_clamp unused).  REG 1: the loss reg_type names
+// (MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA), one omni_box_reg_pair per foreground row.
+template <int MODE, int REG>
 __global__ void __launch_bounds__(256) box_loss_kernel(const float* __restrict__ pred, int ldp, int R, int K,
                                                        const int* __restrict__ cls, const float* __restrict__ prop,
                                                        const float* __restrict__ gt, const int* __restrict__ gt_row,
                                                        float wx, float wy, float ww, float wh, double* __restrict__ sums,
                                                        const float* __restrict__ g_cls, const float* __restrict__ g_reg,
-                                                       float* __restrict__ dpred) {
+                                                       float* __restrict__ dpred, int reg_type, float beta, float scale_clamp) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int r = blockIdx.x * 4 + wave; r < R; r += (int)gridDim.x * 4) {
@@ -64,11 +67,17 @@ __global__ void __launch_bounds__(256) box_loss_kernel(const float* __restrict__
                 if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
             }
             float reg = 0.f;
-            if (fg) {
+            if (fg && REG == 0) {
                 float gd[4];
                 gt_deltas(prop + 4 * r, gt + 4 * gt_row[r], wx, wy, ww, wh, gd);
                 const float* dp = row + (K + 1) + 4 * c;
                 reg = fabsf(dp[0] - gd[0]) + fabsf(dp[1] - gd[1]) + fabsf(dp[2] - gd[2]) + fabsf(dp[3] - gd[3]);
+            }
+            if (fg && REG == 1) {
+                float v[4], gd[4];
+                omni_box_reg_pair<false>(reg_type, beta, scale_clamp, row + (K + 1) + 4 * c, prop + 4 * r, gt + 4 * gt_row[r], wx, wy, ww,
+                                         wh, v, gd);
+                reg = v[0] + v[1] + v[2] + v[3];
             }
             acc[0] += (double)ce;
             acc[2] += 1.0;
@@ -85,11 +94,18 @@ __global__ void __launch_bounds__(256) box_loss_kernel(const float* __restrict__
             const float gc = g_cls[0] / n, gr = g_reg[0] / n;
             if (lane <= K) drow[lane] = (e0 / den - (lane == c ? 1.f : 0.f)) * gc;
             if (lane + 64 <= K) drow[lane + 64] = (e1 / den - ((lane + 64) == c ? 1.f : 0.f)) * gc;
-            if (fg && lane < 4) {
+            if (REG == 0 && fg && lane < 4) {
                 float gd[4];
                 gt_deltas(prop + 4 * r, gt + 4 * gt_row[r], wx, wy, ww, wh, gd);
                 const float df = row[(K + 1) + 4 * c + lane] - gd[lane];
                 drow[(K + 1) + 4 * c + lane] = (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * gr;
+            }
+            if (REG == 1 && fg && lane == 0) {                 // the IoU losses couple the four deltas: one lane owns the row's box
+                float v[4], gd[4];
+                omni_box_reg_pair<true>(reg_type, beta, scale_clamp, row + (K + 1) + 4 * c, prop + 4 * r, gt + 4 * gt_row[r], wx, wy, ww,
+                                        wh, v, gd);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) drow[(K + 1) + 4 * c + q] = gd[q] * gr;
             }
         }
     }
@@ -124,30 +140,66 @@ __global__ void __launch_bounds__(256) box_decode_gt_kernel(const float* __restr
 
 }  // namespace
 
+// forward (sums zeroed here; grid-stride, at most BOX_LOSS_FWD_BLOCKS workgroups) and backward (one wave per row) of either REG
+template <int REG>
+static int box_loss_fwd(const float* pred, int ldp, int R, int K, const int* cls, const float* prop, const float* gt, const int* gt_row,
+                        float wx, float wy, float ww, float wh, int reg_type, float beta, float scale_clamp, double* sums, void* stream) {
+    if (R < 0 || K <= 0 || K + 1 > 128 || ldp < 5 * K + 1) return OMNI_ERR_ARG;
+    omni_memset_async(sums, 0, sizeof(double) * 7, (hipStream_t)stream);
+    if (R == 0) return OMNI_OK;
+    const int blocks = (R + 3) / 4 < BOX_LOSS_FWD_BLOCKS ? (R + 3) / 4 : BOX_LOSS_FWD_BLOCKS;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(box_loss_kernel<0, REG>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, ldp,
+                       R, K, cls, prop, gt, gt_row, wx, wy, ww, wh, sums, (const float*)nullptr, (const float*)nullptr,
+                       (float*)nullptr, reg_type, beta, scale_clamp);
+    return omni_launch_status();
+}
+
+template <int REG>
+static int box_loss_bwd(const float* pred, int ldp, int R, int K, const int* cls, const float* prop, const float* gt, const int* gt_row,
+                        float wx, float wy, float ww, float wh, int reg_type, float beta, float scale_clamp, const double* sums,
+                        const float* g_cls, const float* g_reg, float* dpred, void* stream) {
+    if (R < 0 || K <= 0 || K + 1 > 128 || ldp < 5 * K + 1) return OMNI_ERR_ARG;
+    if (R == 0) return OMNI_OK;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(box_loss_kernel<1, REG>), dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, pred, ldp,
+                       R, K, cls, prop, gt, gt_row, wx, wy, ww, wh, const_cast<double*>(sums), g_cls, g_reg, dpred, reg_type, beta,
+                       scale_clamp);
+    return omni_launch_status();
+}
+
+static bool box_reg_args_ok(int reg_type, float beta, float scale_clamp) {
+    return reg_type >= OMNI_BOX_REG_SMOOTH_L1 && reg_type <= OMNI_BOX_REG_CIOU && beta >= 0.f && scale_clamp == scale_clamp;
+}
+
 extern "C" {
 
 // sums: 7 doubles, zeroed here.  loss_cls = sums[0]/max(sums[2],1); loss_box_reg = sums[1]/max(sums[2],1).
 int omni_box_loss_fwd(const float* pred, int ldp, int R, int K, const int* cls, const float* prop, const float* gt,
                       const int* gt_row, float wx, float wy, float ww, float wh, double* sums, void* stream) {
-    if (R < 0 || K <= 0 || K + 1 > 128 || ldp < 5 * K + 1) return OMNI_ERR_ARG;
-    omni_memset_async(sums, 0, sizeof(double) * 7, (hipStream_t)stream);
-    if (R == 0) return OMNI_OK;
-    const int blocks = (R + 3) / 4 < BOX_LOSS_FWD_BLOCKS ? (R + 3) / 4 : BOX_LOSS_FWD_BLOCKS;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(box_loss_kernel<0>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, pred, ldp,
-                       R, K, cls, prop, gt, gt_row, wx, wy, ww, wh, sums, (const float*)nullptr, (const float*)nullptr,
-                       (float*)nullptr);
-    return omni_launch_status();
+    return box_loss_fwd<0>(pred, ldp, R, K, cls, prop, gt, gt_row, wx, wy, ww, wh, 0, 0.f, 0.f, sums, stream);
 }
 
 // dpred (R, ldp) overwritten; sums from the forward call; g_cls / g_reg device scalars.
 int omni_box_loss_bwd(const float* pred, int ldp, int R, int K, const int* cls, const float* prop, const float* gt,
                       const int* gt_row, float wx, float wy, float ww, float wh, const double* sums, const float* g_cls,
                       const float* g_reg, float* dpred, void* stream) {
-    if (R < 0 || K <= 0 || K + 1 > 128 || ldp < 5 * K + 1) return OMNI_ERR_ARG;
-    if (R == 0) return OMNI_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(box_loss_kernel<1>), dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, pred, ldp,
-                       R, K, cls, prop, gt, gt_row, wx, wy, ww, wh, const_cast<double*>(sums), g_cls, g_reg, dpred);
-    return omni_launch_status();
+    return box_loss_bwd<0>(pred, ldp, R, K, cls, prop, gt, gt_row, wx, wy, ww, wh, 0, 0.f, 0.f, sums, g_cls, g_reg, dpred, stream);
+}
+
+// The same two with the regression term reg_type names (OMNI_BOX_REG_*: 0 smooth-L1 with beta, 1 giou, 2 diou, 3 ciou on
+// apply_deltas(deltas, proposal) with dw, dh bounded by scale_clamp); same sums layout, same divisor.
+int omni_box_reg_loss_fwd(const float* pred, int ldp, int R, int K, const int* cls, const float* prop, const float* gt,
+                          const int* gt_row, float wx, float wy, float ww, float wh, int reg_type, float beta, float scale_clamp,
+                          double* sums, void* stream) {
+    if (!box_reg_args_ok(reg_type, beta, scale_clamp)) return OMNI_ERR_ARG;
+    return box_loss_fwd<1>(pred, ldp, R, K, cls, prop, gt, gt_row, wx, wy, ww, wh, reg_type, beta, scale_clamp, sums, stream);
+}
+
+int omni_box_reg_loss_bwd(const float* pred, int ldp, int R, int K, const int* cls, const float* prop, const float* gt,
+                          const int* gt_row, float wx, float wy, float ww, float wh, int reg_type, float beta, float scale_clamp,
+                          const double* sums, const float* g_cls, const float* g_reg, float* dpred, void* stream) {
+    if (!box_reg_args_ok(reg_type, beta, scale_clamp)) return OMNI_ERR_ARG;
+    return box_loss_bwd<1>(pred, ldp, R, K, cls, prop, gt, gt_row, wx, wy, ww, wh, reg_type, beta, scale_clamp, sums, g_cls, g_reg, dpred,
+                           stream);
 }
 
 // out (R, 4): the predicted box of each row's GT class (TRAIN_ON_PRED_BOXES, roi_heads.py:283-289).

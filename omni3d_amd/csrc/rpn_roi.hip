@@ -21,6 +21,7 @@
 #include <device_rt.h>
 #include "philox.h"
 #pragma clang fp contract(off)
+#include "box_reg_loss.h"   // below the pragma: the regression losses are evaluated here as the L1 they stand beside is, uncontracted
 
 namespace {
 
@@ -236,14 +237,17 @@ __device__ __forceinline__ void rpn_zero_pad(float* __restrict__ d, long base, i
         for (int c = RPN_A * 5; c < RPN_C; ++c) d[base + c] = 0.f;
     }
 }
-template <int MODE>
+// REG 0: the L1 regression of the default configuration (beta unused).  REG 1: smooth-L1 with MODEL.RPN.SMOOTH_L1_BETA through
+// omni_box_reg_pair, weights (1,1,1,1).  IoUness evaluates no other type (rpn.py:270-271): reg_type and scale_clamp are only here so
+// that both loss kernels take one argument list.
+template <int MODE, int REG>
 __global__ void __launch_bounds__(256) rpn_loss_kernel(Levels lv, Levels dlv, int B, int A,
                                                        const float* __restrict__ anchors,
                                                        const signed char* __restrict__ labels,
                                                        const int* __restrict__ midx, const float* __restrict__ gt,
                                                        const int* __restrict__ gt_off, double* __restrict__ sums,
                                                        const float* __restrict__ g_cls, const float* __restrict__ g_loc,
-                                                       float inv_norm) {
+                                                       float inv_norm, int reg_type, float beta, float scale_clamp) {
     float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const long tot = (long)B * A;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long)gridDim.x * blockDim.x) {
@@ -264,18 +268,22 @@ __global__ void __launch_bounds__(256) rpn_loss_kernel(Levels lv, Levels dlv, in
             const float sw = ab.z - ab.x, sh = ab.w - ab.y, scx = ab.x + 0.5f * sw, scy = ab.y + 0.5f * sh;
             const float tw = gb.z - gb.x, th = gb.w - gb.y, tcx = gb.x + 0.5f * tw, tcy = gb.y + 0.5f * th;
             const float gd[4] = {(tcx - scx) / sw, (tcy - scy) / sh, logf(tw / sw), logf(th / sh)};
+            float rv[4], rg[4];
+            if (REG == 1)
+                omni_box_reg_pair<MODE == 1>(OMNI_BOX_REG_SMOOTH_L1, beta, 0.f, lv.y[l] + base + RPN_A + k * 4, anchors + 4 * a,
+                                             gt + 4 * (gt_off[n] + midx[i]), 1.f, 1.f, 1.f, 1.f, rv, rg);
             if (MODE == 0) {
                 const float bce = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
                 float l1 = 0.f;
 #pragma unroll
-                for (int d = 0; d < 4; ++d) l1 += fabsf(lv.y[l][base + RPN_A + k * 4 + d] - gd[d]);
+                for (int d = 0; d < 4; ++d) l1 += REG == 1 ? rv[d] : fabsf(lv.y[l][base + RPN_A + k * 4 + d] - gd[d]);
                 s[0] += bce * t; s[1] += l1 * t; s[2] += 1.f; s[4] += sg;
             } else {
                 dcls = (sg - t) * t * inv_norm * g_cls[0];
 #pragma unroll
                 for (int d = 0; d < 4; ++d) {
                     const float df = lv.y[l][base + RPN_A + k * 4 + d] - gd[d];
-                    const float sgn = df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f);
+                    const float sgn = REG == 1 ? rg[d] : (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f));
                     dloc[d] = sgn * t * inv_norm * g_loc[0];
                 }
             }
@@ -296,12 +304,15 @@ __global__ void __launch_bounds__(256) rpn_loss_kernel(Levels lv, Levels dlv, in
 
 // MODEL.RPN.OBJECTNESS_UNCERTAINTY 'none' (rpn.py:181-195, detectron2's RPN losses): objectness = BCE-with-logits against the 0 / 1
 // anchor labels over every sampled anchor, localisation = L1 on the foreground deltas without the IoU weight.  Same sums layout.
-template <int MODE>
+// REG 1: the loss reg_type names (MODEL.RPN.BBOX_REG_LOSS_TYPE: smooth-L1 with beta, giou, diou, ciou -- detectron2's
+// _dense_box_regression_loss), unweighted.
+template <int MODE, int REG>
 __global__ void __launch_bounds__(256) rpn_loss_plain_kernel(Levels lv, Levels dlv, int B, int A, const float* __restrict__ anchors,
                                                              const signed char* __restrict__ labels, const int* __restrict__ midx,
                                                              const float* __restrict__ gt, const int* __restrict__ gt_off,
                                                              double* __restrict__ sums, const float* __restrict__ g_cls,
-                                                             const float* __restrict__ g_loc, float inv_norm) {
+                                                             const float* __restrict__ g_loc, float inv_norm, int reg_type,
+                                                             float beta, float scale_clamp) {
     float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const long tot = (long)B * A;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long)gridDim.x * blockDim.x) {
@@ -324,11 +335,15 @@ __global__ void __launch_bounds__(256) rpn_loss_plain_kernel(Levels lv, Levels d
             const float sw = ab.z - ab.x, sh = ab.w - ab.y, scx = ab.x + 0.5f * sw, scy = ab.y + 0.5f * sh;
             const float tw = gb.z - gb.x, th = gb.w - gb.y, tcx = gb.x + 0.5f * tw, tcy = gb.y + 0.5f * th;
             const float gd[4] = {(tcx - scx) / sw, (tcy - scy) / sh, logf(tw / sw), logf(th / sh)};
+            float rv[4], rg[4];
+            if (REG == 1)
+                omni_box_reg_pair<MODE == 1>(reg_type, beta, scale_clamp, lv.y[l] + base + RPN_A + k * 4, anchors + 4 * a,
+                                             gt + 4 * (gt_off[n] + midx[i]), 1.f, 1.f, 1.f, 1.f, rv, rg);
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 const float df = lv.y[l][base + RPN_A + k * 4 + d] - gd[d];
-                if (MODE == 0) s[1] += fabsf(df);
-                else dloc[d] = (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * inv_norm * g_loc[0];
+                if (MODE == 0) s[1] += REG == 1 ? rv[d] : fabsf(df);
+                else dloc[d] = (REG == 1 ? rg[d] : (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f))) * inv_norm * g_loc[0];
             }
             if (MODE == 0) { s[2] += 1.f; s[4] += sg; }
         } else if (MODE == 0) {
@@ -574,6 +589,49 @@ static inline long rpn_loss_blocks(long tot) {
     return b < RPN_LOSS_MAX_BLOCKS ? b : RPN_LOSS_MAX_BLOCKS;
 }
 
+// The launches behind omni_rpn_loss_* (REG 0), omni_rpn_loss_plain_* (PLAIN, REG 0) and omni_rpn_reg_loss_* (REG 1).
+// Forward: sums (6 doubles) zeroed here, grid-stride with at most RPN_LOSS_MAX_BLOCKS workgroups.
+template <bool PLAIN, int REG>
+static int rpn_loss_fwd(const void* const* level_ptrs, const int* level_hw, int nlev, int B, const float* anchors,
+                        const signed char* labels, const int* matched_idx, const float* gt, const int* gt_off, int reg_type,
+                        float beta, float scale_clamp, double* sums, void* stream) {
+    if (nlev <= 0 || nlev > MAXL) return OMNI_ERR_ARG;
+    Levels lv = make_levels(level_ptrs, level_hw, nlev);
+    const int A = lv.a_off[nlev];
+    hipStream_t st = (hipStream_t)stream;
+    omni_memset_async(sums, 0, sizeof(double) * 6, st);
+    const long tot = (long)B * A;
+    if (tot == 0) return OMNI_OK;
+    const auto kernel = PLAIN ? rpn_loss_plain_kernel<0, REG> : rpn_loss_kernel<0, REG>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)rpn_loss_blocks(tot)), dim3(256), 0, st, lv, lv, B, A, anchors, labels, matched_idx, gt,
+                       gt_off, sums, (const float*)nullptr, (const float*)nullptr, 0.f, reg_type, beta, scale_clamp);
+    return omni_launch_status();
+}
+
+// Backward: one thread per anchor; together they write every element of the level tensors.
+template <bool PLAIN, int REG>
+static int rpn_loss_bwd(const void* const* level_ptrs, const void* const* dlevel_ptrs, const int* level_hw, int nlev, int B,
+                        const float* anchors, const signed char* labels, const int* matched_idx, const float* gt, const int* gt_off,
+                        int reg_type, float beta, float scale_clamp, const float* g_cls, const float* g_loc, float inv_norm,
+                        void* stream) {
+    if (nlev <= 0 || nlev > MAXL) return OMNI_ERR_ARG;
+    Levels lv = make_levels(level_ptrs, level_hw, nlev);
+    Levels dlv = make_levels(dlevel_ptrs, level_hw, nlev);
+    const int A = lv.a_off[nlev];
+    const long tot = (long)B * A;
+    if (tot == 0) return OMNI_OK;
+    const auto kernel = PLAIN ? rpn_loss_plain_kernel<1, REG> : rpn_loss_kernel<1, REG>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, lv, dlv, B, A, anchors, labels,
+                       matched_idx, gt, gt_off, (double*)nullptr, g_cls, g_loc, inv_norm, reg_type, beta, scale_clamp);
+    return omni_launch_status();
+}
+
+// IoUness evaluates smooth-L1 only (rpn.py:270-271 raises for every other type)
+static bool rpn_reg_args_ok(int plain, int reg_type, float beta, float scale_clamp) {
+    return reg_type >= OMNI_BOX_REG_SMOOTH_L1 && reg_type <= (plain ? OMNI_BOX_REG_CIOU : OMNI_BOX_REG_SMOOTH_L1) && beta >= 0.f &&
+           scale_clamp == scale_clamp;
+}
+
 extern "C" {
 
 // mode 0: IoU (detectron2 pairwise_iou), mode 1: IoA = inter / area(boxes2).  out (N, M).
@@ -640,17 +698,7 @@ int omni_rpn_gather_logits(const void* const* level_ptrs, const int* level_hw, i
 int omni_rpn_loss_fwd(const void* const* level_ptrs, const int* level_hw, int nlev, int B, const float* anchors,
                       const signed char* labels, const int* matched_idx, const float* gt, const int* gt_off, double* sums,
                       void* stream) {
-    if (nlev <= 0 || nlev > MAXL) return OMNI_ERR_ARG;
-    Levels lv = make_levels(level_ptrs, level_hw, nlev);
-    const int A = lv.a_off[nlev];
-    hipStream_t st = (hipStream_t)stream;
-    omni_memset_async(sums, 0, sizeof(double) * 6, st);
-    const long tot = (long)B * A;
-    if (tot == 0) return OMNI_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(rpn_loss_kernel<0>), dim3((unsigned)rpn_loss_blocks(tot)), dim3(256), 0, st, lv, lv,
-                       B, A, anchors, labels, matched_idx, gt, gt_off, sums, (const float*)nullptr, (const float*)nullptr,
-                       0.f);
-    return omni_launch_status();
+    return rpn_loss_fwd<false, 0>(level_ptrs, level_hw, nlev, B, anchors, labels, matched_idx, gt, gt_off, 0, 0.f, 0.f, sums, stream);
 }
 
 // grads of (g_cls * cls_sum + g_loc * loc_sum) * inv_norm wrt the level tensors, written into
@@ -658,47 +706,45 @@ int omni_rpn_loss_fwd(const void* const* level_ptrs, const int* level_hw, int nl
 int omni_rpn_loss_bwd(const void* const* level_ptrs, const void* const* dlevel_ptrs, const int* level_hw, int nlev, int B,
                       const float* anchors, const signed char* labels, const int* matched_idx, const float* gt,
                       const int* gt_off, const float* g_cls, const float* g_loc, float inv_norm, void* stream) {
-    if (nlev <= 0 || nlev > MAXL) return OMNI_ERR_ARG;
-    Levels lv = make_levels(level_ptrs, level_hw, nlev);
-    Levels dlv = make_levels(dlevel_ptrs, level_hw, nlev);
-    const int A = lv.a_off[nlev];
-    hipStream_t st = (hipStream_t)stream;
-    const long tot = (long)B * A;                   // one thread per anchor; together they write every element of the level tensors
-    if (tot == 0) return OMNI_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(rpn_loss_kernel<1>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, lv, dlv,
-                       B, A, anchors, labels, matched_idx, gt, gt_off, (double*)nullptr, g_cls, g_loc, inv_norm);
-    return omni_launch_status();
+    return rpn_loss_bwd<false, 0>(level_ptrs, dlevel_ptrs, level_hw, nlev, B, anchors, labels, matched_idx, gt, gt_off, 0, 0.f, 0.f, g_cls,
+                                  g_loc, inv_norm, stream);
 }
 
 // The same two entry points for MODEL.RPN.OBJECTNESS_UNCERTAINTY 'none' (plain 0 / 1 objectness targets, unweighted L1).
 int omni_rpn_loss_plain_fwd(const void* const* level_ptrs, const int* level_hw, int nlev, int B, const float* anchors,
                             const signed char* labels, const int* matched_idx, const float* gt, const int* gt_off, double* sums,
                             void* stream) {
-    if (nlev <= 0 || nlev > MAXL) return OMNI_ERR_ARG;
-    Levels lv = make_levels(level_ptrs, level_hw, nlev);
-    const int A = lv.a_off[nlev];
-    hipStream_t st = (hipStream_t)stream;
-    omni_memset_async(sums, 0, sizeof(double) * 6, st);
-    const long tot = (long)B * A;
-    if (tot == 0) return OMNI_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(rpn_loss_plain_kernel<0>), dim3((unsigned)rpn_loss_blocks(tot)), dim3(256), 0, st, lv, lv,
-                       B, A, anchors, labels, matched_idx, gt, gt_off, sums, (const float*)nullptr, (const float*)nullptr, 0.f);
-    return omni_launch_status();
+    return rpn_loss_fwd<true, 0>(level_ptrs, level_hw, nlev, B, anchors, labels, matched_idx, gt, gt_off, 0, 0.f, 0.f, sums, stream);
 }
 
 int omni_rpn_loss_plain_bwd(const void* const* level_ptrs, const void* const* dlevel_ptrs, const int* level_hw, int nlev, int B,
                             const float* anchors, const signed char* labels, const int* matched_idx, const float* gt,
                             const int* gt_off, const float* g_cls, const float* g_loc, float inv_norm, void* stream) {
-    if (nlev <= 0 || nlev > MAXL) return OMNI_ERR_ARG;
-    Levels lv = make_levels(level_ptrs, level_hw, nlev);
-    Levels dlv = make_levels(dlevel_ptrs, level_hw, nlev);
-    const int A = lv.a_off[nlev];
-    hipStream_t st = (hipStream_t)stream;
-    const long tot = (long)B * A;                   // one thread per anchor; together they write every element of the level tensors
-    if (tot == 0) return OMNI_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(rpn_loss_plain_kernel<1>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, lv, dlv,
-                       B, A, anchors, labels, matched_idx, gt, gt_off, (double*)nullptr, g_cls, g_loc, inv_norm);
-    return omni_launch_status();
+    return rpn_loss_bwd<true, 0>(level_ptrs, dlevel_ptrs, level_hw, nlev, B, anchors, labels, matched_idx, gt, gt_off, 0, 0.f, 0.f, g_cls,
+                                 g_loc, inv_norm, stream);
+}
+
+// Either objectness mode (plain != 0: 'none') with the regression term reg_type names (OMNI_BOX_REG_*: 0 smooth-L1 with beta; with
+// plain also 1 giou, 2 diou, 3 ciou on apply_deltas(deltas, anchor), dw / dh bounded by scale_clamp); same sums layout.
+int omni_rpn_reg_loss_fwd(const void* const* level_ptrs, const int* level_hw, int nlev, int B, const float* anchors,
+                          const signed char* labels, const int* matched_idx, const float* gt, const int* gt_off, int plain,
+                          int reg_type, float beta, float scale_clamp, double* sums, void* stream) {
+    if (!rpn_reg_args_ok(plain, reg_type, beta, scale_clamp)) return OMNI_ERR_ARG;
+    return plain ? rpn_loss_fwd<true, 1>(level_ptrs, level_hw, nlev, B, anchors, labels, matched_idx, gt, gt_off, reg_type, beta,
+                                         scale_clamp, sums, stream)
+                 : rpn_loss_fwd<false, 1>(level_ptrs, level_hw, nlev, B, anchors, labels, matched_idx, gt, gt_off, reg_type, beta,
+                                          scale_clamp, sums, stream);
+}
+
+int omni_rpn_reg_loss_bwd(const void* const* level_ptrs, const void* const* dlevel_ptrs, const int* level_hw, int nlev, int B,
+                          const float* anchors, const signed char* labels, const int* matched_idx, const float* gt,
+                          const int* gt_off, int plain, int reg_type, float beta, float scale_clamp, const float* g_cls,
+                          const float* g_loc, float inv_norm, void* stream) {
+    if (!rpn_reg_args_ok(plain, reg_type, beta, scale_clamp)) return OMNI_ERR_ARG;
+    return plain ? rpn_loss_bwd<true, 1>(level_ptrs, dlevel_ptrs, level_hw, nlev, B, anchors, labels, matched_idx, gt, gt_off, reg_type,
+                                         beta, scale_clamp, g_cls, g_loc, inv_norm, stream)
+                 : rpn_loss_bwd<false, 1>(level_ptrs, dlevel_ptrs, level_hw, nlev, B, anchors, labels, matched_idx, gt, gt_off, reg_type,
+                                          beta, scale_clamp, g_cls, g_loc, inv_norm, stream);
 }
 
 // masked (n) = keep ? scores : -inf

@@ -88,13 +88,16 @@ class RPNWithIgnore(nn.Module):
         self.loss_weight = loss_weight if isinstance(loss_weight, dict) else {"loss_rpn_cls": loss_weight, "loss_rpn_loc": loss_weight}
         self.ignore_thresh = ignore_thresh
         self.objectness_uncertainty = objectness_uncertainty
-        if box_reg_loss_type != "smooth_l1" or smooth_l1_beta != 0.0:
-            raise NotImplementedError("MI355X hot path: L1 anchor regression (BBOX_REG_LOSS_TYPE smooth_l1, SMOOTH_L1_BETA 0: Base.yaml / "
-                                      "upstream defaults); the reference's IoUness losses only evaluate smooth_l1 as well (rpn.py:258-271)")
         if objectness_uncertainty.lower() not in ("iouness", "none"):
             # rpn.py:169-180 sends every other value down the same IoUness code path; only the two names that occur are accepted here
             raise NotImplementedError(f"MODEL.RPN.OBJECTNESS_UNCERTAINTY '{objectness_uncertainty}': 'IoUness' (Base.yaml:55) and 'none'")
         self.plain_objectness = objectness_uncertainty.lower() == "none"
+        # the IoUness losses only evaluate smooth_l1 (rpn.py:258-271); detectron2's _dense_box_regression_loss also the IoU losses
+        if box_reg_loss_type not in (("smooth_l1", "giou", "diou", "ciou") if self.plain_objectness else ("smooth_l1",)):
+            raise ValueError(f"Invalid dense box regression loss type '{box_reg_loss_type}'")
+        if smooth_l1_beta < 0.0:
+            raise ValueError(f"MODEL.RPN.SMOOTH_L1_BETA {smooth_l1_beta}: must be >= 0")
+        self.box_reg_loss_type, self.smooth_l1_beta = box_reg_loss_type, float(smooth_l1_beta)
         self.pending_logs = {}
         self.injected = None   # parity tests: dict with 'E' (B,A) exponential variates
         self.last = None
@@ -143,7 +146,8 @@ class RPNWithIgnore(nn.Module):
         inv_norm = 1.0 / (self.batch_size_per_image * B)          # rpn.py:198
         names = ("rpn/cls", "rpn/loc")
         w = tuple(self.loss_weight.get(k, 1.0) for k in names)                     # rpn.py:203 (names never match => 1.0)
-        vec, sums = HF.rpn_loss(levels, anchors, labels, matched_idx, targets.gt, targets.gt_off, inv_norm, w, self.plain_objectness)
+        vec, sums = HF.rpn_loss(levels, anchors, labels, matched_idx, targets.gt, targets.gt_off, inv_norm, w, self.plain_objectness,
+                                self.box_reg_loss_type, self.smooth_l1_beta)
         self.pending_logs = {"rpn": (sums, B)}
         return HF.LossDict({names[0]: vec[0], names[1]: vec[1]}, vectors=[(vec, names)])
 

@@ -18,8 +18,15 @@ class FastRCNNOutputs(nn.Module):
         super().__init__()
         if isinstance(input_shape, int):
             input_shape = ShapeSpec(channels=input_shape)
-        if cls_agnostic_bbox_reg or box_reg_loss_type != "smooth_l1" or smooth_l1_beta != 0.0:
-            raise NotImplementedError("MI355X hot path: class-specific L1 box regression (reference defaults)")
+        if cls_agnostic_bbox_reg:
+            raise NotImplementedError("MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG True: the fused prediction tensor holds class-specific deltas")
+        if box_reg_loss_type not in ("smooth_l1", "giou", "diou", "ciou"):
+            raise ValueError(f"Invalid bbox reg loss type '{box_reg_loss_type}'")        # fast_rcnn.py:253-254
+        if smooth_l1_beta < 0.0:
+            raise ValueError(f"MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA {smooth_l1_beta}: must be >= 0")
+        # giou / diou / ciou: an extension over the reference, whose box head only evaluates smooth_l1 (fast_rcnn.py:245-254); they
+        # follow detectron2's FastRCNNOutputLayers.box_reg_loss (sum over the foreground rows / number of rows)
+        self.box_reg_loss_type, self.smooth_l1_beta = box_reg_loss_type, float(smooth_l1_beta)
         self.num_classes = num_classes
         input_size = input_shape.channels * (input_shape.width or 1) * (input_shape.height or 1)
         self.cls_score = Linear(input_size, num_classes + 1)
@@ -61,7 +68,8 @@ class FastRCNNOutputs(nn.Module):
         """fast_rcnn.py:145-194; cls (R) int32 with -2 on padding rows."""
         names = ("BoxHead/loss_cls", "BoxHead/loss_box_reg")
         w = tuple(self.loss_weight.get(k, 1.0) for k in names)
-        vec, sums = HF.box_loss(pred, self.num_classes, cls, prop_boxes, targets.gt, gt_row, self.box2box_weights, w)
+        vec, sums = HF.box_loss(pred, self.num_classes, cls, prop_boxes, targets.gt, gt_row, self.box2box_weights, w,
+                                self.box_reg_loss_type, self.smooth_l1_beta)
         self.pending_logs = {"fast_rcnn": sums}
         return HF.LossDict({names[0]: vec[0], names[1]: vec[1]}, vectors=[(vec, names)])
 

@@ -1174,16 +1174,16 @@ class _RPNLoss(Function):
     """-> ((2,) = [sum BCE*t, sum L1*t] * inv_norm * loss weights, raw sums); level tensors are the fused head outputs (B,16,H,W) CL."""
 
     @staticmethod
-    def forward(ctx, anchors, labels, matched_idx, gt, gt_off, inv_norm, weights, plain, *levels):
+    def forward(ctx, anchors, labels, matched_idx, gt, gt_off, inv_norm, weights, plain, reg, *levels):
         ctx.set_materialize_grads(False)      # no zero tensors for the non-differentiable side outputs
         lv = [_cl(t).permute(0, 2, 3, 1) for t in levels]
         pack = det.LevelPack(lv)
-        sums = det.rpn_loss_fwd(pack, anchors, labels, matched_idx, gt, gt_off, plain)
+        sums = det.rpn_loss_fwd(pack, anchors, labels, matched_idx, gt, gt_off, plain, *reg)
         # (fp64 sums x fp64 coefficients, rounded once into the fp32 loss vector: one launch)
         vec = glue.scale_vec(sums, (inv_norm * weights[0], inv_norm * weights[1]), n=2)
         ctx.pack = pack
         ctx.save_for_backward(anchors, labels, matched_idx, gt, gt_off)
-        ctx.inv_norm, ctx.weights, ctx.plain = inv_norm, weights, plain
+        ctx.inv_norm, ctx.weights, ctx.plain, ctx.reg = inv_norm, weights, plain, reg
         ctx.mark_non_differentiable(sums)
         return vec, sums
 
@@ -1193,25 +1193,27 @@ class _RPNLoss(Function):
         if ctx.weights != (1.0, 1.0):
             g = g.float() * _coef(ctx.weights, g.device)
         g_cls, g_loc = _scalar_grads(g, 2)
-        grads = det.rpn_loss_bwd(ctx.pack, anchors, labels, matched_idx, gt, gt_off, g_cls, g_loc, ctx.inv_norm, ctx.plain)
-        return (None,) * 8 + tuple(t.permute(0, 3, 1, 2) for t in grads)
+        grads = det.rpn_loss_bwd(ctx.pack, anchors, labels, matched_idx, gt, gt_off, g_cls, g_loc, ctx.inv_norm, ctx.plain, *ctx.reg)
+        return (None,) * 9 + tuple(t.permute(0, 3, 1, 2) for t in grads)
 
 
-def rpn_loss(levels, anchors, labels, matched_idx, gt, gt_off, inv_norm, weights=(1.0, 1.0), plain=False):
-    """plain: OBJECTNESS_UNCERTAINTY 'none' instead of 'IoUness' -> ((2,) [cls, loc] weighted losses, raw sums)"""
-    return _RPNLoss.apply(anchors, labels, matched_idx, gt, gt_off, inv_norm, tuple(float(w) for w in weights), bool(plain), *levels)
+def rpn_loss(levels, anchors, labels, matched_idx, gt, gt_off, inv_norm, weights=(1.0, 1.0), plain=False, reg_type="smooth_l1", beta=0.0):
+    """plain: OBJECTNESS_UNCERTAINTY 'none' instead of 'IoUness'; reg_type, beta: MODEL.RPN.BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA (the
+    defaults are the L1 kernels) -> ((2,) [cls, loc] weighted losses, raw sums)"""
+    return _RPNLoss.apply(anchors, labels, matched_idx, gt, gt_off, inv_norm, tuple(float(w) for w in weights), bool(plain),
+                          (reg_type, float(beta)), *levels)
 
 
 class _BoxLoss(Function):
     """-> ((2,) = [loss_cls, loss_box_reg] * loss weights, raw sums)"""
 
     @staticmethod
-    def forward(ctx, pred, K, cls, prop, gt, gt_row, weights, loss_w):
+    def forward(ctx, pred, K, cls, prop, gt, gt_row, weights, loss_w, reg):
         ctx.set_materialize_grads(False)      # no zero tensors for the non-differentiable side outputs
         pred = pred.contiguous()
-        sums = det.box_loss_fwd(pred, K, cls, prop, gt, gt_row, weights)
+        sums = det.box_loss_fwd(pred, K, cls, prop, gt, gt_row, weights, *reg)
         ctx.save_for_backward(pred, cls, prop, gt, gt_row, sums)
-        ctx.meta = (K, weights, loss_w)
+        ctx.meta = (K, weights, loss_w, reg)
         ctx.mark_non_differentiable(sums)
         # (fp64 sums / max(fp64 count, 1) x loss weights, rounded once into the fp32 loss vector: one launch, round 6)
         vec = glue.scale_vec(sums, loss_w, denom=sums[2:3], denom_min=1.0, n=2)
@@ -1220,16 +1222,17 @@ class _BoxLoss(Function):
     @staticmethod
     def backward(ctx, g, _):
         pred, cls, prop, gt, gt_row, sums = ctx.saved_tensors
-        K, weights, loss_w = ctx.meta
+        K, weights, loss_w, reg = ctx.meta
         if loss_w != (1.0, 1.0):
             g = g.float() * _coef(loss_w, g.device)
         g_cls, g_reg = _scalar_grads(g, 2)
-        return (det.box_loss_bwd(pred, K, cls, prop, gt, gt_row, sums, g_cls, g_reg, weights),) + (None,) * 7
+        return (det.box_loss_bwd(pred, K, cls, prop, gt, gt_row, sums, g_cls, g_reg, weights, *reg),) + (None,) * 8
 
 
-def box_loss(pred, K, cls, prop, gt, gt_row, weights=(10.0, 10.0, 5.0, 5.0), loss_w=(1.0, 1.0)):
-    """-> ((2,) [loss_cls, loss_box_reg] weighted, raw sums)"""
-    return _BoxLoss.apply(pred, K, cls, prop, gt, gt_row, tuple(weights), tuple(float(w) for w in loss_w))
+def box_loss(pred, K, cls, prop, gt, gt_row, weights=(10.0, 10.0, 5.0, 5.0), loss_w=(1.0, 1.0), reg_type="smooth_l1", beta=0.0):
+    """reg_type, beta: MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA (the defaults are the L1 kernels)
+    -> ((2,) [loss_cls, loss_box_reg] weighted, raw sums)"""
+    return _BoxLoss.apply(pred, K, cls, prop, gt, gt_row, tuple(weights), tuple(float(w) for w in loss_w), (reg_type, float(beta)))
 
 
 class _CubeLoss(Function):

@@ -155,23 +155,48 @@ def rpn_gather_logits(pack):
     return out
 
 
-def rpn_loss_fwd(pack, anchors, labels, matched_idx, gt, gt_off, plain=False):
-    """plain: MODEL.RPN.OBJECTNESS_UNCERTAINTY 'none' (0 / 1 objectness targets, unweighted L1) instead of 'IoUness'"""
+BOX_REG_TYPES = {"smooth_l1": 0, "giou": 1, "diou": 2, "ciou": 3}     # OMNI_BOX_REG_* (csrc/box_reg_loss.h)
+SCALE_CLAMP = math.log(1000.0 / 16)                                  # Box2BoxTransform's bound on dw, dh
+
+
+def box_reg_args(reg_type, beta, scale_clamp):
+    """None for the default (smooth_l1, beta 0: the L1 entry points), else the (type, beta, clamp) arguments of the omni_*_reg_loss entries"""
+    if reg_type not in BOX_REG_TYPES:
+        raise ValueError(f"Invalid bbox reg loss type '{reg_type}'")
+    if reg_type == "smooth_l1" and beta == 0.0:
+        return None
+    return (BOX_REG_TYPES[reg_type], float(beta), float(scale_clamp))
+
+
+def rpn_loss_fwd(pack, anchors, labels, matched_idx, gt, gt_off, plain=False, reg_type="smooth_l1", beta=0.0, scale_clamp=SCALE_CLAMP):
+    """plain: MODEL.RPN.OBJECTNESS_UNCERTAINTY 'none' (0 / 1 objectness targets, unweighted L1) instead of 'IoUness';
+    reg_type, beta: MODEL.RPN.BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA ('giou', 'diou', 'ciou' with plain only)"""
     L = _dev(anchors, labels, matched_idx, gt, gt_off)
     sums = _empty((6,), torch.float64, anchors)
-    L.call("omni_rpn_loss_plain_fwd" if plain else "omni_rpn_loss_fwd", *pack.args(), pack.B, _lib.ptr(anchors), _lib.ptr(labels), _lib.ptr(matched_idx),
-           _lib.ptr(gt), _lib.ptr(gt_off), _lib.ptr(sums), _lib.stream_of(anchors))
+    reg = box_reg_args(reg_type, beta, scale_clamp)
+    if reg is None:
+        L.call("omni_rpn_loss_plain_fwd" if plain else "omni_rpn_loss_fwd", *pack.args(), pack.B, _lib.ptr(anchors), _lib.ptr(labels), _lib.ptr(matched_idx),
+               _lib.ptr(gt), _lib.ptr(gt_off), _lib.ptr(sums), _lib.stream_of(anchors))
+    else:
+        L.call("omni_rpn_reg_loss_fwd", *pack.args(), pack.B, _lib.ptr(anchors), _lib.ptr(labels), _lib.ptr(matched_idx), _lib.ptr(gt),
+               _lib.ptr(gt_off), int(bool(plain)), *reg, _lib.ptr(sums), _lib.stream_of(anchors))
     return sums
 
 
-def rpn_loss_bwd(pack, anchors, labels, matched_idx, gt, gt_off, g_cls, g_loc, inv_norm, plain=False):
+def rpn_loss_bwd(pack, anchors, labels, matched_idx, gt, gt_off, g_cls, g_loc, inv_norm, plain=False, reg_type="smooth_l1", beta=0.0,
+                 scale_clamp=SCALE_CLAMP):
     L = _dev(anchors, labels, matched_idx, gt, gt_off, g_cls, g_loc)
     grads = [torch.empty_like(t) for t in pack.tensors]
     dp = _ptrs(grads)
     a = pack.args()
-    L.call("omni_rpn_loss_plain_bwd" if plain else "omni_rpn_loss_bwd", a[0], _cast(dp), a[1], a[2], pack.B, _lib.ptr(anchors), _lib.ptr(labels),
-           _lib.ptr(matched_idx), _lib.ptr(gt), _lib.ptr(gt_off), _lib.ptr(g_cls), _lib.ptr(g_loc), float(inv_norm),
-           _lib.stream_of(anchors))
+    reg = box_reg_args(reg_type, beta, scale_clamp)
+    if reg is None:
+        L.call("omni_rpn_loss_plain_bwd" if plain else "omni_rpn_loss_bwd", a[0], _cast(dp), a[1], a[2], pack.B, _lib.ptr(anchors), _lib.ptr(labels),
+               _lib.ptr(matched_idx), _lib.ptr(gt), _lib.ptr(gt_off), _lib.ptr(g_cls), _lib.ptr(g_loc), float(inv_norm),
+               _lib.stream_of(anchors))
+    else:
+        L.call("omni_rpn_reg_loss_bwd", a[0], _cast(dp), a[1], a[2], pack.B, _lib.ptr(anchors), _lib.ptr(labels), _lib.ptr(matched_idx),
+               _lib.ptr(gt), _lib.ptr(gt_off), int(bool(plain)), *reg, _lib.ptr(g_cls), _lib.ptr(g_loc), float(inv_norm), _lib.stream_of(anchors))
     return grads
 
 
@@ -346,21 +371,25 @@ def roi_align_bwd(dfeats_nhwc, scales, rois, batch_idx, levels, P, dout, dout2=N
            int(per_image), int(first), _lib.stream_of(rois))
 
 
-def box_loss_fwd(pred, K, cls, prop, gt, gt_row, weights=(10.0, 10.0, 5.0, 5.0)):
+def box_loss_fwd(pred, K, cls, prop, gt, gt_row, weights=(10.0, 10.0, 5.0, 5.0), reg_type="smooth_l1", beta=0.0, scale_clamp=SCALE_CLAMP):
+    """reg_type, beta: MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA"""
     L = _dev(pred, cls, prop, gt, gt_row)
     R, ldp = pred.shape
     sums = _empty((7,), torch.float64, pred)
-    L.call("omni_box_loss_fwd", _lib.ptr(pred), ldp, R, K, _lib.ptr(cls), _lib.ptr(prop), _lib.ptr(gt), _lib.ptr(gt_row),
-           *[float(w) for w in weights], _lib.ptr(sums), _lib.stream_of(pred))
+    reg = box_reg_args(reg_type, beta, scale_clamp)
+    L.call("omni_box_loss_fwd" if reg is None else "omni_box_reg_loss_fwd", _lib.ptr(pred), ldp, R, K, _lib.ptr(cls), _lib.ptr(prop), _lib.ptr(gt),
+           _lib.ptr(gt_row), *[float(w) for w in weights], *(reg or ()), _lib.ptr(sums), _lib.stream_of(pred))
     return sums
 
 
-def box_loss_bwd(pred, K, cls, prop, gt, gt_row, sums, g_cls, g_reg, weights=(10.0, 10.0, 5.0, 5.0)):
+def box_loss_bwd(pred, K, cls, prop, gt, gt_row, sums, g_cls, g_reg, weights=(10.0, 10.0, 5.0, 5.0), reg_type="smooth_l1", beta=0.0,
+                 scale_clamp=SCALE_CLAMP):
     L = _dev(pred, cls, prop, gt, gt_row, sums, g_cls, g_reg)
     R, ldp = pred.shape
     dpred = torch.empty_like(pred)
-    L.call("omni_box_loss_bwd", _lib.ptr(pred), ldp, R, K, _lib.ptr(cls), _lib.ptr(prop), _lib.ptr(gt), _lib.ptr(gt_row),
-           *[float(w) for w in weights], _lib.ptr(sums), _lib.ptr(g_cls), _lib.ptr(g_reg), _lib.ptr(dpred),
+    reg = box_reg_args(reg_type, beta, scale_clamp)
+    L.call("omni_box_loss_bwd" if reg is None else "omni_box_reg_loss_bwd", _lib.ptr(pred), ldp, R, K, _lib.ptr(cls), _lib.ptr(prop), _lib.ptr(gt),
+           _lib.ptr(gt_row), *[float(w) for w in weights], *(reg or ()), _lib.ptr(sums), _lib.ptr(g_cls), _lib.ptr(g_reg), _lib.ptr(dpred),
            _lib.stream_of(pred))
     return dpred
 
