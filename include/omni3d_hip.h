@@ -1113,6 +1113,54 @@ int omni_box_annotate(const float* box3d, const float* R, const int* box_off, co
 int omni_visibility_ragged(const float* box3d, const float* R, const int* box_off, const float* K, const int* size,
                            const int* tile_off, int I, int N, int tiles, float zplane, int* area, int* visible, void* stream);
 
+/* The KITTI object benchmark's protocol (csrc/eval_kitti.hip), for `cubercnn.evaluation.kitti.KittiEval`: AP|R40 and AP|R11 per
+ * (class, difficulty, metric, overlap set).  The reference has no counterpart; the protocol is the project's reading of the devkit's
+ * evaluate_object, stated in float64 by tests/exact_kitti.py.  A slot is s = ((c * Dn + d) * M + m) * O + o, S = C * Dn * M * O.
+ * Rows are ragged by IMAGE: the detections of image i are rows dt_off[i] .. dt_off[i + 1] - 1 IN DESCENDING SCORE ORDER (stable), its
+ * ground-truth rows gt_off[i] .. gt_off[i + 1] - 1 in input order, its DontCare regions dc_off[i] .. dc_off[i + 1] - 1 (all (I + 1)
+ * int32 from 0, non-decreasing; not checked here).  sim (M, P) float32: for metric m, image i's (G_i, D_i) row-major matrix -- the
+ * detections run fastest -- at sim[m * P + sim_off[i]] (sim_off (I) int64); dc_ov: image i's (R_i, D_i) matrix of (intersection /
+ * area of the detection's 2D box) at dc_pair_off[i].  Per row: dt_code / gt_code int32 class codes, dt_height / gt_height /
+ * gt_trunc / dt_score doubles, gt_occ int32.  Tables, all in device memory: cls_tab (C, ncodes) int32 = 0 where the code is class c
+ * itself, 1 where it is a neighbour class of c, 2 where it is class c set aside by the caller (ground truths only: a detection of
+ * class c has a code with 0), anything else (and every code outside [0, ncodes)) for the rest; diffs (Dn, 3)
+ * doubles (min height, max occlusion, max truncation); min_ov (O, C) doubles, ALL >= 0 (the caller's to keep: pass 2 orders overlaps
+ * by their bit patterns); dc_metric (M) int32, non-zero where DontCare regions absorb false positives.
+ *   ground-truth flag: 0 (counted) the class itself with occ <= max occlusion, trunc <= max truncation, height >= min height; 1
+ *   (neutral) the class itself otherwise -- set aside or not --, and every neighbour; -1 the rest, a row set aside that those three
+ *   bounds would count included.  detection flag: -1 another class, 1 height < min height,
+ *   else 0.  An overlap qualifies when (double)sim > min_ov, strictly.
+ * omni_kitti_match_tp -- pass 1, one 64-lane wave per (image, slot): every ground truth with flag >= 0, in order, takes the unassigned
+ *   detection of its class with a qualifying overlap and the largest score (the earliest among equal scores).  tp_score (S, sumG) =
+ *   that score when both flags are 0, -inf otherwise (every element is written); n_gt (S), ZEROED BY THE CALLER, += the flag-0 rows.
+ * omni_kitti_thresholds -- one workgroup per slot: with v = the finite entries of the slot's tp_score in descending order, i runs over
+ *   them with l = (i + 1) / n_gt, r = (i + 2) / n_gt (l for the last), and v[i] is emitted unless it is not the last and r - cur <
+ *   cur - l; cur starts at 0 and grows by 1 / (npts - 1) per emission; at most npts are emitted.  thresholds (S, npts) = the emitted
+ *   scores, bit for bit, 0 beyond K (S) = their number.  No host round trip: pass 2 reads K on the device.
+ * omni_kitti_match_counts -- pass 2, one wave per (image, slot, k), idle for k >= K[s]: detections scoring below thresholds[s][k] do
+ *   not exist.  Every ground truth with flag >= 0, in order, takes the unassigned flag-0 detection with the largest qualifying overlap
+ *   (the earliest among equals), or without one the earliest qualifying flag-1 detection.  Nothing taken and flag 0: fn; taken and both
+ *   flags 0: tp.  fp = the unassigned flag-0 detections, less -- where dc_metric[m] -- those with dc_ov > min_ov on any region.
+ *   counts (S, npts, 3) int32 (tp, fp, fn), ZEROED BY THE CALLER, integer atomics only: two runs give the same bits.
+ * omni_kitti_finalize -- precision (S, npts) = tp / (tp + fp) and recall = tp / (tp + fn) for k < K (0 for an empty denominator and
+ *   for k >= K), precision replaced by its running maximum from the right; ap (S, 2) = 100 x the mean of precision[1 .. npts - 1]
+ *   (R40 for npts = 41) and 100 x the mean of precision[0, 4, 8, ...] (R11), summed in ascending k, all in double.
+ * OMNI_ERR_ARG before any launch: a negative size, max_dt or max_gt (the caller's largest per-image counts) above 1024, npts outside
+ * [2, 64], I x S (omni_kitti_match_tp) or I x S x npts (omni_kitti_match_counts) >= 2^26: one workgroup per problem.  I == 0 or S == 0
+ * launches nothing and returns OMNI_OK. */
+int omni_kitti_match_tp(const float* sim, long long P, const long long* sim_off, const int* dt_off, const int* gt_off, const int* dt_code,
+                        const double* dt_height, const double* dt_score, const int* gt_code, const double* gt_height, const int* gt_occ,
+                        const double* gt_trunc, const int* cls_tab, int ncodes, const double* diffs, const double* min_ov, int I, int C,
+                        int Dn, int M, int O, int sumD, int sumG, int max_dt, int max_gt, double* tp_score, int* n_gt, void* stream);
+int omni_kitti_thresholds(const double* tp_score, const int* n_gt, int S, int sumG, int npts, double* thresholds, int* K, void* stream);
+int omni_kitti_match_counts(const float* sim, long long P, const long long* sim_off, const int* dt_off, const int* gt_off, const int* dt_code,
+                            const double* dt_height, const double* dt_score, const int* gt_code, const double* gt_height, const int* gt_occ,
+                            const double* gt_trunc, const int* cls_tab, int ncodes, const double* diffs, const double* min_ov,
+                            const float* dc_ov, const long long* dc_pair_off, const int* dc_off, const int* dc_metric,
+                            const double* thresholds, const int* K, int npts, int I, int C, int Dn, int M, int O, int sumD, int sumG,
+                            int max_dt, int max_gt, int* counts, void* stream);
+int omni_kitti_finalize(const int* counts, const int* K, int S, int npts, double* precision, double* recall, double* ap, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,41 @@ def bev_eval_args(cfg):
     return {"eval_bev": bool(node.ENABLED), "bev_up": up}
 
 
+_EVAL_KITTI = {"ENABLED": False, "OCC_CUTS": [0.75, 0.5, 0.25], "DC_METRICS": ["2D", "BEV", "3D"], "R11": False}
+
+
+def add_kitti_eval_config(cfg):
+    """TEST.EVAL_KITTI.*: the KITTI object benchmark's own protocol next to AP2D / AP3D (`cubercnn.evaluation.kitti.KittiEval`,
+    csrc/eval_kitti.hip): AP|R40 of the 2D box, the bird's-eye view and the 3D box at Easy / Moderate / Hard for car, pedestrian and
+    cyclist.  The reference has no such pass and `get_cfg_defaults` stays key for key what the reference defines, so, as with
+    `add_bev_eval_config`, the node is absent until this call; without it nothing is evaluated this way.  Idempotent: values already
+    set are kept.
+    OCC_CUTS: the visibility cuts that make the occlusion level (a convention of this project, see `KittiParams`); DC_METRICS: the
+    metrics in which DontCare regions absorb false positives; R11: also report the 11-point AP."""
+    if "EVAL_KITTI" not in cfg.TEST:
+        cfg.TEST.EVAL_KITTI = CN()
+    for key, value in _EVAL_KITTI.items():
+        cfg.TEST.EVAL_KITTI.setdefault(key, list(value) if isinstance(value, list) else value)
+    return cfg
+
+
+def kitti_eval_args(cfg):
+    """TEST.EVAL_KITTI -> the keyword arguments of `Omni3DEvaluationHelper` / `Omni3DEvaluator`:
+    `Omni3DEvaluationHelper(names, filter_settings, folder, **kitti_eval_args(cfg))`.  A cfg without the node: the feature off."""
+    node = cfg.TEST.get("EVAL_KITTI")
+    if node is None:
+        node = _EVAL_KITTI
+        get = node.__getitem__
+    else:
+        get = lambda k: getattr(node, k)      # noqa: E731
+    cuts, dc = tuple(float(v) for v in get("OCC_CUTS")), tuple(str(v) for v in get("DC_METRICS"))
+    if any(m not in ("2D", "BEV", "3D") for m in dc):
+        raise ValueError("TEST.EVAL_KITTI.DC_METRICS must be taken from 2D, BEV, 3D")
+    if list(cuts) != sorted(cuts, reverse=True):
+        raise ValueError("TEST.EVAL_KITTI.OCC_CUTS must descend")
+    return {"eval_kitti": bool(get("ENABLED")), "kitti_params": {"occCuts": cuts, "dcMetrics": dc}, "kitti_r11": bool(get("R11"))}
+
+
 _EVAL_DIST = {"ENABLED": False, "UP": [], "DIST_THRS": [0.5, 1.0, 2.0, 4.0], "TP_DIST": 2.0, "MIN_RECALL": 0.1}
 
 

@@ -15,6 +15,31 @@ from .omni3d_evaluation import AnnotationIndex, Omni3Deval
 from .pairs import BEV_UP
 
 
+def _kitti_options(eval_kitti, kitti_params, kitti_r11):
+    """the checked `eval_kitti` options of the drivers: None when the switch is off, else (dict of `KittiParams` attributes, r11)"""
+    if not eval_kitti:
+        return None
+    from .kitti import KittiParams
+    params = dict(kitti_params or {})
+    unknown = set(params) - set(vars(KittiParams()))
+    if unknown:
+        raise ValueError("kitti_params: unknown keys %s" % sorted(unknown))
+    return params, bool(kitti_r11)
+
+
+def _kitti_pass(gt, dt, options, only_2d, names=None, img_ids=None):
+    """the KITTI-protocol pass of the drivers (`cubercnn.evaluation.kitti.KittiEval`) -> (rows {'AP3D|R40-car-moderate': ...}, the table's text, the KittiEval)"""
+    from .kitti import KittiEval
+    params, r11 = options
+    ev = KittiEval(gt, dt, names=names, img_ids=img_ids)
+    for key, value in params.items():
+        setattr(ev.params, key, value)
+    if only_2d:
+        ev.params.metrics = ("2D",)
+    ev.evaluate()
+    return ev.results(r11=r11), ev.summarize(r11=r11, verbose=False), ev
+
+
 def instances_to_coco_json(instances, img_id):
     """omni3d_evaluation.py:970-1013.  The reference converts each field with its own `.tolist()` after a per-field device
     copy and averages the corner depths one box at a time in numpy; here one host copy per field and a vectorised depth."""
@@ -128,14 +153,21 @@ class Omni3DEvaluator:
     eval_agnostic (the reference evaluator's `useCats = 0`, off by default): every evaluated mode gets a second pass with
     `params.useCats = 0` after its ordinary one -- one group per image, the categories ignored -- which adds 'bbox_<mode>_agnostic' =
     the mode's seven headline APs under their usual names plus 'AR1', 'AR10', 'AR100', and 'log_str_<mode>_agnostic' (short form:
-    'agnostic_<mode>'); nothing else changes."""
+    'agnostic_<mode>'); nothing else changes.
+
+    eval_kitti (extension, off by default; `kitti_params` = optional dict of `KittiParams` attributes such as `occCuts` / `dcMetrics`,
+    `kitti_r11` adds the 11-point rows): after the modes, one pass of the KITTI object benchmark's own protocol
+    (`cubercnn.evaluation.kitti.KittiEval`; with only_2d its 2D metric alone) adds 'bbox_KITTI' = {'AP3D|R40-car-moderate': ..., ...} and
+    'log_str_KITTI' = the devkit-style table (short form: 'KITTI' and 'kitti_eval' under 'bbox'; the short form's records need
+    `category_name`, or `kitti_names` = category id -> name); nothing else changes."""
 
     def __init__(self, dataset_name, tasks=None, distributed=True, output_dir=None, *, max_dets_per_image=None, use_fast_impl=False,
                  eval_prox=False, only_2d=False, filter_settings=None, img_ids=None, cat_ids=None, eval_bev=False, bev_up=BEV_UP,
                  eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None, errors=None,
-                 eval_agnostic=False):
+                 eval_agnostic=False, eval_kitti=False, kitti_params=None, kitti_r11=False, kitti_names=None):
         self._only_2d, self._eval_prox, self._output_dir, self._distributed = only_2d, eval_prox, output_dir, distributed
         self._eval_agnostic = bool(eval_agnostic)
+        self._kitti, self._kitti_names = _kitti_options(eval_kitti, kitti_params, kitti_r11), kitti_names
         self._bootstrap, self._errors = _bootstrap_params(bootstrap), _error_params(errors)
         self._opts = check_options(let_params=let_params, bev_up=bev_up, dist_up=dist_up, dist_params=dist_params)
         self._switches = {"eval_bev": bool(eval_bev), "eval_dist": bool(eval_dist), "eval_let": bool(eval_let)}
@@ -193,6 +225,9 @@ class Omni3DEvaluator:
             if self._eval_agnostic:
                 res["agnostic_" + mode] = _agnostic_pass(self._make_eval(AnnotationIndex(copy.deepcopy(self._gt), self._img_ids, self._cat_ids),
                                                                          AnnotationIndex(copy.deepcopy(self._predictions), self._img_ids, self._cat_ids), mode))[0]
+        if self._kitti is not None:
+            res["KITTI"], _, res["kitti_eval"] = _kitti_pass(AnnotationIndex(copy.deepcopy(self._gt), self._img_ids, self._cat_ids),
+                                                             copy.deepcopy(self._predictions), self._kitti, self._only_2d, self._kitti_names)
         return {"bbox": res}
 
     def evaluate(self, img_ids=None):
@@ -255,6 +290,9 @@ class Omni3DEvaluator:
                 if img_ids is not None:
                     ev.params.imgIds = img_ids
                 self._results["bbox_" + mode + "_agnostic"], self._results["log_str_" + mode + "_agnostic"] = _agnostic_pass(ev)
+        if self._kitti is not None:
+            self._results["bbox_KITTI"], self._results["log_str_KITTI"], _ = _kitti_pass(self._omni_api, copy.deepcopy(kept), self._kitti,
+                                                                                         self._only_2d, self._kitti_names, img_ids)
         return copy.deepcopy({k: v for k, v in self._results.items() if not k.endswith("_merge")}) | \
             {k: v for k, v in self._results.items() if k.endswith("_merge")}
 
@@ -278,11 +316,15 @@ class Omni3DEvaluationHelper:
 
     eval_agnostic (off by default; the switch `Omni3DEvaluator` takes): every split's result gets 'bbox_<mode>_agnostic' and
     'log_str_<mode>_agnostic', `results_agnostic[name]` = {'iters', '<mode>': {the seven headline APs, 'AR1', 'AR10', 'AR100'}, ...}
-    per split and for <Concat>, and one log line per split.  The printed tables do not change."""
+    per split and for <Concat>, and one log line per split.  The printed tables do not change.
+
+    eval_kitti (off by default; `kitti_params`, `kitti_r11` as `Omni3DEvaluator` takes them): every split's result gets 'bbox_KITTI' and
+    'log_str_KITTI', `results_kitti[name]` = {'iters', 'AP3D|R40-car-moderate': ..., ...} per split, and the table is logged.  There is
+    no <Concat> row: the protocol belongs to one benchmark's split.  The printed tables do not change."""
 
     def __init__(self, dataset_names, filter_settings, output_folder, iter_label="-", only_2d=False, eval_bev=False, bev_up=BEV_UP,
                  eval_dist=False, dist_up=None, dist_params=None, eval_let=False, let_params=None, bootstrap=None, errors=None,
-                 eval_agnostic=False):
+                 eval_agnostic=False, eval_kitti=False, kitti_params=None, kitti_r11=False):
         from collections import OrderedDict
         from ...d2.data import MetadataCatalog
         from ..data.datasets import simple_register
@@ -304,6 +346,9 @@ class Omni3DEvaluationHelper:
         self.errors, self.results_errors = _error_params(errors), OrderedDict()
         # the reference evaluator's useCats = 0 (off by default): class-agnostic AP / AR of every mode per split and for <Concat>
         self.eval_agnostic, self.results_agnostic = bool(eval_agnostic), OrderedDict()
+        # extension (off by default): the KITTI object benchmark's own protocol per split, in `results_kitti`
+        self.eval_kitti, self.kitti_params, self.kitti_r11, self.results_kitti = bool(eval_kitti), kitti_params, bool(kitti_r11), OrderedDict()
+        _kitti_options(eval_kitti, kitti_params, kitti_r11)
         self.overall_imgIds, self.overall_catIds = set(), set()
         self.output_folders = {n: os.path.join(output_folder, n) for n in self.dataset_names}
         for name in self.dataset_names:
@@ -312,7 +357,8 @@ class Omni3DEvaluationHelper:
             ev = Omni3DEvaluator(name, output_dir=self.output_folders[name], filter_settings=filter_settings, only_2d=only_2d,
                                  eval_prox=("Objectron" in name or "SUNRGBD" in name), distributed=False, eval_bev=self.eval_bev,
                                  eval_dist=self.eval_dist, eval_let=self.eval_let, bootstrap=self.bootstrap, errors=self.errors,
-                                 **({"eval_agnostic": True} if self.eval_agnostic else {}), **self._opts)
+                                 **({"eval_agnostic": True} if self.eval_agnostic else {}),
+                                 **({"eval_kitti": True, "kitti_params": kitti_params, "kitti_r11": kitti_r11} if self.eval_kitti else {}), **self._opts)
             ev.reset()
             self.evaluators[name] = ev
             self.overall_imgIds.update(ev._omni_api.getImgIds())
@@ -384,6 +430,9 @@ class Omni3DEvaluationHelper:
                                                                                  if "bbox_" + mode + "_agnostic" in res}}
             log.info("{} iter={} class-agnostic AP / AR100: {}".format(dataset_name, self.iter_label, {
                 mode: (round(row["AP"], 2), round(row["AR100"], 2)) for mode, row in self.results_agnostic[dataset_name].items() if mode != "iters"}))
+        if self.eval_kitti and "bbox_KITTI" in res:
+            self.results_kitti[dataset_name] = {"iters": self.iter_label, **res["bbox_KITTI"]}
+            log.info("{} iter={} KITTI protocol\n{}".format(dataset_name, self.iter_label, res["log_str_KITTI"]))
         logperf.print_ap_category_histogram(dataset_name, self._per_category(r2, r3))
 
     def _per_category(self, r2, r3):

@@ -1,0 +1,36 @@
+"""The KITTI object benchmark's protocol on an Omni3D annotation file and a result file:
+
+    python tools/kitti_eval.py datasets/Omni3D/KITTI_val.json output/inference/KITTI_val/omni_instances_results.json [--r11] [--loose]
+
+prints AP|R40 of the 2D box, the bird's-eye view and the 3D box at Easy / Moderate / Hard for car, pedestrian and cyclist
+(`cubercnn.evaluation.kitti.KittiEval`; the protocol is this project's reading of the devkit).  --r11 adds the 11-point
+AP, --loose the table at the loose min-overlaps (0.5 / 0.25 / 0.25).  The result file holds the records of
+`omni_instances_results.json`, with the category ids of the annotation file."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("gt", help="Omni3D annotation file (JSON)")
+    ap.add_argument("dt", help="detections: the records of omni_instances_results.json")
+    ap.add_argument("--r11", action="store_true", help="also print the 11-point AP")
+    ap.add_argument("--loose", action="store_true", help="also print the table at the loose min-overlaps")
+    ap.add_argument("--modal-2d-boxes", action="store_true", help="use KITTI's own 2D boxes (bbox2D_tight) where present, as DATASETS.MODAL_2D_BOXES")
+    args = ap.parse_args(argv)
+    from omni3d_amd.cubercnn.data.datasets import Omni3D, get_filter_settings_from_cfg
+    from omni3d_amd.cubercnn.evaluation.kitti import KittiEval
+    fs = get_filter_settings_from_cfg(None)
+    fs["ignore_names"] = ["dontcare", "ignore", "void"]
+    fs["modal_2D_boxes"] = bool(args.modal_2d_boxes)
+    ev = KittiEval(Omni3D([args.gt], filter_settings=fs), args.dt)
+    ev.evaluate()
+    ev.summarize(r11=args.r11, overlaps=None if args.loose else (list(ev.params.minOverlaps)[0],))
+    return ev
+
+
+if __name__ == "__main__":
+    main()
