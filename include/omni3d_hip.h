@@ -1161,6 +1161,35 @@ int omni_kitti_match_counts(const float* sim, long long P, const long long* sim_
                             int max_dt, int max_gt, int* counts, void* stream);
 int omni_kitti_finalize(const int* counts, const int* K, int S, int npts, double* precision, double* recall, double* ap, void* stream);
 
+/* AOS, the benchmark's average orientation similarity (csrc/eval_kitti.hip; the project's reading of the devkit's compute_aos path,
+ * written from memory; float64 statement: tests/exact_kitti_aos.py).
+ * omni_kitti_match_counts_aos -- omni_kitti_match_counts (counts: the same bits) and, for every true positive (the condition under
+ *   which tp is incremented) of a slot whose metric has aos_metric[m] != 0, q = (1 + cos(gt_alpha[row] - dt_alpha[detection])) / 2 in
+ *   double, 0 when either alpha is not finite (NaN: no heading).  sim_sum (S, npts) 64-bit integers, ZEROED BY THE CALLER, +=
+ *   llrint(q * 2^40): fixed point, integer atomics (one per wave), so two runs give the same bits.  dt_alpha (sumD), gt_alpha (sumG)
+ *   float64, aos_metric (M) int32.  OMNI_ERR_ARG also for sumG >= 2^23, the bound under which the sum cannot overflow.
+ * omni_kitti_finalize_aos -- aos (S, npts) = sim_sum * 2^-40 / (tp + fp) for k < K (0 for an empty denominator and for k >= K),
+ *   replaced by its running maximum from the right over k < K; aos_ap (S, 2) = 100 x the mean of aos[1 .. npts - 1] and of
+ *   aos[0, 4, 8, ...], in the order of omni_kitti_finalize.  A slot of a metric with aos_metric[m] == 0: NaN in both. */
+int omni_kitti_match_counts_aos(const float* sim, long long P, const long long* sim_off, const int* dt_off, const int* gt_off, const int* dt_code,
+                                const double* dt_height, const double* dt_score, const int* gt_code, const double* gt_height, const int* gt_occ,
+                                const double* gt_trunc, const int* cls_tab, int ncodes, const double* diffs, const double* min_ov,
+                                const float* dc_ov, const long long* dc_pair_off, const int* dc_off, const int* dc_metric,
+                                const double* thresholds, const int* K, int npts, int I, int C, int Dn, int M, int O, int sumD, int sumG,
+                                int max_dt, int max_gt, const double* dt_alpha, const double* gt_alpha, const int* aos_metric, int* counts,
+                                long long* sim_sum, void* stream);
+int omni_kitti_finalize_aos(const int* counts, const long long* sim_sum, const int* K, const int* aos_metric, int S, int M, int O, int npts,
+                            double* aos, double* aos_ap, void* stream);
+
+/* Cuboid corners -> the KITTI object benchmark's box parameters (csrc/kitti_params.hip), one thread per box, double arithmetic on the
+ * float32 corners.  corners (n, 8, 3) in the corner order of omni_cuboid_corners: l = |v1 - v0|, h = |v3 - v0|, w = |v4 - v0|, c = the
+ * mean of the eight corners.  u = up normalised, a = camera x less its part along u, normalised, b = u x a (up (0, -1, 0): a = x,
+ * b = z).  out (n, 9) float64: h, w, l, (x, y, z) = c - (h / 2) u (the centre of the bottom face), rotation_y = atan2(-e.b, e.a) with
+ * e = v1 - v0 (0 for a heading without a ground-plane component), alpha = rotation_y - atan2(c.a, c.b) wrapped into (-pi, pi], valid.
+ * valid = 1 when all 24 inputs are finite and l, h, w > 0; otherwise 0 and the other eight are NaN.  OMNI_ERR_ARG: n < 0, an up vector
+ * of zero or non-finite length or parallel to camera x. */
+int omni_kitti_box_params(const float* corners, int n, double up_x, double up_y, double up_z, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,11 @@
 //   omni_kitti_thresholds    one workgroup per slot: the scores at the ranks the recall sampling emits (radix selection)
 //   omni_kitti_match_counts  one 64-lane wave per (image, slot, threshold k < K[slot]): pass 2 with the DontCare step
 //   omni_kitti_finalize      precision / recall / AP per slot
+// AOS (average orientation similarity, the devkit's compute_aos path as this project reads it, written from memory like the rest;
+// float64 statement: tests/exact_kitti_aos.py) is one more template parameter on pass 2 and on the finalize:
+//   omni_kitti_match_counts_aos  pass 2, and per true positive q = (1 + cos(gt_alpha - dt_alpha)) / 2 summed in fixed point
+//   omni_kitti_finalize_aos      aos = sim_sum 2^-40 / (tp + fp), made monotone and averaged like precision
+// The <false> instantiations are the kernels behind the plain entry points, unchanged.
 // As in eval_match.hip the sequential side (here the ground truths) is walked by the wave, the parallel side (the detections,
 // at most 1024 = 16 per lane) is spread over the lanes and reduced with shuffles; the overlaps are compared with the
 // min-overlap as doubles.  "Assigned" is one bit per detection in a register of the lane that owns it: no LDS in the matching.
@@ -49,6 +54,17 @@ struct KittiP {
     const int* K;              // (S)
     int* counts;               // (S, npts, 3) tp, fp, fn
 };
+
+// pass 2 with AOS: the headings (NaN: none) and the table of fixed-point sums
+struct KittiAosP : KittiP {
+    const double* dt_alpha;    // (sumD) observation angle, NaN: no heading
+    const double* gt_alpha;    // (sumG)
+    const int* aos_metric;     // (M): the metrics whose slots accumulate
+    unsigned long long* sim_sum;   // (S, npts): sum of llrint(q 2^40) over the true positives
+};
+template <bool AOS> struct KittiArg { typedef KittiP type; };
+template <> struct KittiArg<true> { typedef KittiAosP type; };
+constexpr double KITTI_AOS_ONE = 1099511627776.0;      // 2^40
 
 struct Slot { int c, d, m, o; double mo, hmin, omax, tmax; };
 
@@ -141,7 +157,8 @@ __global__ void __launch_bounds__(64) kitti_match_tp_kernel(KittiP p) {
     if (lane == 0 && ngt > 0) atomicAdd(p.n_gt + s, ngt);
 }
 
-__global__ void __launch_bounds__(64) kitti_match_counts_kernel(KittiP p) {
+template <bool AOS>
+__global__ void __launch_bounds__(64) kitti_match_counts_kernel(typename KittiArg<AOS>::type p) {
     const int lane = threadIdx.x;
     const int S = p.C * p.Dn * p.M * p.O;
     int b = blockIdx.x;
@@ -156,6 +173,9 @@ __global__ void __launch_bounds__(64) kitti_match_counts_kernel(KittiP p) {
     unsigned cls, small, assigned = 0u;
     kitti_dt_masks(p, q, d0, D, lane, thr, cls, small);
     int tp = 0, fn = 0;
+    unsigned long long sim_q = 0ull;                    // AOS: lane 0's fixed-point sum of q over this wave's true positives
+    bool aos_on = false;
+    if constexpr (AOS) aos_on = p.aos_metric[q.m] != 0;
     for (int g = 0; g < G; ++g) {
         const int gf = kitti_gt_flag(p, q, g0 + g);
         if (gf < 0) continue;
@@ -185,6 +205,14 @@ __global__ void __launch_bounds__(64) kitti_match_counts_kernel(KittiP p) {
         const int bi = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
         if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
         tp += (gf == 0 && (key >> 32) != 0ull);
+        if constexpr (AOS) {
+            if (aos_on && lane == 0 && gf == 0 && (key >> 32) != 0ull) {
+                const double ga = p.gt_alpha[g0 + g], da = p.dt_alpha[d0 + bi];
+                // no heading on either side contributes 0
+                const double qq = (isfinite(ga) && isfinite(da)) ? 0.5 * (1.0 + cos(ga - da)) : 0.0;
+                sim_q += (unsigned long long)llrint(qq * KITTI_AOS_ONE);
+            }
+        }
     }
     // false positives: the usable detections of full height nobody took, less those a DontCare region covers
     unsigned open = cls & ~small & ~assigned;
@@ -205,6 +233,9 @@ __global__ void __launch_bounds__(64) kitti_match_counts_kernel(KittiP p) {
         if (tp) atomicAdd(c, tp);
         if (fp) atomicAdd(c + 1, fp);
         if (fn) atomicAdd(c + 2, fn);
+        if constexpr (AOS) {
+            if (sim_q) atomicAdd(p.sim_sum + ((long long)s * p.npts + k), sim_q);
+        }
     }
 }
 
@@ -280,23 +311,36 @@ __global__ void __launch_bounds__(KITTI_THR_BLOCK) kitti_thresholds_kernel(const
     }
 }
 
+// AOS: `precision` is the table of orientation similarities, `recall` is not written, and the last four arguments are in use
+template <bool AOS>
 __global__ void __launch_bounds__(64) kitti_finalize_kernel(const int* __restrict__ counts, const int* __restrict__ K, int S, int npts,
-                                                            double* __restrict__ precision, double* __restrict__ recall, double* __restrict__ ap) {
+                                                            double* __restrict__ precision, double* __restrict__ recall, double* __restrict__ ap,
+                                                            const unsigned long long* __restrict__ sim_sum, const int* __restrict__ aos_metric,
+                                                            int M, int O) {
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= S) return;
     const int nk = K[s];
     double* pr = precision + (long long)s * npts;
     double* rc = recall + (long long)s * npts;
+    if constexpr (AOS) {
+        if (!aos_metric[(s / O) % M]) {                 // a slot of a metric without AOS
+            const double nan = __builtin_nan("");
+            for (int k = 0; k < npts; ++k) pr[k] = nan;
+            ap[2 * s] = ap[2 * s + 1] = nan;
+            return;
+        }
+    }
     for (int k = 0; k < npts; ++k) {
         double a = 0.0, b = 0.0;
         if (k < nk) {
             const int* c = counts + ((long long)s * npts + k) * 3;
             const double tp = (double)c[0], fp = (double)c[1], fn = (double)c[2];
-            a = tp + fp > 0.0 ? tp / (tp + fp) : 0.0;
+            if constexpr (AOS) a = tp + fp > 0.0 ? (double)sim_sum[(long long)s * npts + k] * (1.0 / KITTI_AOS_ONE) / (tp + fp) : 0.0;
+            else a = tp + fp > 0.0 ? tp / (tp + fp) : 0.0;
             b = tp + fn > 0.0 ? tp / (tp + fn) : 0.0;
         }
         pr[k] = a;
-        rc[k] = b;
+        if constexpr (!AOS) rc[k] = b;
     }
     double run = 0.0;
     for (int k = nk - 1; k >= 0; --k) {             // right-to-left running maximum over the thresholds in use
@@ -365,15 +409,48 @@ int omni_kitti_match_counts(const float* sim, long long P, const long long* sim_
     p.diffs = diffs; p.min_ov = min_ov; p.I = I; p.C = C; p.Dn = Dn; p.M = M; p.O = O; p.ncodes = ncodes; p.sumD = sumD; p.sumG = sumG;
     p.npts = npts; p.dc_ov = dc_ov; p.dc_pair_off = dc_pair_off; p.dc_off = dc_off; p.dc_metric = dc_metric; p.thresholds = thresholds;
     p.K = K; p.counts = counts;
-    hipLaunchKernelGGL(kitti_match_counts_kernel, dim3((unsigned)((long long)I * S * npts)), dim3(64), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(kitti_match_counts_kernel<false>, dim3((unsigned)((long long)I * S * npts)), dim3(64), 0, (hipStream_t)stream, p);
+    return omni_launch_status();
+}
+
+int omni_kitti_match_counts_aos(const float* sim, long long P, const long long* sim_off, const int* dt_off, const int* gt_off, const int* dt_code,
+                                const double* dt_height, const double* dt_score, const int* gt_code, const double* gt_height, const int* gt_occ,
+                                const double* gt_trunc, const int* cls_tab, int ncodes, const double* diffs, const double* min_ov,
+                                const float* dc_ov, const long long* dc_pair_off, const int* dc_off, const int* dc_metric,
+                                const double* thresholds, const int* K, int npts, int I, int C, int Dn, int M, int O, int sumD, int sumG,
+                                int max_dt, int max_gt, const double* dt_alpha, const double* gt_alpha, const int* aos_metric, int* counts,
+                                long long* sim_sum, void* stream) {
+    const int rc = kitti_check(I, C, Dn, M, O, ncodes, sumD, sumG, max_dt, max_gt, npts, npts);
+    // sumG < 2^23 true positives of at most 2^40 each: the 64-bit sum cannot overflow
+    if (rc != OMNI_OK || P < 0 || sumG >= (1 << 23)) return OMNI_ERR_ARG;
+    const int S = C * Dn * M * O;
+    if (I == 0 || S == 0) return OMNI_OK;
+    KittiAosP p{};
+    p.sim = sim; p.P = P; p.sim_off = sim_off; p.dt_off = dt_off; p.gt_off = gt_off; p.dt_code = dt_code; p.dt_height = dt_height;
+    p.dt_score = dt_score; p.gt_code = gt_code; p.gt_height = gt_height; p.gt_occ = gt_occ; p.gt_trunc = gt_trunc; p.cls_tab = cls_tab;
+    p.diffs = diffs; p.min_ov = min_ov; p.I = I; p.C = C; p.Dn = Dn; p.M = M; p.O = O; p.ncodes = ncodes; p.sumD = sumD; p.sumG = sumG;
+    p.npts = npts; p.dc_ov = dc_ov; p.dc_pair_off = dc_pair_off; p.dc_off = dc_off; p.dc_metric = dc_metric; p.thresholds = thresholds;
+    p.K = K; p.counts = counts;
+    p.dt_alpha = dt_alpha; p.gt_alpha = gt_alpha; p.aos_metric = aos_metric; p.sim_sum = (unsigned long long*)sim_sum;
+    hipLaunchKernelGGL(kitti_match_counts_kernel<true>, dim3((unsigned)((long long)I * S * npts)), dim3(64), 0, (hipStream_t)stream, p);
     return omni_launch_status();
 }
 
 int omni_kitti_finalize(const int* counts, const int* K, int S, int npts, double* precision, double* recall, double* ap, void* stream) {
     if (S < 0 || npts < 2 || npts > KITTI_NPTS_MAX) return OMNI_ERR_ARG;
     if (S == 0) return OMNI_OK;
-    hipLaunchKernelGGL(kitti_finalize_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, (hipStream_t)stream, counts, K, S, npts, precision,
-                       recall, ap);
+    hipLaunchKernelGGL(kitti_finalize_kernel<false>, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, (hipStream_t)stream, counts, K, S, npts, precision,
+                       recall, ap, (const unsigned long long*)nullptr, (const int*)nullptr, 1, 1);
+    return omni_launch_status();
+}
+
+int omni_kitti_finalize_aos(const int* counts, const long long* sim_sum, const int* K, const int* aos_metric, int S, int M, int O, int npts,
+                            double* aos, double* aos_ap, void* stream) {
+    if (S < 0 || M < 0 || O < 0 || npts < 2 || npts > KITTI_NPTS_MAX) return OMNI_ERR_ARG;
+    if (S == 0) return OMNI_OK;
+    if (M < 1 || O < 1) return OMNI_ERR_ARG;
+    hipLaunchKernelGGL(kitti_finalize_kernel<true>, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, (hipStream_t)stream, counts, K, S, npts, aos,
+                       (double*)nullptr, aos_ap, (const unsigned long long*)sim_sum, aos_metric, M, O);
     return omni_launch_status();
 }
 

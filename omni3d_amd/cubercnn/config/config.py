@@ -130,6 +130,23 @@ def kitti_eval_args(cfg):
     return {"eval_kitti": bool(get("ENABLED")), "kitti_params": {"occCuts": cuts, "dcMetrics": dc}, "kitti_r11": bool(get("R11"))}
 
 
+def add_kitti_aos_config(cfg):
+    """`add_kitti_eval_config` plus TEST.EVAL_KITTI.AOS (default False): also report the benchmark's average orientation similarity
+    (`KittiParams.aos`; 'AOS|R40-car-moderate', ... in `bbox_KITTI` and the `aos` line of the table).  A separate call, as with
+    `add_nms3d_exact_config`, because `add_kitti_eval_config` keeps adding exactly its four keys.  Idempotent: values already set are kept."""
+    add_kitti_eval_config(cfg)
+    cfg.TEST.EVAL_KITTI.setdefault("AOS", False)
+    return cfg
+
+
+def kitti_aos_eval_args(cfg):
+    """`kitti_eval_args(cfg)` with `kitti_params["aos"]` = TEST.EVAL_KITTI.AOS (False for a cfg without the key)"""
+    args = kitti_eval_args(cfg)
+    node = cfg.TEST.get("EVAL_KITTI")
+    args["kitti_params"]["aos"] = bool(node.get("AOS", False)) if node is not None else False
+    return args
+
+
 _EVAL_DIST = {"ENABLED": False, "UP": [], "DIST_THRS": [0.5, 1.0, 2.0, 4.0], "TP_DIST": 2.0, "MIN_RECALL": 0.1}
 
 

@@ -18,7 +18,14 @@ all found, give 47.5).  That is the benchmark's behaviour and is kept.
 Departures and conventions ("KITTI-protocol evaluation"): the 2D box is the `bbox` the Omni3D index selects (the projected
 cuboid, or KITTI's own hand-drawn box with MODAL_2D_BOXES), the occlusion level comes from `visibility` through `occCuts` unless an
 annotation carries an integer `occlusion`, BEV and 3D overlaps are the project's footprint IoU (`kernels.bev`) and exact cuboid IoU
-(`kernels.iou3d.iou_box3d_exact_pairs`), which equal KITTI's rotated-box IoUs for yaw-only boxes.  No AOS, no label files."""
+(`kernels.iou3d.iou_box3d_exact_pairs`), which equal KITTI's rotated-box IoUs for yaw-only boxes.
+
+AOS (`KittiParams.aos`, off by default): the benchmark's average orientation similarity of the 2D-box matching, again a reading of the
+devkit (its `compute_aos` path) written from memory; float64 statement: tests/exact_kitti_aos.py.  Every true positive of pass 2 adds
+(1 + cos(alpha_gt - alpha_dt)) / 2, the sum is divided by tp + fp and treated like precision.  The observation angle alpha of a record
+is its own finite `alpha` key (KITTI's "unknown" -10 counts as absent), else it comes from the cuboid's corners
+(`kernels.kitti.box_params`: the corner order makes v1 - v0 the length axis, whose angle in the ground plane is KITTI's rotation_y);
+a record with neither has no heading and contributes 0.  Label files: `cubercnn.data.kitti_format`."""
 import json
 
 import numpy as np
@@ -37,9 +44,11 @@ class KittiParams:
     occCuts: occlusion level = the number of cuts c with visibility <= c (0 for an unknown, negative visibility).  The cuts are a
     CONVENTION of this project; they have not been checked against the converter that made Omni3D's KITTI annotations.
     dcMetrics: the metrics in which DontCare regions absorb false positives; all three is this project's reading of the C++ devkit
-    (its numba port restricts the step to 2D)."""
+    (its numba port restricts the step to 2D).
+    aos: also compute the average orientation similarity of the 2D-box matching (it needs "2D" among `metrics`, as in the devkit)."""
 
     def __init__(self):
+        self.aos = False
         self.classes = ("car", "pedestrian", "cyclist")
         self.minOverlaps = {"strict": (0.7, 0.5, 0.5), "loose": (0.5, 0.25, 0.25)}
         self.neighbours = {"car": ("van",), "pedestrian": ("person",)}
@@ -62,6 +71,17 @@ class KittiParams:
             raise ValueError("nSamplePts must lie in [2, %d]" % K.MAX_PTS)
         if any(len(d) != 4 for d in self.difficulties):
             raise ValueError("a difficulty is (name, min height, max occlusion, max truncation)")
+        if self.aos and "2D" not in self.metrics:
+            raise ValueError("aos belongs to the matching of the 2D box: metrics must contain \"2D\"")
+
+
+def record_alpha(a):
+    """the observation angle a record states itself: its finite `alpha` key, KITTI's "unknown" -10 counting as absent -> float or NaN"""
+    v = a.get("alpha")
+    if v is None:
+        return float("nan")
+    v = float(v)
+    return v if np.isfinite(v) and v != -10.0 else float("nan")
 
 
 def occlusion_level(ann, cuts):
@@ -123,7 +143,11 @@ class KittiEval:
 
     `eval` after evaluate(): `precision`, `recall`, `thresholds` [class, difficulty, metric, overlap set, 41], `counts` [..., 41, 3]
     (tp, fp, fn), `n_gt`, `K`, `ap_r40`, `ap_r11` [class, difficulty, metric, overlap set]; the AP of a class the data set lacks is
-    NaN.  More than 1024 detections or ground-truth rows in one image raise ValueError before any launch."""
+    NaN.  More than 1024 detections or ground-truth rows in one image raise ValueError before any launch.
+
+    With `params.aos`: `aos` [..., 41] (NaN in the metrics other than 2D), `aos_r40`, `aos_r11`, `sim_sum` [..., 41] (the fixed-point
+    orientation sums, units of 2^-40) and `n_unoriented`, the ground-truth rows of the evaluated classes without a heading (no `alpha`
+    key and no valid cuboid); `results()` gains the 'AOS|R40-car-moderate' rows and `summarize()` the devkit's `aos` line after `bbox`."""
 
     def __init__(self, gt, dt, names=None, params=None, img_ids=None):
         self.gt, self.dt, self.names, self.img_ids = gt, dt, names, img_ids
@@ -231,9 +255,20 @@ class KittiEval:
             to([float(a["bbox"][3]) for a, _ in rows_g], np.float64), to([occlusion_level(a, p.occCuts) for a, _ in rows_g], np.int32),
             to(trunc, np.float64), cls_tab, [[float(h), float(o), float(t)] for _, h, o, t in p.difficulties],
             np.array([p.minOverlaps[o] for o in osets], dtype=np.float64).reshape(len(osets), len(classes)), [m in p.dcMetrics for m in p.metrics])
-        out = K.run(pb, p.nSamplePts)
+        keys = ("n_gt", "K", "thresholds", "counts", "precision", "recall", "ap")
+        if p.aos:
+            # a record's own `alpha` wins; the others take theirs from the corners, all cuboids in one launch (NaN without a valid one)
+            own_d, own_g = (to([record_alpha(x) for x, _ in rows], np.float64) for rows in (rows_d, rows_g))
+            from_box = K.box_params(torch.cat([b3_d, b3_g]).contiguous(), p.up)[:, 7]
+            dt_alpha = torch.where(torch.isnan(own_d), from_box[:len(rows_d)], own_d).contiguous()
+            gt_alpha = torch.where(torch.isnan(own_g), from_box[len(rows_d):], own_g).contiguous()
+            out = K.run_aos(pb, dt_alpha, gt_alpha, [m == "2D" for m in p.metrics], p.nSamplePts)
+            out["gt_alpha"] = gt_alpha
+            keys += ("sim_sum", "aos", "aos_ap", "gt_alpha")
+        else:
+            out = K.run(pb, p.nSamplePts)
         shape = (len(classes), len(p.difficulties), len(p.metrics), len(osets))
-        host = {k: out[k].cpu().numpy() for k in ("n_gt", "K", "thresholds", "counts", "precision", "recall", "ap")}      # the one synchronisation
+        host = {k: out[k].cpu().numpy() for k in keys}      # the one synchronisation
         ap = host["ap"].reshape(shape + (2,)).copy()
         self.lacking = [c for c in classes if c not in known]
         for c, cname in enumerate(classes):
@@ -243,6 +278,17 @@ class KittiEval:
                      "thresholds": host["thresholds"].reshape(shape + (-1,)), "counts": host["counts"].reshape(shape + (-1, 3)),
                      "n_gt": host["n_gt"].reshape(shape), "K": host["K"].reshape(shape), "ap_r40": ap[..., 0], "ap_r11": ap[..., 1],
                      "classes": classes, "difficulties": [d[0] for d in p.difficulties], "metrics": list(p.metrics), "overlaps": osets}
+        if p.aos:
+            aos_ap = host["aos_ap"].reshape(shape + (2,)).copy()
+            for c, cname in enumerate(classes):
+                if cname in self.lacking:
+                    aos_ap[c] = np.nan
+            # ground-truth rows of the evaluated classes without a heading: each can only ever contribute 0
+            of_class = np.array([n in classes for (n, _), _ in sorted(code_of.items(), key=lambda kv: kv[1])] + [False], dtype=bool)
+            codes_g = np.array([c for _, c in rows_g], dtype=np.int64)
+            self.eval.update({"aos": host["aos"].reshape(shape + (-1,)), "aos_r40": aos_ap[..., 0], "aos_r11": aos_ap[..., 1],
+                              "sim_sum": host["sim_sum"].reshape(shape + (-1,)),
+                              "n_unoriented": int((of_class[codes_g] & ~np.isfinite(host["gt_alpha"])).sum())})
         return self.eval
 
     def results(self, r11=False):
@@ -255,6 +301,11 @@ class KittiEval:
                     for c, cname in enumerate(e["classes"]):
                         for d, dname in enumerate(e["difficulties"]):
                             out["%s|%s-%s-%s%s" % (METRIC_NAMES[metric][1], tag, cname, dname, "" if o == 0 else "@" + oname)] = float(e[key][c, d, m, o])
+                if "aos_r40" in e:                  # with `aos`: the orientation rows of the 2D matching
+                    m = e["metrics"].index("2D")
+                    for c, cname in enumerate(e["classes"]):
+                        for d, dname in enumerate(e["difficulties"]):
+                            out["AOS|%s-%s-%s%s" % (tag, cname, dname, "" if o == 0 else "@" + oname)] = float(e["aos_" + tag.lower()][c, d, m, o])
         return out
 
     def summarize(self, r11=False, overlaps=None, verbose=True):
@@ -273,6 +324,10 @@ class KittiEval:
                     lines.append("%s AP|%s@%.2f (%s; %s):" % (cname.capitalize(), tag, mo, oname, ", ".join(e["difficulties"])))
                     for m, metric in enumerate(e["metrics"]):
                         lines.append("%-4s AP:%s" % (METRIC_NAMES[metric][0], ", ".join("%.4f" % v for v in e[key][c, :, m, o])))
+                        if metric == "2D" and "aos_r40" in e:
+                            lines.append("%-4s AP:%s" % ("aos", ", ".join("%.4f" % v for v in e["aos_" + tag.lower()][c, :, m, o])))
+        if e.get("n_unoriented"):
+            lines.append("AOS: %d ground-truth rows of the evaluated classes have no heading; a true positive on one adds 0" % e["n_unoriented"])
         text = "\n".join(lines)
         if verbose:
             print(text)

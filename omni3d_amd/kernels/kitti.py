@@ -4,6 +4,11 @@ in float64, in tests/exact_kitti.py.  The interface follows `kernels/accumulate.
 
 A `Problem` holds one packed data set (per-image row ranges, per-row quantities, the similarity matrices and the small tables);
 `match_tp`, `thresholds`, `match_counts` and `finalize` are the four launches and `run` chains them without a host round trip.
+
+AOS (the benchmark's average orientation similarity; like the rest a reading of the devkit written from memory, stated in float64 by
+tests/exact_kitti_aos.py): `match_counts_aos` / `finalize_aos` are pass 2 and the finalize with the orientation sum, `run_aos` chains
+the four launches with them.  `box_params` (csrc/kitti_params.hip) turns cuboid corners into KITTI's h, w, l, location, rotation_y and
+alpha; it is where the headings of `KittiEval` and the label files of `cubercnn.data.kitti_format` come from.
 """
 import numpy as np
 import torch
@@ -136,3 +141,105 @@ def run(pb, npts=41):
     counts = match_counts(pb, thr, K)
     prec, rec, ap = finalize(pb, counts, K)
     return {"tp_score": tp, "n_gt": n_gt, "thresholds": thr, "K": K, "counts": counts, "precision": prec, "recall": rec, "ap": ap}
+
+
+# ---- AOS ---------------------------------------------------------------------------------------------------------------------------
+AOS_ONE = 2 ** 40          # the fixed point of `sim_sum`: one true positive with equal headings adds 2^40
+AOS_MAX_ROWS = 2 ** 23     # sumG below this: sumG true positives of at most 2^40 each stay below 2^63
+
+
+def _check_aos(pb, dt_alpha, gt_alpha, aos_metric):
+    """the argument check of the AOS launches -> aos_metric as a host int32 array; ValueError before anything is allocated or launched"""
+    if pb.sumG >= AOS_MAX_ROWS:
+        raise ValueError(f"{pb.sumG} ground-truth rows: the fixed-point orientation sum takes fewer than 2^23")
+    for t, name, n in ((dt_alpha, "dt_alpha", pb.sumD), (gt_alpha, "gt_alpha", pb.sumG)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != (n,) or t.device != pb.device:
+            raise ValueError(f"{name} must be {torch.float64} of shape ({n},) on {pb.device}")
+    aos_metric = np.asarray(aos_metric).astype(np.int32).reshape(-1)
+    if len(aos_metric) != pb.M:
+        raise ValueError(f"aos_metric must hold one value per metric ({pb.M})")
+    return aos_metric
+
+
+def match_counts_aos(pb, thr, K, dt_alpha, gt_alpha, aos_metric, out=None):
+    """pass 2 with the orientation sum -> (counts (S, npts, 3) int32, the bits of `match_counts`; sim_sum (S, npts) int64: over the
+    true positives of the slots whose metric has aos_metric[m] != 0, the sum of llrint(2^40 (1 + cos(gt_alpha - dt_alpha)) / 2), a
+    non-finite alpha on either side contributing 0).  dt_alpha (sumD,), gt_alpha (sumG,) float64, NaN: no heading.  `out` is zeroed here."""
+    aos_metric = _check_aos(pb, dt_alpha, gt_alpha, aos_metric)
+    npts = _check_pts(thr.shape[1])
+    counts, sim_sum = out if out is not None else (torch.empty((pb.S, npts, 3), dtype=torch.int32, device=pb.device),
+                                                   torch.empty((pb.S, npts), dtype=torch.int64, device=pb.device))
+    counts.zero_()
+    sim_sum.zero_()
+    p = _lib.ptr
+    _lib.check_device(dt_alpha, gt_alpha)
+    metric = torch.from_numpy(aos_metric).to(pb.device)
+    pb.lib.call("omni_kitti_match_counts_aos", *pb._common(), p(pb.dc_ov), p(pb.dc_pair_off), p(pb.dc_off), p(pb.dc_metric), p(thr), p(K), npts,
+                *pb._sizes(), p(dt_alpha), p(gt_alpha), p(metric), p(counts), p(sim_sum), _lib.stream_of(counts))
+    return counts, sim_sum
+
+
+def finalize_aos(pb, counts, sim_sum, K, aos_metric, out=None):
+    """-> (aos (S, npts): sim_sum 2^-40 / (tp + fp), made monotone from the right like precision; aos_ap (S, 2) = (AOS|R40, AOS|R11)
+    x 100), float64; NaN for the slots of a metric with aos_metric[m] == 0"""
+    npts = _check_pts(counts.shape[1])
+    aos_metric = np.asarray(aos_metric).astype(np.int32).reshape(-1)
+    if len(aos_metric) != pb.M:
+        raise ValueError(f"aos_metric must hold one value per metric ({pb.M})")
+    if not isinstance(sim_sum, torch.Tensor) or sim_sum.dtype != torch.int64 or tuple(sim_sum.shape) != (pb.S, npts) or sim_sum.device != counts.device:
+        raise ValueError(f"sim_sum must be int64 of shape ({pb.S}, {npts}) on {counts.device}")
+    aos, aos_ap = out if out is not None else (torch.empty((pb.S, npts), dtype=torch.float64, device=pb.device),
+                                               torch.empty((pb.S, 2), dtype=torch.float64, device=pb.device))
+    metric = torch.from_numpy(aos_metric).to(pb.device)
+    pb.lib.call("omni_kitti_finalize_aos", _lib.ptr(counts), _lib.ptr(sim_sum), _lib.ptr(K), _lib.ptr(metric), pb.S, pb.M, pb.O, npts,
+                _lib.ptr(aos), _lib.ptr(aos_ap), _lib.stream_of(aos))
+    return aos, aos_ap
+
+
+def run_aos(pb, dt_alpha, gt_alpha, aos_metric, npts=41):
+    """`run` with AOS: five launches on the current stream, nothing read back -> the dict of `run` (the same bits) plus sim_sum, aos,
+    aos_ap"""
+    _check_aos(pb, dt_alpha, gt_alpha, aos_metric)
+    tp, n_gt = match_tp(pb)
+    thr, K = thresholds(pb, tp, n_gt, npts)
+    counts, sim_sum = match_counts_aos(pb, thr, K, dt_alpha, gt_alpha, aos_metric)
+    prec, rec, ap = finalize(pb, counts, K)
+    aos, aos_ap = finalize_aos(pb, counts, sim_sum, K, aos_metric)
+    return {"tp_score": tp, "n_gt": n_gt, "thresholds": thr, "K": K, "counts": counts, "precision": prec, "recall": rec, "ap": ap,
+            "sim_sum": sim_sum, "aos": aos, "aos_ap": aos_ap}
+
+
+# ---- cuboid corners -> KITTI's box parameters -----------------------------------------------------------------------------------
+UP = (0.0, -1.0, 0.0)              # camera y points down
+
+
+def check_up(up):
+    """-> the up vector as three floats; ValueError for one that is not three finite numbers, of zero length or parallel to camera x
+    (the ground-plane axis a = camera x less its part along up would vanish)"""
+    u = np.asarray(up, dtype=np.float64).reshape(-1)
+    if u.shape != (3,) or not np.isfinite(u).all() or not np.linalg.norm(u) > 0:
+        raise ValueError("up must be three finite numbers, not all zero")
+    n = u / np.linalg.norm(u)
+    if not np.linalg.norm(np.array([1.0, 0.0, 0.0]) - n[0] * n) > 1e-12:
+        raise ValueError("up must not be parallel to camera x: the heading is measured from camera x in the ground plane")
+    return tuple(float(v) for v in u)
+
+
+def box_params(corners, up=UP):
+    """corners (N, 8, 3) float32 contiguous, in the corner order of `det.cuboid_corners` (v1 - v0 the length axis, v3 - v0 the height
+    axis, v4 - v0 the width axis) -> (N, 9) float64: h, w, l, x, y, z, rotation_y, alpha, valid.  (x, y, z) is the centre of the bottom
+    face, c - (h / 2) up; rotation_y = atan2(-e.b, e.a) for e = v1 - v0 in the ground-plane basis (a, b) of `up` (up = (0, -1, 0):
+    a = camera x, b = camera z), which is KITTI's rotation_y for R = Ry(ry); a heading without a ground-plane component gives
+    atan2(0, 0) = 0.  alpha = rotation_y - atan2(c.a, c.b) in (-pi, pi].  valid = 0, and NaN elsewhere, for a box with a non-finite
+    corner or a zero edge.  One launch; N == 0 launches nothing."""
+    if not isinstance(corners, torch.Tensor) or corners.dtype != torch.float32 or corners.dim() != 3 or tuple(corners.shape[1:]) != (8, 3):
+        raise ValueError("corners must be a float32 tensor of shape (N, 8, 3)")
+    if not corners.is_contiguous():
+        raise ValueError("corners must be contiguous")
+    up = check_up(up)
+    L = _lib.check_device(corners)
+    n = corners.shape[0]
+    out = torch.empty((n, 9), dtype=torch.float64, device=corners.device)
+    if n > 0:
+        L.call("omni_kitti_box_params", _lib.ptr(corners), n, *up, _lib.ptr(out), _lib.stream_of(corners))
+    return out

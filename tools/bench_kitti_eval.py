@@ -5,6 +5,7 @@ vans, persons and DontCare regions), yaw-only cuboids, detections = jittered gro
 warm-up call.  Beside it, on the same records, `Omni3Deval(mode="3D")` `evaluate()` + `accumulate()`: the existing thing a reader can
 relate the number to, not a bar.  Information only: there is no earlier figure and no speed bar.
     python tools/bench_kitti_eval.py [output file]
+    python tools/bench_kitti_eval.py --aos [output file]     # evaluate() without and with AOS in one run, both figures APPENDED to the file
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_kitti_eval.py --once      # one evaluate() for the per-launch times"""
 import os
 import statistics
@@ -23,6 +24,7 @@ DIMS = {1: (3.9, 1.5, 1.6), 2: (0.8, 1.75, 0.6), 3: (1.8, 1.7, 0.6), 4: (5.0, 2.
 # the compiler's report for gfx950: VGPR / LDS bytes per workgroup / waves per SIMD / scratch
 RESOURCES = (("kitti_match_tp_kernel", 20, 0, 8, 0), ("kitti_thresholds_kernel", 24, 1304, 8, 0), ("kitti_match_counts_kernel", 28, 0, 8, 0),
              ("kitti_finalize_kernel", 34, 0, 8, 0))
+RESOURCES_AOS = (("kitti_match_counts_kernel<true>", 70, 0, 7, 0), ("kitti_finalize_kernel<true>", 24, 0, 8, 0), ("kitti_box_params_kernel", 72, 0, 7, 0))
 
 
 def _ry(a):
@@ -102,6 +104,26 @@ def main(argv):
     ev = KittiEval(gt_index, dts, names=names)
     if "--once" in argv:
         ev.evaluate()
+        return
+    if "--aos" in argv:
+        # the same evaluator without and with `aos`, one after the other in this run: the comparison is between these two figures
+        t_off = timed(ev.evaluate)
+        ev.params.aos = True
+        t_on = timed(ev.evaluate)
+        e = ev.eval
+        lines = ["AOS (--aos), the same set and run: KittiEval.evaluate() without AOS median %.1f ms (min %.1f, max %.1f), with AOS median %.1f ms "
+                 "(min %.1f, max %.1f); device events around each of %d calls after one warm-up call"
+                 % (statistics.median(t_off), min(t_off), max(t_off), statistics.median(t_on), min(t_on), max(t_on), BLOCKS),
+                 "AOS|R40 car easy / moderate / hard at the strict overlaps: %s (AP2D|R40: %s); ground-truth rows without a heading: %d"
+                 % (", ".join("%.2f" % v for v in e["aos_r40"][0, :, 0, 0]), ", ".join("%.2f" % v for v in e["ap_r40"][0, :, 0, 0]), e["n_unoriented"]),
+                 "gfx950 resources of the AOS kernels from the compiler's report (VGPR / LDS bytes per workgroup / waves per SIMD / scratch):"]
+        lines += ["  %-32s %3d / %4d / %d / %d" % r for r in RESOURCES_AOS]
+        text = "\n".join(lines) + "\n"
+        print(text, end="")
+        out = [a for a in argv if not a.startswith("--")]
+        if out:
+            with open(out[0], "a") as f:
+                f.write(text)
         return
     t_kitti = timed(ev.evaluate)
     plain = [g for g in gts if g["category_id"] != 6]

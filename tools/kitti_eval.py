@@ -1,11 +1,15 @@
 """The KITTI object benchmark's protocol on an Omni3D annotation file and a result file:
 
-    python tools/kitti_eval.py datasets/Omni3D/KITTI_val.json output/inference/KITTI_val/omni_instances_results.json [--r11] [--loose]
+    python tools/kitti_eval.py datasets/Omni3D/KITTI_val.json output/inference/KITTI_val/omni_instances_results.json [--r11] [--loose] [--aos]
+    python tools/kitti_eval.py label_2/ results/data/ --aos          # directories of KITTI label files in place of either JSON file
 
 prints AP|R40 of the 2D box, the bird's-eye view and the 3D box at Easy / Moderate / Hard for car, pedestrian and cyclist
 (`cubercnn.evaluation.kitti.KittiEval`; the protocol is this project's reading of the devkit).  --r11 adds the 11-point
 AP, --loose the table at the loose min-overlaps (0.5 / 0.25 / 0.25).  The result file holds the records of
-`omni_instances_results.json`, with the category ids of the annotation file."""
+`omni_instances_results.json`, with the category ids of the annotation file.  --aos adds the `aos` line (average orientation similarity
+of the 2D-box matching; the heading of a record is its `alpha` key, else it comes from its cuboid).  A directory in place of a file
+is read as KITTI label files (`cubercnn.data.kitti_format.read_kitti_labels`: no calibration file is read, no `P2` shift is applied,
+the image ids are the numeric file stems); with a directory on both sides the two must name the same images."""
 import argparse
 import os
 import sys
@@ -15,8 +19,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("gt", help="Omni3D annotation file (JSON)")
-    ap.add_argument("dt", help="detections: the records of omni_instances_results.json")
+    ap.add_argument("gt", help="Omni3D annotation file (JSON), or a directory of KITTI label files")
+    ap.add_argument("dt", help="detections: the records of omni_instances_results.json, or a directory of KITTI result files")
+    ap.add_argument("--aos", action="store_true", help="also print the average orientation similarity")
     ap.add_argument("--r11", action="store_true", help="also print the 11-point AP")
     ap.add_argument("--loose", action="store_true", help="also print the table at the loose min-overlaps")
     ap.add_argument("--modal-2d-boxes", action="store_true", help="use KITTI's own 2D boxes (bbox2D_tight) where present, as DATASETS.MODAL_2D_BOXES")
@@ -26,7 +31,11 @@ def main(argv=None):
     fs = get_filter_settings_from_cfg(None)
     fs["ignore_names"] = ["dontcare", "ignore", "void"]
     fs["modal_2D_boxes"] = bool(args.modal_2d_boxes)
-    ev = KittiEval(Omni3D([args.gt], filter_settings=fs), args.dt)
+    from omni3d_amd.cubercnn.data.kitti_format import read_kitti_labels
+    gt = read_kitti_labels(args.gt, with_score=False) if os.path.isdir(args.gt) else Omni3D([args.gt], filter_settings=fs)
+    dt = read_kitti_labels(args.dt, with_score=True) if os.path.isdir(args.dt) else args.dt
+    ev = KittiEval(gt, dt)
+    ev.params.aos = bool(args.aos)
     ev.evaluate()
     ev.summarize(r11=args.r11, overlaps=None if args.loose else (list(ev.params.minOverlaps)[0],))
     return ev
