@@ -12,7 +12,15 @@ CASES = [  # H, W -> out_h, out_w, flip
     (64, 48, 50, 48, False),     # vertical only
     (33, 47, 33, 47, True),      # flip only
     (200, 150, 341, 256, True),  # ResizeShortestEdge-style: short edge 150 -> 256
+    # more work items than grid_for's 8192 x 256 threads, and no multiple of them: the grid-stride loops of all three kernels run a
+    # second, partial trip (horizontal 3*750*1067 = 2 400 750, vertical 3*800*1067 = 2 560 800, flip 3*840*840 = 2 116 800)
+    (750, 1000, 800, 1067, True),
+    (840, 840, 840, 840, True),
 ]
+GRID_CAP = 8192 * 256
+for _H, _W, _oh, _ow, _flip in CASES[-2:]:
+    for _n in ([3 * _H * _ow, 3 * _oh * _ow] if (_H, _W) != (_oh, _ow) else [3 * _H * _W]):
+        assert _n > GRID_CAP and _n % GRID_CAP != 0, (_n, GRID_CAP)
 
 
 def _pil(img_chw, out_h, out_w, flip):
@@ -35,6 +43,23 @@ def _run(dev):
         got = resize.resize_bilinear_u8(torch.from_numpy(img).to(dev), oh, ow, flip).cpu().numpy()
         assert got.shape == want.shape
         assert np.array_equal(got, want), (H, W, oh, ow, flip, int(np.abs(got.astype(int) - want.astype(int)).max()))
+        got = _prefilled(torch.from_numpy(img).to(dev), oh, ow, flip).cpu().numpy()
+        assert np.array_equal(got, want), (H, W, oh, ow, flip, "0xFF-prefilled output")
+
+
+def _prefilled(src, out_h, out_w, flip):
+    """the launch of resize.resize_bilinear_u8 with the output and the intermediate image pre-filled with 0xFF: a fresh allocation is
+    often zero, which would hide an unwritten pixel of the black quarter of the test image"""
+    from omni3d_amd import lib
+    from omni3d_amd.kernels.resize import pil_bilinear_coeffs
+    planes, H, W = src.shape
+    (bh, kh, ksh), (bv, kv, ksv) = pil_bilinear_coeffs(W, out_w), pil_bilinear_coeffs(H, out_h)
+    tabs = [torch.from_numpy(np.ascontiguousarray(a)).to(src.device) for a in (bh, kh, bv, kv)]
+    out = torch.full((planes, out_h, out_w), 255, dtype=torch.uint8, device=src.device)
+    tmp = torch.full((planes * H * out_w,), 255, dtype=torch.uint8, device=src.device)
+    lib.get().call("omni_resize_bilinear_u8", src.data_ptr(), out.data_ptr(), tmp.data_ptr(), planes, H, W, out_h, out_w, tabs[0].data_ptr(),
+                   tabs[1].data_ptr(), ksh, tabs[2].data_ptr(), tabs[3].data_ptr(), ksv, int(flip), lib.stream_of(src))
+    return out
 
 
 def test_coefficients_reproduce_pil_on_the_host():
