@@ -1,31 +1,27 @@
 """Launchers of csrc/annotate.hip: the derived box fields of Omni3D annotations (`bbox3D_cam`, `bbox2D_proj`, `bbox2D_trunc`,
 `truncation`, `behind_camera` and the counters behind `visibility`) for all boxes of all images of a dataset, one launch each --
 `get_cuboid_verts` / `convert_3d_box_to_2d` / `estimate_truncation` / `estimate_visibility` of the reference
-(cubercnn/util/math_util.py:221-259, 498-577, 745-758, 728-743), which handle one box or one image per call.
+(cubercnn/util/math_util.py:221-259, 498-577, 745-758, 728-743), which handle one box or one image per call.  The arguments are
+checked by `kernels/_args.py`.
 """
 import numpy as np
 import torch
 
 from .. import lib as _lib
-from .viserr import _check, _check_offsets
+from . import _args
 
 TILE = 16          # csrc/cuboid_cast.h
 
 
 def _inputs(box3d, R, box_off, K, size):
-    f32, i32 = torch.float32, torch.int32
-    if not isinstance(box_off, torch.Tensor) or box_off.dim() != 1 or box_off.numel() < 1:
-        raise ValueError("box_off must be a (I + 1,) int32 tensor")
-    I = box_off.numel() - 1
-    N = box3d.shape[0] if isinstance(box3d, torch.Tensor) and box3d.dim() else -1
-    _check(box3d, f32, (N, 6), "box3d")
-    for t, n, name in ((R, N, "R"), (K, I, "K")):
-        _check(t, f32, (n, 3, 3) if isinstance(t, torch.Tensor) and t.dim() == 3 else (n, 9), name)
-    _check(size, i32, (I, 2), "size")
-    _check_offsets(box_off, I, N, "box_off")
+    I = _args.offset_count(box_off, "box_off")
+    N = _args.tensor(box3d, "box3d", torch.float32, (None, 6))[0]
+    _args.matrices(R, N, "R")
+    _args.matrices(K, I, "K")
+    _args.tensor(size, "size", torch.int32, (I, 2))
+    _args.offsets(box_off, "box_off", N)
     tensors = (box3d, R, box_off, K, size)
-    if len({t.device for t in tensors}) != 1:
-        raise ValueError("all inputs must live on one device")
+    _args.one_device(tensors)
     return I, N, tensors
 
 

@@ -1,5 +1,5 @@
 """Launchers of csrc/eval_bootstrap.hip: AP and recall of B image-level bootstrap replicates from the one set of match tables of an
-evaluation.  The reference has no counterpart; the interface follows `kernels/let.py`.
+evaluation.  The reference has no counterpart; the arguments are checked by `kernels/_args.py`.
 
 A replicate is a row of `weights` (B, I) int32: how many times each of the I evaluated images is present.  Its result is by definition
 what `omni_eval_accumulate` gives on the data set in which image i is present weights[b, i] times, copies adjacent in the image order;
@@ -11,7 +11,7 @@ Overflow rule: the weighted counts are 32-bit.  `bootstrap_counts` raises ValueE
 import torch
 
 from .. import lib as _lib
-from .tperr import _check
+from . import _args
 
 COUNT_LIMIT = 1 << 31
 MAX_IMAGES = 1 << 29
@@ -40,24 +40,16 @@ def bootstrap_counts(grp_off, grp_img, grp_npig, weights, sum_gt=None):
     grp_off (K+1,) int32 / grp_img (G,) int32 / grp_npig (G, A) int32: the (image, category) groups of the evaluation in (category,
     image) order: their ranges per category, the index of a group's image in [0, I), its non-ignored ground truths per range; sum_gt:
     an upper bound of the column sums of grp_npig (default: the largest of them)."""
-    _check(grp_off, "grp_off", torch.int32, (grp_off.numel() if isinstance(grp_off, torch.Tensor) else 0,))
-    K = grp_off.numel() - 1
-    if K < 0:
-        raise ValueError("grp_off must hold K + 1 offsets")
-    G = grp_img.numel() if isinstance(grp_img, torch.Tensor) else 0
-    _check(grp_img, "grp_img", torch.int32, (G,))
-    if not isinstance(grp_npig, torch.Tensor) or grp_npig.dim() != 2 or grp_npig.shape[1] < 1:
+    K = _args.offset_count(grp_off, "grp_off")
+    G = _args.tensor(grp_img, "grp_img", torch.int32, (None,))[0]
+    A = _args.tensor(grp_npig, "grp_npig", torch.int32, (G, None))[1]
+    if A < 1:
         raise ValueError("grp_npig must have shape (G, A) with A >= 1")
-    A = grp_npig.shape[1]
-    _check(grp_npig, "grp_npig", torch.int32, (G, A))
     wmax = check_weights(weights)
     B, I = weights.shape
     tensors = (grp_off, grp_img, grp_npig, weights)
-    if len({t.device for t in tensors}) != 1:
-        raise ValueError("all inputs must live on one device")
-    off = grp_off.tolist()
-    if off[0] != 0 or off[-1] != G or any(b < a for a, b in zip(off, off[1:])):
-        raise ValueError("grp_off must ascend from 0 to the number of groups")
+    _args.one_device(tensors)
+    _args.offsets(grp_off, "grp_off", G)
     if G and (int(grp_npig.min()) < 0 or int(grp_img.min()) < 0 or int(grp_img.max()) >= I):
         raise ValueError("grp_npig must be >= 0 and grp_img must index the I images")
     if sum_gt is None:
@@ -81,40 +73,20 @@ def bootstrap_accumulate(order, cat_off, rank, dt_match, dt_ignore, det_img, wei
     (R,) float64 / max_dets (M,) int32: as for `kernels.let.accumulate_let`; det_img (sumD,) int32: the index of a detection's image in
     [0, I); weights (B, I) int32 >= 0; npig_b (B, K, A) / has_e_b (B, K) int32 from `bootstrap_counts`.  One launch; two calls, and any
     split of the rows of `weights` over several calls, give the same bits."""
-    _check(cat_off, "cat_off", torch.int32, (cat_off.numel() if isinstance(cat_off, torch.Tensor) else 0,))
-    K = cat_off.numel() - 1
-    if K < 0:
-        raise ValueError("cat_off must hold K + 1 offsets")
-    _check(order, "order", torch.int32, (order.numel() if isinstance(order, torch.Tensor) else 0,))
-    if not isinstance(dt_match, torch.Tensor) or dt_match.dim() != 3 or dt_match.shape[0] < 1 or dt_match.shape[1] < 1:
-        raise ValueError("dt_match must have shape (A, T, sumD) with A >= 1 and T >= 1")
-    A, T, sumD = dt_match.shape
-    _check(dt_match, "dt_match", torch.int32, (A, T, sumD))
-    _check(dt_ignore, "dt_ignore", torch.uint8, (A, T, sumD))
-    _check(rank, "rank", torch.int32, (sumD,))
-    _check(det_img, "det_img", torch.int32, (sumD,))
+    K, A, T, R, sumD, _ = _args.merge_order(order, cat_off, dt_match, dt_ignore, rec_thrs)
+    _args.tensor(rank, "rank", torch.int32, (sumD,))
+    _args.tensor(det_img, "det_img", torch.int32, (sumD,))
     wmax = check_weights(weights)
     B, I = weights.shape
-    _check(npig_b, "npig_b", torch.int32, (B, K, A))
-    _check(has_e_b, "has_e_b", torch.int32, (B, K))
-    if not isinstance(rec_thrs, torch.Tensor) or rec_thrs.dim() != 1 or rec_thrs.numel() < 1:
-        raise ValueError("rec_thrs must be 1-D and not empty")
-    _check(rec_thrs, "rec_thrs", torch.float64, (rec_thrs.numel(),))
-    if not isinstance(max_dets, torch.Tensor) or max_dets.dim() != 1 or max_dets.numel() < 1:
-        raise ValueError("max_dets must be 1-D and not empty")
-    _check(max_dets, "max_dets", torch.int32, (max_dets.numel(),))
+    _args.tensor(npig_b, "npig_b", torch.int32, (B, K, A))
+    _args.tensor(has_e_b, "has_e_b", torch.int32, (B, K))
+    M = _args.nonempty(max_dets, "max_dets", torch.int32)
     tensors = (order, cat_off, rank, dt_match, dt_ignore, det_img, weights, npig_b, has_e_b, rec_thrs, max_dets)
-    if len({t.device for t in tensors}) != 1:
-        raise ValueError("all inputs must live on one device")
-    off = cat_off.tolist()
-    if off[0] != 0 or off[-1] != order.numel() or any(b < a for a, b in zip(off, off[1:])):
-        raise ValueError("cat_off must ascend from 0 to len(order)")
-    if order.numel() and (int(order.min()) < 0 or int(order.max()) >= sumD):
-        raise ValueError("order must index the sumD detections")
+    _args.one_device(tensors)
     if sumD * wmax >= COUNT_LIMIT:
         raise ValueError("weighted detection counts would reach 2^31: %d detections x weight %d" % (sumD, wmax))
     L = _lib.check_device(*tensors)
-    R, M, dev = rec_thrs.numel(), max_dets.numel(), weights.device
+    dev = weights.device
     ap = torch.full((B, T, K, A, M), -1.0, dtype=torch.float64, device=dev)
     ar = torch.full((B, T, K, A, M), -1.0, dtype=torch.float64, device=dev)
     if K > 0:

@@ -430,6 +430,22 @@ NMS3D_METHODS = ("evaluator", "exact")
 NMS3D_MAX_SLOTS = 1024     # NMS3D_MAXS of csrc/nms3d.hip: the slots per image the LDS arrays of its second launch hold
 
 
+def _slot_table(prefix, count, verts, scores, cls):
+    """count (B,) int32, verts (B*S, 8, 3) float32, scores (B*S,) float32, cls (B, S) or (B*S,) int32 -> (B, N = B*S, S)"""
+    if count.dim() != 1 or count.dtype != torch.int32:
+        raise ValueError(f"{prefix}: count must be int32 of shape (B,), got {count.dtype} {tuple(count.shape)}")
+    B = count.shape[0]
+    if verts.dim() != 3 or tuple(verts.shape[1:]) != (8, 3) or verts.dtype != torch.float32 or (B and verts.shape[0] % B) or (not B and verts.shape[0]):
+        raise ValueError(f"{prefix}: verts must be float32 of shape (B*S, 8, 3) for B = {B}, got {verts.dtype} {tuple(verts.shape)}")
+    N = verts.shape[0]
+    S = N // B if B else 0
+    if scores.dtype != torch.float32 or tuple(scores.shape) != (N,):
+        raise ValueError(f"{prefix}: scores must be float32 of shape ({N},), got {scores.dtype} {tuple(scores.shape)}")
+    if cls.dtype != torch.int32 or cls.numel() != N or tuple(cls.shape) not in ((N,), (B, S)):
+        raise ValueError(f"{prefix}: cls must be int32 of shape ({B}, {S}) or ({N},), got {cls.dtype} {tuple(cls.shape)}")
+    return B, N, S
+
+
 def nms3d(verts, scores, cls, count, iou_thr, class_agnostic=True, eps_coplanar=1e-4, eps_nonzero=1e-8, method="evaluator"):
     """Greedy suppression of duplicate cuboids among the fixed detection slots (csrc/nms3d.hip, omni_nms3d): verts (B*S, 8, 3)
     float32, scores (B*S,) float32, cls (B, S) or (B*S,) int32, count (B,) int32 -> keep (B, S) int32, order (B, S) int32 (the kept
@@ -440,17 +456,7 @@ def nms3d(verts, scores, cls, count, iou_thr, class_agnostic=True, eps_coplanar=
     the number of slots in use whose corners are no cuboid, and such a slot takes no part."""
     if method not in NMS3D_METHODS:
         raise ValueError(f"nms3d: method must be one of {NMS3D_METHODS}, got {method!r}")
-    if count.dim() != 1 or count.dtype != torch.int32:
-        raise ValueError(f"nms3d: count must be int32 of shape (B,), got {count.dtype} {tuple(count.shape)}")
-    B = count.shape[0]
-    if verts.dim() != 3 or tuple(verts.shape[1:]) != (8, 3) or verts.dtype != torch.float32 or (B and verts.shape[0] % B) or (not B and verts.shape[0]):
-        raise ValueError(f"nms3d: verts must be float32 of shape (B*S, 8, 3) for B = {B}, got {verts.dtype} {tuple(verts.shape)}")
-    N = verts.shape[0]
-    S = N // B if B else 0
-    if scores.dtype != torch.float32 or tuple(scores.shape) != (N,):
-        raise ValueError(f"nms3d: scores must be float32 of shape ({N},), got {scores.dtype} {tuple(scores.shape)}")
-    if cls.dtype != torch.int32 or cls.numel() != N or tuple(cls.shape) not in ((N,), (B, S)):
-        raise ValueError(f"nms3d: cls must be int32 of shape ({B}, {S}) or ({N},), got {cls.dtype} {tuple(cls.shape)}")
+    B, _, S = _slot_table("nms3d", count, verts, scores, cls)
     L = _dev(verts, scores, cls, count)
     iou = _empty((B, S, S), torch.float32, verts)
     keep = _empty((B, S), torch.int32, verts)
@@ -472,17 +478,7 @@ def fuse3d(verts, scores, cls, count, iou_thr, views=1, aux=None, class_agnostic
     (B*S, 3), axes (B*S, 3, 3), dims (B*S, 3), score (B*S,), cls (B*S,) int32, aux (B*S, A), size (B*S,) int32 members, head (B*S,) int32
     head slot, count (B,) int32 clusters per image, cluster (B, S) int32 head slot of every slot, iou (B, S, S), invalid (1,) int32.
     Rows of one image come in descending fused score and are zero (head -1) behind its count.  Two launches, no host synchronisation."""
-    if count.dim() != 1 or count.dtype != torch.int32:
-        raise ValueError(f"fuse3d: count must be int32 of shape (B,), got {count.dtype} {tuple(count.shape)}")
-    B = count.shape[0]
-    if verts.dim() != 3 or tuple(verts.shape[1:]) != (8, 3) or verts.dtype != torch.float32 or (B and verts.shape[0] % B) or (not B and verts.shape[0]):
-        raise ValueError(f"fuse3d: verts must be float32 of shape (B*S, 8, 3) for B = {B}, got {verts.dtype} {tuple(verts.shape)}")
-    N = verts.shape[0]
-    S = N // B if B else 0
-    if scores.dtype != torch.float32 or tuple(scores.shape) != (N,):
-        raise ValueError(f"fuse3d: scores must be float32 of shape ({N},), got {scores.dtype} {tuple(scores.shape)}")
-    if cls.dtype != torch.int32 or cls.numel() != N or tuple(cls.shape) not in ((N,), (B, S)):
-        raise ValueError(f"fuse3d: cls must be int32 of shape ({B}, {S}) or ({N},), got {cls.dtype} {tuple(cls.shape)}")
+    B, N, S = _slot_table("fuse3d", count, verts, scores, cls)
     if int(views) != views or views < 1:
         raise ValueError(f"fuse3d: views must be an integer >= 1, got {views!r}")
     if aux is not None and (aux.dim() != 2 or aux.shape[0] != N or aux.dtype != torch.float32):

@@ -1,12 +1,12 @@
 """Launcher of csrc/eval_errors.hip: the error type of every detection and the Miss flag of every ground truth of a data set, after
-TIDE (Bolya et al., ECCV 2020).  The reference has no counterpart; the interface follows `kernels/bootstrap.py`.  `Omni3Deval.errors`
+TIDE (Bolya et al., ECCV 2020).  The reference has no counterpart; the arguments are checked by `kernels/_args.py`.  `Omni3Deval.errors`
 documents the definitions in full; the codes are the constants below.
 """
 import numpy as np
 import torch
 
 from .. import lib as _lib
-from .tperr import _check
+from . import _args
 
 TP, IGN, CLS, LOC, BOTH, DUPE, BKG = range(7)          # the codes of `type`
 FP_TYPES = (CLS, LOC, BOTH, DUPE, BKG)                 # the false-positive codes, in TIDE's order
@@ -22,24 +22,18 @@ def error_types(sim, dt_off, gt_off, dt_cat, dt_matched, dt_ignore, dt_score, gt
     dt_score (sumD,) float64; gt_cat (sumG,) int32, gt_matched / gt_ignore (sumG,) uint8: the outcome of the greedy matching at one
     (range, threshold); 0 < t_bg < t_fg.  ValueError on a wrong argument, and on an image with more than MAX_GT ground truths, before
     anything is launched: nothing is truncated.  One launch; two calls give the same bits."""
-    for name, o in (("dt_off", dt_off), ("gt_off", gt_off)):
-        _check(o, name, torch.int32, (o.numel() if isinstance(o, torch.Tensor) else 0,))
-    if dt_off.numel() < 1 or dt_off.numel() != gt_off.numel():
+    do, go = np.asarray(_args.offsets(dt_off, "dt_off"), np.int64), np.asarray(_args.offsets(gt_off, "gt_off"), np.int64)
+    if len(do) != len(go):
         raise ValueError("dt_off / gt_off must hold I + 1 offsets each")
-    I = dt_off.numel() - 1
-    do, go = np.asarray(dt_off.tolist(), np.int64), np.asarray(gt_off.tolist(), np.int64)
-    if do[0] != 0 or go[0] != 0 or (np.diff(do) < 0).any() or (np.diff(go) < 0).any():
-        raise ValueError("dt_off / gt_off must ascend from 0")
+    I = len(do) - 1
     sumD, sumG = int(do[-1]), int(go[-1])
-    _check(dt_cat, "dt_cat", torch.int32, (sumD,))
-    _check(dt_matched, "dt_matched", torch.uint8, (sumD,))
-    _check(dt_ignore, "dt_ignore", torch.uint8, (sumD,))
-    _check(dt_score, "dt_score", torch.float64, (sumD,))
-    _check(gt_cat, "gt_cat", torch.int32, (sumG,))
-    _check(gt_matched, "gt_matched", torch.uint8, (sumG,))
-    _check(gt_ignore, "gt_ignore", torch.uint8, (sumG,))
+    for t, name, dtype, n in ((dt_cat, "dt_cat", torch.int32, sumD), (dt_matched, "dt_matched", torch.uint8, sumD),
+                              (dt_ignore, "dt_ignore", torch.uint8, sumD), (dt_score, "dt_score", torch.float64, sumD),
+                              (gt_cat, "gt_cat", torch.int32, sumG), (gt_matched, "gt_matched", torch.uint8, sumG),
+                              (gt_ignore, "gt_ignore", torch.uint8, sumG)):
+        _args.tensor(t, name, dtype, (n,))
     sim_off = np.concatenate([[0], np.cumsum(np.diff(do) * np.diff(go))]).astype(np.int64)
-    _check(sim, "sim", torch.float32, (int(sim_off[-1]),))
+    _args.tensor(sim, "sim", torch.float32, (int(sim_off[-1]),))
     t_fg, t_bg = float(t_fg), float(t_bg)
     if not 0.0 < t_bg < t_fg:
         raise ValueError("the thresholds must satisfy 0 < t_bg < t_fg")
@@ -47,8 +41,7 @@ def error_types(sim, dt_off, gt_off, dt_cat, dt_matched, dt_ignore, dt_score, gt
     if max_gt > MAX_GT:
         raise ValueError("an image holds %d ground truths, the capacity is %d" % (max_gt, MAX_GT))
     tensors = (sim, dt_off, gt_off, dt_cat, dt_matched, dt_ignore, dt_score, gt_cat, gt_matched, gt_ignore)
-    if len({t.device for t in tensors}) != 1:
-        raise ValueError("all inputs must live on one device")
+    _args.one_device(tensors)
     L = _lib.check_device(*tensors)
     dev = sim.device
     out = {"type": torch.empty(sumD, dtype=torch.int8, device=dev), "attr": torch.empty(sumD, dtype=torch.int32, device=dev),

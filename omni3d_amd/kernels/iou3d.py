@@ -6,10 +6,8 @@
 import torch
 
 from .. import lib as _lib
-
-
-def _empty(shape, dtype, like):
-    return torch.empty(shape, dtype=dtype, device=like.device)
+from . import _args
+from ._args import empty as _empty      # a name of this module: the tests poison the outputs through it
 
 
 def _check_boxes(b, name):
@@ -95,18 +93,11 @@ def cuboid_fit(boxes, eps_dim=1e-8, fit_tol=1e-3, counts=None):
     dimension is <= eps_dim, or a vertex lies further than fit_tol x the largest dimension from its fitted corner.  counts: optional
     int32 (1,) tensor the number of invalid boxes is added to.  ValueError on a wrong shape / dtype / stride / argument before
     anything is launched; N == 0 launches nothing."""
-    if not isinstance(boxes, torch.Tensor):
-        raise ValueError("boxes must be a tensor")
-    _check_boxes(boxes, "boxes")
-    if not boxes.is_contiguous():
-        raise ValueError("boxes must be contiguous")
+    N = _args.corners(boxes, "boxes")
     if not float(eps_dim) >= 0.0 or not float(fit_tol) >= 0.0 or float(eps_dim) == float("inf") or float(fit_tol) == float("inf"):
         raise ValueError("eps_dim and fit_tol must be finite and >= 0")
-    if counts is not None and (not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.numel() != 1
-                               or counts.device != boxes.device):
-        raise ValueError("counts must be one int32 on the boxes' device")
+    _args.counter(counts, boxes)
     L = _lib.check_device(boxes, counts)
-    N = boxes.shape[0]
     centre, axes, dims = _empty((N, 3), torch.float64, boxes), _empty((N, 3, 3), torch.float64, boxes), _empty((N, 3), torch.float64, boxes)
     valid = _empty((N,), torch.int32, boxes)
     if N > 0:
@@ -115,35 +106,22 @@ def cuboid_fit(boxes, eps_dim=1e-8, fit_tol=1e-3, counts=None):
     return centre, axes, dims, valid
 
 
-def _check_fit(fit, name):
-    if not isinstance(fit, (tuple, list)) or len(fit) != 4 or not all(isinstance(t, torch.Tensor) for t in fit):
-        raise ValueError(f"{name} must be the (centre, axes, dims, valid) of cuboid_fit")
-    centre, axes, dims, valid = fit
-    n = centre.shape[0] if centre.dim() else -1
-    for t, shape in ((centre, (n, 3)), (axes, (n, 3, 3)), (dims, (n, 3))):
-        if tuple(t.shape) != shape or t.dtype != torch.float64:
-            raise ValueError(f"{name}: expected float64 of shape {shape}, got {t.dtype} {tuple(t.shape)}")
-    if tuple(valid.shape) != (n,) or valid.dtype != torch.int32:
-        raise ValueError(f"{name}: valid must be int32 of shape ({n},)")
-    if not all(t.is_contiguous() for t in fit):
-        raise ValueError(f"{name} must be contiguous")
-    return n
+FIT = (("centre", torch.float64, (3,)), ("axes", torch.float64, (3, 3)), ("dims", torch.float64, (3,)), ("valid", torch.int32, ()))
+
+
+def check_fit(fit, name):
+    """fit is the tuple of `cuboid_fit`, contiguous -> its number of boxes; ValueError otherwise"""
+    return _args.box_set(fit, name, "cuboid_fit", FIT)
 
 
 def iou_fitted_pairs(fit1, fit2, idx1, idx2):
     """(vol, iou), each (P,) float32: the exact intersection volume and IoU3D of fitted cuboid idx1[p] of fit1 and idx2[p] of fit2
     (the tuples of `cuboid_fit`).  idx1 / idx2: 1-D int32 or int64 tensors of equal length.  Exactly 0 for a pair with an invalid box,
     an index outside its set or disjoint bounding spheres; never NaN; two calls give the same bits; P == 0 launches nothing."""
-    n1, n2 = _check_fit(fit1, "fit1"), _check_fit(fit2, "fit2")
-    for i in (idx1, idx2):
-        if not isinstance(i, torch.Tensor) or i.dim() != 1 or i.dtype not in (torch.int32, torch.int64):
-            raise ValueError("idx1 / idx2 must be 1-D int32 or int64 tensors")
-    if idx1.shape != idx2.shape:
-        raise ValueError("idx1 / idx2 must be of equal length")
+    n1, n2 = check_fit(fit1, "fit1"), check_fit(fit2, "fit2")
     tensors = (*fit1, *fit2, idx1, idx2)
-    if len({t.device for t in tensors}) != 1:
-        raise ValueError("all inputs must live on one device")
-    idx1, idx2 = idx1.to(torch.int32).contiguous(), idx2.to(torch.int32).contiguous()
+    idx1, idx2 = _args.pair_index(idx1, idx2)
+    _args.one_device(tensors)
     L = _lib.check_device(*tensors)
     P = idx1.numel()
     vol, iou = _empty((P,), torch.float32, idx1), _empty((P,), torch.float32, idx1)
@@ -163,10 +141,8 @@ def iou_box3d_exact(boxes1, boxes2, eps_dim=1e-8, fit_tol=1e-3):
     fitted to the corners (`cuboid_fit`), right whatever the relative pose of the two boxes.  The rows and columns of invalid boxes
     are exactly 0."""
     fit1, fit2 = cuboid_fit(boxes1, eps_dim, fit_tol), cuboid_fit(boxes2, eps_dim, fit_tol)
-    N, M, dev = boxes1.shape[0], boxes2.shape[0], boxes1.device
-    idx1 = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(M)
-    idx2 = torch.arange(M, dtype=torch.int32, device=dev).repeat(N)
-    vol, iou = iou_fitted_pairs(fit1, fit2, idx1, idx2)
+    N, M = boxes1.shape[0], boxes2.shape[0]
+    vol, iou = iou_fitted_pairs(fit1, fit2, *_args.all_pairs(N, M, boxes1.device))
     return vol.view(N, M), iou.view(N, M)
 
 

@@ -1,6 +1,6 @@
 """Launchers of csrc/eval_kitti.hip: the KITTI object benchmark's protocol (AP|R40 / AP|R11 per class, difficulty, metric and overlap
 set) for `cubercnn.evaluation.kitti.KittiEval`.  The reference has no counterpart; the protocol is stated in include/omni3d_hip.h and,
-in float64, in tests/exact_kitti.py.  The interface follows `kernels/accumulate.py`: device tensors in, device tensors out.
+in float64, in tests/exact_kitti.py.  Device tensors in, device tensors out; the tensor arguments are checked by `kernels/_args.py`.
 
 A `Problem` holds one packed data set (per-image row ranges, per-row quantities, the similarity matrices and the small tables);
 `match_tp`, `thresholds`, `match_counts` and `finalize` are the four launches and `run` chains them without a host round trip.
@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import lib as _lib
+from . import _args
 
 MAX_ROWS = 1024            # detections / ground-truth rows of one image (csrc/eval_kitti.hip)
 MAX_PTS = 64
@@ -25,6 +26,12 @@ def _offsets(sizes, name):
     if (sizes < 0).any():
         raise ValueError(f"{name} must not be negative")
     return sizes, np.concatenate([[0], np.cumsum(sizes)])
+
+
+def _on_device(t, name, dtype, shape, dev):
+    _args.shaped(t, name, dtype, shape)
+    if t.device != dev:
+        raise ValueError(f"{name} must be on {dev}")
 
 
 class Problem:
@@ -60,15 +67,13 @@ class Problem:
         self.S = self.C * self.Dn * self.M * self.O
         sim_off, dc_pair_off = np.concatenate([[0], np.cumsum(dt_sizes * gt_sizes)]), np.concatenate([[0], np.cumsum(dt_sizes * dc_sizes)])
         self.P = int(sim_off[-1])
-        if not isinstance(sim, torch.Tensor) or sim.dtype != torch.float32 or tuple(sim.shape) != (self.M, self.P):
-            raise ValueError(f"sim must be float32 of shape ({self.M}, {self.P})")
+        _args.shaped(sim, "sim", torch.float32, (self.M, self.P))
         dev = self.device = sim.device
         for t, name, dtype, n in ((dc_ov, "dc_ov", torch.float32, int(dc_pair_off[-1])), (dt_code, "dt_code", torch.int32, self.sumD),
                                   (dt_height, "dt_height", torch.float64, self.sumD), (dt_score, "dt_score", torch.float64, self.sumD),
                                   (gt_code, "gt_code", torch.int32, self.sumG), (gt_height, "gt_height", torch.float64, self.sumG),
                                   (gt_occ, "gt_occ", torch.int32, self.sumG), (gt_trunc, "gt_trunc", torch.float64, self.sumG)):
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != (n,) or t.device != dev:
-                raise ValueError(f"{name} must be {dtype} of shape ({n},) on {dev}")
+            _on_device(t, name, dtype, (n,), dev)
         self.rows = (dt_code, dt_height, dt_score, gt_code, gt_height, gt_occ, gt_trunc)
         self.sim, self.dc_ov = sim, dc_ov
         self.lib = _lib.check_device(sim, dc_ov, *self.rows)
@@ -152,9 +157,8 @@ def _check_aos(pb, dt_alpha, gt_alpha, aos_metric):
     """the argument check of the AOS launches -> aos_metric as a host int32 array; ValueError before anything is allocated or launched"""
     if pb.sumG >= AOS_MAX_ROWS:
         raise ValueError(f"{pb.sumG} ground-truth rows: the fixed-point orientation sum takes fewer than 2^23")
-    for t, name, n in ((dt_alpha, "dt_alpha", pb.sumD), (gt_alpha, "gt_alpha", pb.sumG)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != (n,) or t.device != pb.device:
-            raise ValueError(f"{name} must be {torch.float64} of shape ({n},) on {pb.device}")
+    _on_device(dt_alpha, "dt_alpha", torch.float64, (pb.sumD,), pb.device)
+    _on_device(gt_alpha, "gt_alpha", torch.float64, (pb.sumG,), pb.device)
     aos_metric = np.asarray(aos_metric).astype(np.int32).reshape(-1)
     if len(aos_metric) != pb.M:
         raise ValueError(f"aos_metric must hold one value per metric ({pb.M})")
@@ -186,8 +190,7 @@ def finalize_aos(pb, counts, sim_sum, K, aos_metric, out=None):
     aos_metric = np.asarray(aos_metric).astype(np.int32).reshape(-1)
     if len(aos_metric) != pb.M:
         raise ValueError(f"aos_metric must hold one value per metric ({pb.M})")
-    if not isinstance(sim_sum, torch.Tensor) or sim_sum.dtype != torch.int64 or tuple(sim_sum.shape) != (pb.S, npts) or sim_sum.device != counts.device:
-        raise ValueError(f"sim_sum must be int64 of shape ({pb.S}, {npts}) on {counts.device}")
+    _on_device(sim_sum, "sim_sum", torch.int64, (pb.S, npts), counts.device)
     aos, aos_ap = out if out is not None else (torch.empty((pb.S, npts), dtype=torch.float64, device=pb.device),
                                                torch.empty((pb.S, 2), dtype=torch.float64, device=pb.device))
     metric = torch.from_numpy(aos_metric).to(pb.device)
@@ -216,9 +219,7 @@ UP = (0.0, -1.0, 0.0)              # camera y points down
 def check_up(up):
     """-> the up vector as three floats; ValueError for one that is not three finite numbers, of zero length or parallel to camera x
     (the ground-plane axis a = camera x less its part along up would vanish)"""
-    u = np.asarray(up, dtype=np.float64).reshape(-1)
-    if u.shape != (3,) or not np.isfinite(u).all() or not np.linalg.norm(u) > 0:
-        raise ValueError("up must be three finite numbers, not all zero")
+    u = _args.up_vector(up)
     n = u / np.linalg.norm(u)
     if not np.linalg.norm(np.array([1.0, 0.0, 0.0]) - n[0] * n) > 1e-12:
         raise ValueError("up must not be parallel to camera x: the heading is measured from camera x in the ground plane")
@@ -232,13 +233,9 @@ def box_params(corners, up=UP):
     a = camera x, b = camera z), which is KITTI's rotation_y for R = Ry(ry); a heading without a ground-plane component gives
     atan2(0, 0) = 0.  alpha = rotation_y - atan2(c.a, c.b) in (-pi, pi].  valid = 0, and NaN elsewhere, for a box with a non-finite
     corner or a zero edge.  One launch; N == 0 launches nothing."""
-    if not isinstance(corners, torch.Tensor) or corners.dtype != torch.float32 or corners.dim() != 3 or tuple(corners.shape[1:]) != (8, 3):
-        raise ValueError("corners must be a float32 tensor of shape (N, 8, 3)")
-    if not corners.is_contiguous():
-        raise ValueError("corners must be contiguous")
+    n = _args.corners(corners, "corners")
     up = check_up(up)
     L = _lib.check_device(corners)
-    n = corners.shape[0]
     out = torch.empty((n, 9), dtype=torch.float64, device=corners.device)
     if n > 0:
         L.call("omni_kitti_box_params", _lib.ptr(corners), n, *up, _lib.ptr(out), _lib.stream_of(corners))

@@ -1,6 +1,6 @@
 """Launchers of csrc/let_iou.hip: the longitudinal-error-tolerant IoU3D of a detection and a ground truth, and the longitudinal
 precision along the recall curve (LET-3D-AP / LET-3D-APL, Hung et al. 2022, the camera-only metric of the Waymo Open Dataset).  The
-reference has no counterpart; the interface follows `kernels/tperr.py`: a box set is the tuple ``(centre, axes, dims, valid)`` of
+reference has no counterpart; the arguments are checked by `kernels/_args.py`: a box set is the tuple ``(centre, axes, dims, valid)`` of
 `iou3d.cuboid_fit`, box 1 = detection (fitted centre P), box 2 = ground truth (fitted centre G), the sensor at the origin.
 
 Of a pair:
@@ -15,8 +15,9 @@ import math
 import torch
 
 from .. import lib as _lib
-from .iou3d import _check_fit, cuboid_fit
-from .tperr import _check, _empty
+from . import _args
+from ._args import empty as _empty      # a name of this module: the tests poison the outputs through it
+from .iou3d import check_fit, cuboid_fit
 
 TOL_FRAC, TOL_MIN = 0.1, 0.5       # Waymo's values: a convention, not tuned here
 
@@ -39,17 +40,11 @@ def let_pairs(fit1, fit2, idx1, idx2, tol_frac=TOL_FRAC, tol_min=TOL_MIN):
     of fit2 (the tuples of `cuboid_fit`).  idx1 / idx2: 1-D int32 or int64 tensors of equal length.  (0, 0, NaN) for a gated pair;
     NaN never leaves through iou or aff; two calls give the same bits; P == 0 launches nothing.  ValueError on a wrong argument
     before anything is launched."""
-    n1, n2 = _check_fit(fit1, "fit1"), _check_fit(fit2, "fit2")
-    for i in (idx1, idx2):
-        if not isinstance(i, torch.Tensor) or i.dim() != 1 or i.dtype not in (torch.int32, torch.int64):
-            raise ValueError("idx1 / idx2 must be 1-D int32 or int64 tensors")
-    if idx1.shape != idx2.shape:
-        raise ValueError("idx1 / idx2 must be of equal length")
-    tol_frac, tol_min = check_tolerance(tol_frac, tol_min)
+    n1, n2 = check_fit(fit1, "fit1"), check_fit(fit2, "fit2")
     tensors = (*fit1, *fit2, idx1, idx2)
-    if len({t.device for t in tensors}) != 1:
-        raise ValueError("all inputs must live on one device")
-    idx1, idx2 = idx1.to(torch.int32).contiguous(), idx2.to(torch.int32).contiguous()
+    idx1, idx2 = _args.pair_index(idx1, idx2)
+    tol_frac, tol_min = check_tolerance(tol_frac, tol_min)
+    _args.one_device(tensors)
     L = _lib.check_device(*tensors)
     P = idx1.numel()
     iou, aff, lon = _empty((P,), torch.float32, idx1), _empty((P,), torch.float64, idx1), _empty((P,), torch.float64, idx1)
@@ -64,10 +59,8 @@ def box3d_let(boxes_dt, boxes_gt, tol_frac=TOL_FRAC, tol_min=TOL_MIN):
     fitted by `cuboid_fit` with its default eps_dim and fit_tol; the rows and columns of invalid boxes are (0, 0, NaN)."""
     check_tolerance(tol_frac, tol_min)
     fit1, fit2 = cuboid_fit(boxes_dt), cuboid_fit(boxes_gt)
-    N, M, dev = boxes_dt.shape[0], boxes_gt.shape[0], boxes_dt.device
-    idx1 = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(M)
-    idx2 = torch.arange(M, dtype=torch.int32, device=dev).repeat(N)
-    iou, aff, lon = let_pairs(fit1, fit2, idx1, idx2, tol_frac, tol_min)
+    N, M = boxes_dt.shape[0], boxes_gt.shape[0]
+    iou, aff, lon = let_pairs(fit1, fit2, *_args.all_pairs(N, M, boxes_dt.device), tol_frac, tol_min)
     return iou.view(N, M), aff.view(N, M), lon.view(N, M)
 
 
@@ -85,41 +78,18 @@ def accumulate_let(order, cat_off, rank, dt_match, dt_ignore, pair_row, aff, lon
     precision_l is prec_L made monotone from the right and sampled at rec_thrs as `precision` is, -1 in the same cells (npig == 0 or
     has_e == 0); tp_affinity / tp_lon are the means of aff / lon over the true positives, -1 without one.  Two calls give the same
     bits."""
-    _check(cat_off, "cat_off", torch.int32, (cat_off.numel() if isinstance(cat_off, torch.Tensor) else 0,))
-    K = cat_off.numel() - 1
-    if K < 0:
-        raise ValueError("cat_off must hold K + 1 offsets")
-    _check(order, "order", torch.int32, (order.numel() if isinstance(order, torch.Tensor) else 0,))
-    if not isinstance(dt_match, torch.Tensor) or dt_match.dim() != 3 or dt_match.shape[0] < 1 or dt_match.shape[1] < 1:
-        raise ValueError("dt_match must have shape (A, T, sumD) with A >= 1 and T >= 1")
-    A, T, sumD = dt_match.shape
-    _check(dt_match, "dt_match", torch.int32, (A, T, sumD))
-    _check(dt_ignore, "dt_ignore", torch.uint8, (A, T, sumD))
-    _check(rank, "rank", torch.int32, (sumD,))
-    _check(pair_row, "pair_row", torch.int64, (sumD,))
-    if not isinstance(aff, torch.Tensor) or aff.dim() != 1:
-        raise ValueError("aff must have shape (P,)")
-    P = aff.shape[0]
-    _check(aff, "aff", torch.float64, (P,))
-    _check(lon, "lon", torch.float64, (P,))
-    _check(npig, "npig", torch.int32, (K, A))
-    _check(has_e, "has_e", torch.int32, (K,))
-    if not isinstance(rec_thrs, torch.Tensor) or rec_thrs.dim() != 1 or rec_thrs.numel() < 1:
-        raise ValueError("rec_thrs must be 1-D and not empty")
-    _check(rec_thrs, "rec_thrs", torch.float64, (rec_thrs.numel(),))
-    if not isinstance(max_dets, torch.Tensor) or max_dets.dim() != 1 or max_dets.numel() < 1:
-        raise ValueError("max_dets must be 1-D and not empty")
-    _check(max_dets, "max_dets", torch.int32, (max_dets.numel(),))
+    K, A, T, R, sumD, _ = _args.merge_order(order, cat_off, dt_match, dt_ignore, rec_thrs)
+    _args.tensor(rank, "rank", torch.int32, (sumD,))
+    _args.tensor(pair_row, "pair_row", torch.int64, (sumD,))
+    P = _args.tensor(aff, "aff", torch.float64, (None,))[0]
+    _args.tensor(lon, "lon", torch.float64, (P,))
+    _args.tensor(npig, "npig", torch.int32, (K, A))
+    _args.tensor(has_e, "has_e", torch.int32, (K,))
+    M = _args.nonempty(max_dets, "max_dets", torch.int32)
     tensors = (order, cat_off, rank, dt_match, dt_ignore, pair_row, aff, lon, npig, has_e, rec_thrs, max_dets)
-    if len({t.device for t in tensors}) != 1:
-        raise ValueError("all inputs must live on one device")
-    off = cat_off.tolist()
-    if off[0] != 0 or off[-1] != order.numel() or any(b < a for a, b in zip(off, off[1:])):
-        raise ValueError("cat_off must ascend from 0 to len(order)")
-    if order.numel() and (int(order.min()) < 0 or int(order.max()) >= sumD):
-        raise ValueError("order must index the sumD detections")
+    _args.one_device(tensors)
     L = _lib.check_device(*tensors)
-    R, M, dev = rec_thrs.numel(), max_dets.numel(), order.device
+    dev = order.device
     prec_l = torch.full((T, R, K, A, M), -1.0, dtype=torch.float64, device=dev)
     tp_aff = torch.full((T, K, A, M), -1.0, dtype=torch.float64, device=dev)
     tp_lon = torch.full((T, K, A, M), -1.0, dtype=torch.float64, device=dev)

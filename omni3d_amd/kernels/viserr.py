@@ -1,29 +1,13 @@
 """Launcher of csrc/vis_errors.hip: the 3D error report of `visualize_from_instances` (reference cubercnn/vis/vis.py:95-171)
 for all predictions of a dataset in one call -- the 2D-IoU match of every prediction to the ground truth of its image and category
-and the seven errors of the matched pairs, summed in a fixed order.
+and the seven errors of the matched pairs, summed in a fixed order.  The arguments are checked by `kernels/_args.py`.
 """
 import torch
 
 from .. import lib as _lib
+from . import _args
 
 ERR_NAMES = ("xy", "z", "w", "h", "l", "dim", "ry")
-
-
-def _check(t, dtype, shape, name):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
-        raise ValueError(f"{name} must be a {dtype} tensor")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    return t
-
-
-def _check_offsets(off, images, rows, name):
-    _check(off, torch.int32, (images + 1,), name)
-    o = off.cpu()
-    if int(o[0]) != 0 or int(o[-1]) != rows or bool((o[1:] < o[:-1]).any()):
-        raise ValueError(f"{name} must start at 0, never decrease and end at {rows}")
 
 
 def match_errors(dt_box, dt_cat, dt_c2d, dt_z, dt_dims, dt_pose, dt_off, gt_box, gt_cat, gt_center, gt_dims, gt_pose, gt_off, K):
@@ -37,23 +21,20 @@ def match_errors(dt_box, dt_cat, dt_c2d, dt_z, dt_dims, dt_pose, dt_off, gt_box,
     not a measured parity): pi / 2 - (trace(R_dt R_gt^T) - 1) / 2, and NaN / not counted where the trace lies outside
     [-1 - 1e-4, 3 + 1e-4], where pytorch3d raises and the reference skips the pair for ry only."""
     f32, i32 = torch.float32, torch.int32
-    if not isinstance(dt_off, torch.Tensor) or dt_off.dim() != 1 or dt_off.numel() < 1:
-        raise ValueError("dt_off must be a (I + 1,) int32 tensor")
-    I = dt_off.numel() - 1
-    D = dt_box.shape[0] if isinstance(dt_box, torch.Tensor) and dt_box.dim() else -1
-    G = gt_box.shape[0] if isinstance(gt_box, torch.Tensor) and gt_box.dim() else -1
-    for t, shape, name in ((dt_box, (D, 4), "dt_box"), (dt_c2d, (D, 2), "dt_c2d"), (dt_z, (D,), "dt_z"), (dt_dims, (D, 3), "dt_dims"),
-                           (gt_box, (G, 4), "gt_box"), (gt_center, (G, 3), "gt_center"), (gt_dims, (G, 3), "gt_dims")):
-        _check(t, f32, shape, name)
-    _check(dt_cat, i32, (D,), "dt_cat")
-    _check(gt_cat, i32, (G,), "gt_cat")
+    I = _args.offset_count(dt_off, "dt_off")
+    D = _args.tensor(dt_box, "dt_box", f32, (None, 4))[0]
+    G = _args.tensor(gt_box, "gt_box", f32, (None, 4))[0]
+    for t, name, shape in ((dt_c2d, "dt_c2d", (D, 2)), (dt_z, "dt_z", (D,)), (dt_dims, "dt_dims", (D, 3)), (gt_center, "gt_center", (G, 3)),
+                           (gt_dims, "gt_dims", (G, 3))):
+        _args.tensor(t, name, f32, shape)
+    _args.tensor(dt_cat, "dt_cat", i32, (D,))
+    _args.tensor(gt_cat, "gt_cat", i32, (G,))
     for t, n, name in ((dt_pose, D, "dt_pose"), (gt_pose, G, "gt_pose"), (K, I, "K")):
-        _check(t, f32, (n, 3, 3) if isinstance(t, torch.Tensor) and t.dim() == 3 else (n, 9), name)
-    _check_offsets(dt_off, I, D, "dt_off")
-    _check_offsets(gt_off, I, G, "gt_off")
+        _args.matrices(t, n, name)
+    _args.offsets(dt_off, "dt_off", D)
+    _args.offsets(gt_off, "gt_off", G, count=I)
     tensors = (dt_box, dt_cat, dt_c2d, dt_z, dt_dims, dt_pose, dt_off, gt_box, gt_cat, gt_center, gt_dims, gt_pose, gt_off, K)
-    if len({t.device for t in tensors}) != 1:
-        raise ValueError("all inputs must live on one device")
+    _args.one_device(tensors)
     L = _lib.check_device(*tensors)
     dev = dt_box.device
     match = torch.empty(D, dtype=i32, device=dev)
