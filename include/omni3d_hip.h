@@ -758,6 +758,28 @@ int omni_det_compact(const int* keep, const int* valid, const float* vals, const
 int omni_resize_bilinear_u8(const unsigned char* src, unsigned char* dst, unsigned char* tmp, int planes, int H, int W,
                             int HO, int WO, const int* bounds_h, const int* kk_h, int ksize_h, const int* bounds_v,
                             const int* kk_v, int ksize_v, int flip, void* stream);
+/* Training augmentations (csrc/augment.hip): INPUT.CROP and INPUT.COLOR_JITTER.
+ * omni_pil_bilinear_coeffs: the tables above for in_size -> out_size, built on the device, one thread per output index: the double
+ * arithmetic of kernels/resize.py::pil_bilinear_coeffs in its order, contraction off -- bit-equal to it for every size pair.  The
+ * whole ksize row is written, zeros included.  ksize must be 2 * ceil(max(in_size / out_size, 1)) + 1, else OMNI_ERR_ARG. */
+int omni_pil_bilinear_coeffs(int in_size, int out_size, int* bounds, int* kk, int ksize, void* stream);
+/* omni_resize_bilinear_u8 of the window src[:, y0:y0+ch, x0:x0+cw] of the full (planes, H, W) image -> dst (planes, HO, WO), read
+ * in place through the image's pitch: no copy of the window, nothing outside it is read.  tmp = planes*ch*WO bytes; the tables are
+ * those of (cw -> WO) and (ch -> HO).  ch == HO skips the vertical pass, cw == WO the horizontal one; an identity size is a windowed
+ * mirror (flip) or a windowed copy kernel.  A window not inside [0, W) x [0, H) or a non-positive extent returns OMNI_ERR_ARG
+ * before any launch. */
+int omni_crop_resize_u8(const unsigned char* src, unsigned char* dst, unsigned char* tmp, int planes, int H, int W, int x0, int y0,
+                        int ch, int cw, int HO, int WO, const int* bounds_h, const int* kk_h, int ksize_h, const int* bounds_v,
+                        const int* kk_v, int ksize_v, int flip, void* stream);
+/* Brightness, contrast and saturation of a (3, H, W) image in place, in integers: weights wb / wc / ws with 12 fractional bits
+ * (4096 = 1.0), each in [0, 16384] else OMNI_ERR_ARG; c_red = plane of red (0 RGB, 2 BGR), green is plane 1.  >> is arithmetic,
+ * clamp is to [0, 255]:
+ *   v1 = clamp((wb*v + 2048) >> 12)
+ *   S = sum of v1 over the N = 3*H*W values, M8 = (256*S + N/2) / N;  v2 = clamp((wc*256*v1 + (4096-wc)*M8 + 2^19) >> 20)
+ *   g8 = 77*R2 + 150*G2 + 29*B2;                                      v3 = clamp((ws*256*v2 + (4096-ws)*g8 + 2^19) >> 20)
+ * A weight of 4096 is the identity; all three at 4096 launch nothing.  sum: one device unsigned long long, zeroed and filled here
+ * when wc != 4096 (one 64-bit integer atomic per workgroup, same bits every run) and read by the apply pass on the device. */
+int omni_color_jitter_u8(unsigned char* img, int H, int W, int wb, int wc, int ws, int c_red, unsigned long long* sum, void* stream);
 
 /* ---------------------------------------------------------------------------- optimizer */
 

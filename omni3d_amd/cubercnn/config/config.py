@@ -374,6 +374,44 @@ def tta_args(cfg):
             "class_agnostic": bool(get("CLASS_AGNOSTIC"))}
 
 
+_COLOR_JITTER = {"ENABLED": False, "BRIGHTNESS": [0.8, 1.2], "CONTRAST": [0.8, 1.2], "SATURATION": [0.8, 1.2]}
+
+
+def add_color_jitter_config(cfg):
+    """INPUT.COLOR_JITTER.*: photometric augmentation of the training images (`DatasetMapper3D`, csrc/augment.hip,
+    omni_color_jitter_u8): a brightness, a contrast and a saturation weight are drawn uniformly from their [low, high] interval for
+    every image and applied, in that order, by the integer definition of include/omni3d_hip.h.  Neither detectron2's defaults nor the
+    reference define the node, so, as with `add_bev_eval_config`, it is absent until this call; without it nothing is jittered.
+    Idempotent: values already set are kept.  An interval of [1, 1] switches its step off and draws nothing.
+    The intervals [0.8, 1.2] are conventions (the mild setting detection code bases commonly ship), not tuned values; their effect
+    on AP has not been measured."""
+    if "COLOR_JITTER" not in cfg.INPUT:
+        cfg.INPUT.COLOR_JITTER = CN()
+    for key, value in _COLOR_JITTER.items():
+        cfg.INPUT.COLOR_JITTER.setdefault(key, list(value) if isinstance(value, list) else value)
+    return cfg
+
+
+def color_jitter_args(cfg):
+    """INPUT.COLOR_JITTER -> {"enabled", "brightness", "contrast", "saturation"}, the intervals as (low, high) floats;
+    `DatasetMapper3D` reads them through this.  A cfg without the node: the feature off.  ValueError unless every interval is two
+    finite numbers with 0 <= low <= high <= 4 (4 is the largest weight the kernel's 32-bit arithmetic is shown to hold)."""
+    import math
+    node = cfg.INPUT.get("COLOR_JITTER")
+    have = dict(node) if node is not None else {}
+    out = {"enabled": bool(have.get("ENABLED", False))}
+    for key in ("BRIGHTNESS", "CONTRAST", "SATURATION"):
+        iv = have.get(key, _COLOR_JITTER[key])
+        if isinstance(iv, (str, bytes)) or not hasattr(iv, "__len__") or len(iv) != 2 or any(
+                isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) for v in iv):
+            raise ValueError(f"INPUT.COLOR_JITTER.{key} must be two numbers [low, high], got {iv!r}")
+        lo, hi = float(iv[0]), float(iv[1])
+        if not 0.0 <= lo <= hi <= 4.0:
+            raise ValueError(f"INPUT.COLOR_JITTER.{key} must satisfy 0 <= low <= high <= 4, got {iv!r}")
+        out[key.lower()] = (lo, hi)
+    return out
+
+
 def build_tta_model(cfg, model):
     """the model wrapped for test-time augmentation when TEST.AUG.ENABLED, else the model itself"""
     if not tta_args(cfg)["enabled"]:

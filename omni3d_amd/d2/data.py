@@ -1,5 +1,6 @@
 """detectron2.data plumbing: DatasetCatalog / MetadataCatalog registries and the two transforms the reference's mapper uses
-(ResizeShortestEdge, RandomFlip) with detectron2's parameter sampling and coordinate rules."""
+(ResizeShortestEdge, RandomFlip) with detectron2's parameter sampling and coordinate rules, and RandomCrop (INPUT.CROP), which
+detectron2's mapper puts in front of them."""
 import types
 
 import numpy as np
@@ -74,6 +75,18 @@ class HFlipTransform:
         return coords
 
 
+class CropTransform:
+    """detectron2 CropTransform: the window [x0, x0 + w) x [y0, y0 + h) becomes the image"""
+
+    def __init__(self, x0, y0, w, h):
+        self.x0, self.y0, self.w, self.h = x0, y0, w, h
+
+    def apply_coords(self, coords):
+        coords[:, 0] -= self.x0
+        coords[:, 1] -= self.y0
+        return coords
+
+
 class NoOpTransform:
     def apply_coords(self, coords):
         return coords
@@ -108,3 +121,52 @@ def resize_shortest_edge_size(h, w, short_edge_length, max_size, sample_style="r
         scale = max_size * 1.0 / max(newh, neww)
         newh, neww = newh * scale, neww * scale
     return int(newh + 0.5), int(neww + 0.5)
+
+
+CROP_TYPES = ("relative_range", "relative", "absolute", "absolute_range")
+
+
+def check_crop(crop_type, crop_size):
+    """INPUT.CROP.TYPE / SIZE as detectron2's RandomCrop takes them -> (crop_type, (s0, s1)); ValueError otherwise"""
+    if crop_type not in CROP_TYPES:
+        raise ValueError("INPUT.CROP.TYPE must be one of {}, got {!r}".format(", ".join(CROP_TYPES), crop_type))
+    if isinstance(crop_size, (str, bytes)) or not hasattr(crop_size, "__len__") or len(crop_size) != 2:
+        raise ValueError("INPUT.CROP.SIZE must hold two numbers, got {!r}".format(crop_size))
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in crop_size):
+        raise ValueError("INPUT.CROP.SIZE must hold two numbers, got {!r}".format(crop_size))
+    s0, s1 = crop_size
+    if crop_type.startswith("relative"):
+        if not (0 < s0 <= 1 and 0 < s1 <= 1):
+            raise ValueError("INPUT.CROP.SIZE of a relative crop must lie in (0, 1], got {!r}".format(crop_size))
+    else:
+        if int(s0) != s0 or int(s1) != s1 or s0 < 1 or s1 < 1:
+            raise ValueError("INPUT.CROP.SIZE of an absolute crop must hold integers > 0, got {!r}".format(crop_size))
+        s0, s1 = int(s0), int(s1)
+        if crop_type == "absolute_range" and s0 > s1:
+            raise ValueError("INPUT.CROP.SIZE of an absolute_range crop must be (low, high) with low <= high, got {!r}".format(crop_size))
+    return crop_type, (s0, s1)
+
+
+def random_crop_box(h, w, crop_type, crop_size, rng=np.random):
+    """detectron2 RandomCrop.get_crop_size + get_transform -> (x0, y0, cropw, croph) inside the h x w image.  This is a reading of
+    detectron2's code written down from memory, not checked against an installed detectron2: crop_size is (height, width) for
+    "relative" (fractions) and "absolute" (pixels); "relative_range" draws each fraction uniformly from [size, 1] (size in float32,
+    one rng.rand(2)); "absolute_range" draws the height, then the width, from [min(edge, s0), min(edge, s1)].  The origin is drawn
+    last: y0, then x0."""
+    if crop_type == "relative":
+        ch, cw = crop_size
+        croph, cropw = int(h * ch + 0.5), int(w * cw + 0.5)
+    elif crop_type == "relative_range":
+        size = np.asarray(crop_size, dtype=np.float32)
+        ch, cw = size + rng.rand(2) * (1 - size)
+        croph, cropw = int(h * ch + 0.5), int(w * cw + 0.5)
+    elif crop_type == "absolute":
+        croph, cropw = min(crop_size[0], h), min(crop_size[1], w)
+    elif crop_type == "absolute_range":
+        croph = rng.randint(min(h, crop_size[0]), min(h, crop_size[1]) + 1)
+        cropw = rng.randint(min(w, crop_size[0]), min(w, crop_size[1]) + 1)
+    else:
+        raise ValueError("Unknown crop type {}".format(crop_type))
+    y0 = rng.randint(h - croph + 1)
+    x0 = rng.randint(w - cropw + 1)
+    return int(x0), int(y0), int(cropw), int(croph)

@@ -1,5 +1,5 @@
-"""The argument checks the evaluation launchers share.  Nothing here launches or allocates on a device; every check raises ValueError
-with the name of the argument and what was expected, and a launcher finishes all of them before it allocates or launches anything.
+"""The argument checks the evaluation launchers, and the augmentation launchers (kernels/augment.py), share.  Nothing here launches
+or allocates on a device; every check raises ValueError with the name of the argument and what was expected, and a launcher finishes all of them before it allocates or launches anything.
 Read back from the device are only an offsets tensor (`offsets`, once) and the extremes of `order` (`merge_order`, once).
 """
 import collections
@@ -35,6 +35,24 @@ def nonempty(t, name, dtype):
     if n < 1:
         raise ValueError(f"{name} must be 1-D and not empty")
     return n
+
+
+def integer(v, name, lo=None, hi=None):
+    """v is an int (no bool, no float) with lo <= v <= hi where given -> v"""
+    if isinstance(v, bool) or not isinstance(v, int) or (lo is not None and v < lo) or (hi is not None and v > hi):
+        bound = "" if lo is None and hi is None else f" >= {lo}" if hi is None else f" <= {hi}" if lo is None else f" in [{lo}, {hi}]"
+        raise ValueError(f"{name} must be an integer{bound}, got {v!r}")
+    return v
+
+
+def window(box, H, W, name="box"):
+    """box = (x0, y0, w, h): four integers, a window of positive extent inside an H x W image -> the four"""
+    if not isinstance(box, (tuple, list)) or len(box) != 4:
+        raise ValueError(f"{name} must be four integers (x0, y0, w, h), got {box!r}")
+    x0, y0, w, h = (integer(v, f"{name}[{i}]") for i, v in enumerate(box))
+    if w <= 0 or h <= 0 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise ValueError(f"{name} {tuple(box)} must be a window of positive extent inside the {H} x {W} image")
+    return x0, y0, w, h
 
 
 def one_device(tensors):
