@@ -780,6 +780,25 @@ int omni_crop_resize_u8(const unsigned char* src, unsigned char* dst, unsigned c
  * A weight of 4096 is the identity; all three at 4096 launch nothing.  sum: one device unsigned long long, zeroed and filled here
  * when wc != 4096 (one 64-bit integer atomic per workgroup, same bits every run) and read by the apply pass on the device. */
 int omni_color_jitter_u8(unsigned char* img, int H, int W, int wb, int wc, int ws, int c_red, unsigned long long* sum, void* stream);
+/* INPUT.CAMERA_ROTATION (csrc/warp.hip): a projective warp with bilinear sampling.  src (planes, H, W) -> dst (planes, HO, WO), both
+ * contiguous, not overlapping; m = 9 HOST doubles, row-major, mapping an output pixel to a source pixel; fill = `planes` HOST bytes.
+ * Both are read at the call and passed to the kernel by value.  One double-precision projective map per pixel, every product and
+ * sum rounded on its own in the order written (no contraction), then integers -- the same bytes on the host and on every device.
+ * For output row i, column j:
+ *   xd = j + 0.5, yd = i + 0.5
+ *   X = (m0*xd + m1*yd) + m2,  Y = (m3*xd + m4*yd) + m5,  D = (m6*xd + m7*yd) + m8
+ *   r = 1.0 / D,  u = X*r,  v = Y*r
+ *   if !(u >= 0 && u <= W && v >= 0 && v <= H): out[p] = fill[p] in every plane p (a NaN fills as well)
+ *   su = u - 0.5, sv = v - 0.5, x0 = floor(su), y0 = floor(sv)
+ *   a = (int)((su - x0)*256.0 + 0.5), b = (int)((sv - y0)*256.0 + 0.5)            both in [0, 256]
+ *   x1 = x0 + 1, y1 = y0 + 1, all four indices clamped into the image (edge replication)
+ *   top = s[y0][x0]*(256-a) + s[y0][x1]*a,  bot = s[y1][x0]*(256-a) + s[y1][x1]*a
+ *   out = (top*(256-b) + bot*b + 32768) >> 16                                      at most 255*65536 + 32768 < 2^31
+ * OMNI_ERR_ARG, and nothing launched: a null pointer, a size <= 0, planes > 4, overlapping src / dst ranges, an entry of m that is not
+ * finite, D <= 0 at one of the corners (0,0), (WO,0), (0,HO), (WO,HO) of the output rectangle (D is affine: positive at the corners,
+ * positive all over it). */
+int omni_warp_homography_u8(const unsigned char* src, unsigned char* dst, int planes, int H, int W, int HO, int WO, const double* m,
+                            const unsigned char* fill, void* stream);
 
 /* ---------------------------------------------------------------------------- optimizer */
 

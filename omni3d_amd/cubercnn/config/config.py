@@ -412,6 +412,56 @@ def color_jitter_args(cfg):
     return out
 
 
+_CAMERA_ROTATION = {"ENABLED": False, "ROLL": [-5.0, 5.0], "PITCH": [-3.0, 3.0], "YAW": [0.0, 0.0], "FILL": []}
+CAMERA_ROTATION_MAX_DEG = 15.0
+
+
+def add_camera_rotation_config(cfg):
+    """INPUT.CAMERA_ROTATION.*: geometric augmentation of the training images (`DatasetMapper3D`, csrc/warp.hip,
+    omni_warp_homography_u8): a roll, a pitch and a yaw of the camera about its optical centre are drawn uniformly, in degrees, from
+    their [low, high] interval for every image; the pixels move by the homography K Q K^-1, the 3D targets by Q, and `K`, the image
+    size and the virtual depth stay as they are.  FILL: the three bytes, in INPUT.FORMAT channel order, of the border the rotation
+    uncovers; empty = MODEL.PIXEL_MEAN rounded to the nearest byte, about zero after normalisation.  Neither detectron2's defaults nor
+    the reference define the node, so it is absent until this call; without it nothing is rotated.  Idempotent: values already set are
+    kept.  An interval of [c, c] fixes its angle and draws nothing.
+    The intervals (roll +-5, pitch +-3, no yaw) are conventions, not tuned values; their effect on AP has not been measured."""
+    if "CAMERA_ROTATION" not in cfg.INPUT:
+        cfg.INPUT.CAMERA_ROTATION = CN()
+    for key, value in _CAMERA_ROTATION.items():
+        cfg.INPUT.CAMERA_ROTATION.setdefault(key, list(value) if isinstance(value, list) else value)
+    return cfg
+
+
+def camera_rotation_args(cfg):
+    """INPUT.CAMERA_ROTATION -> {"enabled", "roll", "pitch", "yaw", "fill"}: the intervals as (low, high) floats in degrees, the fill as
+    three bytes; `DatasetMapper3D` reads them through this.  A cfg without the node: the feature off.  ValueError unless every interval
+    is two finite numbers with -15 <= low <= high <= 15 and FILL is empty or three integers in [0, 255]."""
+    import math
+    node = cfg.INPUT.get("CAMERA_ROTATION")
+    have = dict(node) if node is not None else {}
+    out = {"enabled": bool(have.get("ENABLED", False))}
+    for key in ("ROLL", "PITCH", "YAW"):
+        iv = have.get(key, _CAMERA_ROTATION[key])
+        if isinstance(iv, (str, bytes)) or not hasattr(iv, "__len__") or len(iv) != 2 or any(
+                isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) for v in iv):
+            raise ValueError(f"INPUT.CAMERA_ROTATION.{key} must be two numbers [low, high] in degrees, got {iv!r}")
+        lo, hi = float(iv[0]), float(iv[1])
+        if not -CAMERA_ROTATION_MAX_DEG <= lo <= hi <= CAMERA_ROTATION_MAX_DEG:
+            raise ValueError(f"INPUT.CAMERA_ROTATION.{key} must satisfy -15 <= low <= high <= 15, got {iv!r}")
+        out[key.lower()] = (lo, hi)
+    fill = have.get("FILL", [])
+    if isinstance(fill, (str, bytes)) or not hasattr(fill, "__len__") or len(fill) not in (0, 3) or any(
+            isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255 for v in fill):
+        raise ValueError(f"INPUT.CAMERA_ROTATION.FILL must be empty or three integers in [0, 255], got {fill!r}")
+    if len(fill) == 0:
+        mean = list(cfg.MODEL.PIXEL_MEAN)
+        if len(mean) != 3:
+            raise ValueError(f"INPUT.CAMERA_ROTATION.FILL is empty and MODEL.PIXEL_MEAN does not hold three values: {mean!r}")
+        fill = [min(max(int(math.floor(float(v) + 0.5)), 0), 255) for v in mean]
+    out["fill"] = tuple(int(v) for v in fill)
+    return out
+
+
 def build_tta_model(cfg, model):
     """the model wrapped for test-time augmentation when TEST.AUG.ENABLED, else the model itself"""
     if not tta_args(cfg)["enabled"]:

@@ -1,6 +1,6 @@
 """detectron2.data plumbing: DatasetCatalog / MetadataCatalog registries and the two transforms the reference's mapper uses
 (ResizeShortestEdge, RandomFlip) with detectron2's parameter sampling and coordinate rules, and RandomCrop (INPUT.CROP), which
-detectron2's mapper puts in front of them."""
+detectron2's mapper puts in front of them; the geometry of INPUT.CAMERA_ROTATION (a camera rotation and its pixel homography)."""
 import types
 
 import numpy as np
@@ -121,6 +121,32 @@ def resize_shortest_edge_size(h, w, short_edge_length, max_size, sample_style="r
         scale = max_size * 1.0 / max(newh, neww)
         newh, neww = newh * scale, neww * scale
     return int(newh + 0.5), int(neww + 0.5)
+
+
+def camera_rotation(roll, pitch, yaw):
+    """A rotation of the camera about its optical centre, angles in degrees, camera frame x right, y down, z forward:
+    Q = Rz(roll) @ Ry(yaw) @ Rx(pitch) as float64 (3, 3).  A point of the scene moves as X' = Q X."""
+    r, p, y = (np.deg2rad(float(a)) for a in (roll, pitch, yaw))
+    rz = np.array([[np.cos(r), -np.sin(r), 0.0], [np.sin(r), np.cos(r), 0.0], [0.0, 0.0, 1.0]])
+    ry = np.array([[np.cos(y), 0.0, np.sin(y)], [0.0, 1.0, 0.0], [-np.sin(y), 0.0, np.cos(y)]])
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(p), -np.sin(p)], [0.0, np.sin(p), np.cos(p)]])
+    return rz @ ry @ rx
+
+
+def rotation_homography(K, Q):
+    """-> (Hm, Hinv) float64: Hm = K Q K^-1 moves a pixel of the image to its place under the camera rotation Q, Hinv = K Q^T K^-1
+    moves it back (the map a warp samples through)"""
+    K, Q = np.asarray(K, dtype=np.float64), np.asarray(Q, dtype=np.float64)
+    Kinv = np.linalg.inv(K)
+    return K @ Q @ Kinv, K @ Q.T @ Kinv
+
+
+def homography_apply(Hm, pts):
+    """pts (n, 2) pixels through the 3 x 3 map Hm -> ((n, 2) pixels, (n,) denominators), float64"""
+    pts = np.asarray(pts, dtype=np.float64).reshape(-1, 2)
+    xyw = np.concatenate([pts, np.ones((len(pts), 1))], axis=1) @ np.asarray(Hm, dtype=np.float64).T
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return xyw[:, :2] / xyw[:, 2:3], xyw[:, 2]
 
 
 CROP_TYPES = ("relative_range", "relative", "absolute", "absolute_range")

@@ -55,6 +55,17 @@ def window(box, H, W, name="box"):
     return x0, y0, w, h
 
 
+def matrix3(m, name):
+    """nine finite numbers as a 3 x 3 -> them as a contiguous float64 array"""
+    try:
+        a = np.ascontiguousarray(np.asarray(m, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a 3 x 3 matrix of finite numbers, got {m!r}") from None
+    if a.shape != (3, 3) or not np.isfinite(a).all():
+        raise ValueError(f"{name} must be a 3 x 3 matrix of finite numbers, got {m!r}")
+    return a
+
+
 def one_device(tensors):
     if len({t.device for t in tensors}) != 1:
         raise ValueError("all inputs must live on one device")

@@ -1,7 +1,9 @@
-"""Launchers of csrc/augment.hip: Pillow's bilinear coefficient rows built on the device, the PIL-exact resize of a window of an image
-(INPUT.CROP) and the integer colour jitter (INPUT.COLOR_JITTER).  Nothing here uploads a table, copies the source or reads back."""
+"""Launchers of csrc/augment.hip and csrc/warp.hip: Pillow's bilinear coefficient rows built on the device, the PIL-exact resize of a window
+of an image (INPUT.CROP), the integer colour jitter (INPUT.COLOR_JITTER) and the projective warp (INPUT.CAMERA_ROTATION).  Nothing here
+uploads a table, copies the source or reads back."""
 import math
 
+import numpy as np
 import torch
 
 from .. import lib as _lib
@@ -9,6 +11,7 @@ from . import _args
 
 CROP_GRID_THREADS = 8192 * 256      # csrc/augment.hip grid_for: the resampling passes stride over more work items than this
 JITTER_GRID_THREADS = 2048 * 256    # csrc/augment.hip JITTER_MAX_BLOCKS: the same for the jitter's two passes
+WARP_GRID_THREADS = 2048 * 256      # csrc/warp.hip WARP_MAX_BLOCKS: the warp strides over more output pixels than this
 WEIGHT_ONE, WEIGHT_MAX = 4096, 16384
 
 
@@ -66,3 +69,31 @@ def color_jitter_u8_(img, wb, wc, ws, fmt):
     total = _args.empty((1,), torch.int64, img)         # the contrast sum: written and read on the device only
     L.call("omni_color_jitter_u8", _lib.ptr(img), H, W, wb, wc, ws, c_red, _lib.ptr(total), _lib.stream_of(img))
     return img
+
+
+def warp_denominator_positive(m, out_h, out_w):
+    """the third row of the 3 x 3 map `m` is positive at the four corners of the out_h x out_w output rectangle, hence all over it: the
+    entry's check, in its arithmetic"""
+    m6, m7, m8 = (float(v) for v in m[2])
+    return all((m6 * x + m7 * y) + m8 > 0.0 for y in (0.0, float(out_h)) for x in (0.0, float(out_w)))
+
+
+def warp_homography_u8(img, m, out_h, out_w, fill=(0, 0, 0)):
+    """img (3, H, W) uint8 -> a new (3, out_h, out_w) uint8 tensor: output pixel (j + 0.5, i + 0.5) takes the bilinear sample of `img` at
+    m @ (j + 0.5, i + 0.5, 1), by the integer definition of include/omni3d_hip.h (omni_warp_homography_u8); where the map leaves the
+    source the pixel is `fill`, one byte per plane.  m: 3 x 3 finite numbers with a positive denominator over the output rectangle.
+    The matrix and the fill travel in the launch's arguments: one launch, nothing uploaded."""
+    _, H, W = _args.tensor(img, "img", torch.uint8, (3, None, None))
+    if min(H, W) < 1:
+        raise ValueError("img must not be empty")
+    m = _args.matrix3(m, "m")
+    _args.integer(out_h, "out_h", 1), _args.integer(out_w, "out_w", 1)
+    if not isinstance(fill, (tuple, list)) or len(fill) != 3:
+        raise ValueError(f"fill must be three integers in [0, 255], got {fill!r}")
+    fill = np.array([_args.integer(v, f"fill[{i}]", 0, 255) for i, v in enumerate(fill)], dtype=np.uint8)
+    if not warp_denominator_positive(m, out_h, out_w):
+        raise ValueError("m must have a positive denominator m[2] @ (x, y, 1) at every corner of the output rectangle")
+    L = _lib.check_device(img)
+    out = _args.empty((3, out_h, out_w), torch.uint8, img)
+    L.call("omni_warp_homography_u8", _lib.ptr(img), _lib.ptr(out), 3, H, W, out_h, out_w, m.ctypes.data, fill.ctypes.data, _lib.stream_of(img))
+    return out

@@ -1,7 +1,9 @@
 """Time of one training-mapper call per image with the augmentations of csrc/augment.hip: `DatasetMapper3D(cfg, True, device)` from
-configs/Base.yaml (MIN_SIZE_TRAIN 256..640, random flip) on a 375 x 1242 and a 1080 x 1920 source with eight cuboids, in three
-variants -- plain (the parent's path: csrc/resize.hip with host-built tables, reported as context only), INPUT.CROP, and INPUT.CROP +
-INPUT.COLOR_JITTER.  The plain path is timed twice: "cold", the table cache emptied before the first call, so that each of the 25
+configs/Base.yaml (MIN_SIZE_TRAIN 256..640, random flip) on a 375 x 1242 and a 1080 x 1920 source with eight cuboids, in five
+variants -- plain (the parent's path: csrc/resize.hip with host-built tables, reported as context only), INPUT.CROP, INPUT.CROP +
+INPUT.COLOR_JITTER, INPUT.CAMERA_ROTATION (csrc/warp.hip: the warp of the full frame, then the plain resize, timed with the resize's
+tables cached like the plain call it is compared with) and INPUT.CAMERA_ROTATION + INPUT.CROP (the warp of the window only, then the
+plain resize, whose tables are new for every crop and built on the host).  The plain path is timed twice: "cold", the table cache emptied before the first call, so that each of the 25
 output sizes of MIN_SIZE_TRAIN builds its tables on the host when it first appears, and "tables cached", every table of this source
 built before the first call -- its steady state on a dataset with a handful of source sizes.  Each figure is the median over 20
 calls, after 5 warm-up calls, of the time between two device events recorded around the whole call (host work, the upload and the
@@ -18,7 +20,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from omni3d_amd.cubercnn.config import add_color_jitter_config, get_cfg_defaults  # noqa: E402
+from omni3d_amd.cubercnn.config import add_camera_rotation_config, add_color_jitter_config, get_cfg_defaults  # noqa: E402
 from omni3d_amd.cubercnn.data import DatasetMapper3D  # noqa: E402
 from omni3d_amd.d2.config import get_cfg  # noqa: E402
 from omni3d_amd.d2.data import resize_shortest_edge_size  # noqa: E402
@@ -26,7 +28,9 @@ from omni3d_amd.d2.structures import BoxMode  # noqa: E402
 from omni3d_amd.kernels import augment, resize  # noqa: E402
 
 SOURCES = [(375, 1242), (1080, 1920)]
-VARIANTS = [("plain", []), ("crop", ["INPUT.CROP.ENABLED", True]), ("crop + jitter", ["INPUT.CROP.ENABLED", True, "INPUT.COLOR_JITTER.ENABLED", True])]
+VARIANTS = [("plain", []), ("crop", ["INPUT.CROP.ENABLED", True]), ("crop + jitter", ["INPUT.CROP.ENABLED", True, "INPUT.COLOR_JITTER.ENABLED", True]),
+            ("rotate", ["INPUT.CAMERA_ROTATION.ENABLED", True]), ("rotate + crop", ["INPUT.CAMERA_ROTATION.ENABLED", True, "INPUT.CROP.ENABLED", True])]
+CACHED = {"plain": (False, True), "rotate": (True,)}      # variants whose resize tables depend on the source alone: timed with them built
 WARMUP, CALLS = 5, 20
 
 
@@ -54,6 +58,7 @@ def make_cfg(opts):
     cfg = get_cfg()
     get_cfg_defaults(cfg)
     add_color_jitter_config(cfg)
+    add_camera_rotation_config(cfg)
     cfg.merge_from_file(os.path.join(ROOT, "configs", "Base.yaml"))
     cfg.merge_from_list(list(opts))
     return cfg
@@ -101,7 +106,7 @@ def main(out=None):
     for h, w in SOURCES:
         record = make_record(h, w)
         for name, opts in VARIANTS:
-            for cached in ((False, True) if name == "plain" else (None,)):
+            for cached in CACHED.get(name, (None,)):
                 cfg = make_cfg(opts)
                 mapper = DatasetMapper3D(cfg, True, device=device, rng=np.random.RandomState(0))
                 mapper.dataset_id_to_unknown_cats = {0: set()}
@@ -112,7 +117,7 @@ def main(out=None):
                         resize.pil_bilinear_coeffs(w, nw), resize.pil_bilinear_coeffs(h, nh)
                 label = name if cached is None else name + (", tables cached" if cached else ", cold")
                 lines.append("%4d x %4d  %-22s %7.3f ms%s" % (h, w, label, time_mapper(mapper, record),
-                                                              "   (the parent's path, context only)" if cached is not None else ""))
+                                                              "   (the parent's path, context only)" if name == "plain" else ""))
     lines.append("coefficient tables for one size pair: host pil_bilinear_coeffs on a cache miss (host clock) | device_coeffs (allocation + one "
                  "launch, device events)")
     for in_size, out_size in ((1242, 640), (1118, 1067), (1920, 1138), (1080, 640)):

@@ -1,9 +1,9 @@
 """Shows what the training mapper's augmentation does to an Omni3D annotation file: runs `DatasetMapper3D(cfg, is_train=True)` with the
-configured INPUT.CROP / INPUT.COLOR_JITTER / resize / flip over the first --n images and draws every kept ground-truth cuboid on the
+configured INPUT.CAMERA_ROTATION / INPUT.CROP / INPUT.COLOR_JITTER / resize / flip over the first --n images and draws every kept ground-truth cuboid on the
 augmented image through the camera the mapper returns (`K` scaled by image height / `height`).  The boxes sit on their objects when
-pixels, camera and 3D targets still belong together; under a crop that is the point of looking.
+pixels, camera and 3D targets still belong together; under a crop or a camera rotation that is the point of looking.
     python tools/show_augment.py DATASET.json OUT_DIR [--n 8] [--seed 0] [--image-root DIR] [--config-file YAML] [KEY VALUE ...]
-e.g. ... INPUT.CROP.ENABLED True INPUT.COLOR_JITTER.ENABLED True.  Images are read from --image-root (default: the directory above the
+e.g. ... INPUT.CAMERA_ROTATION.ENABLED True INPUT.CROP.ENABLED True INPUT.COLOR_JITTER.ENABLED True.  Images are read from --image-root (default: the directory above the
 JSON file's, the Omni3D layout datasets/Omni3D/<name>.json + datasets/<file_path>)."""
 import argparse
 import json
@@ -62,13 +62,14 @@ def main(argv=None):
     from PIL import Image
     from omni3d_amd import lib
     from omni3d_amd.cubercnn import data
-    from omni3d_amd.cubercnn.config import add_color_jitter_config, get_cfg_defaults
+    from omni3d_amd.cubercnn.config import add_camera_rotation_config, add_color_jitter_config, get_cfg_defaults
     from omni3d_amd.d2.config import get_cfg
     from omni3d_amd.d2.data import MetadataCatalog
 
     cfg = get_cfg()
     get_cfg_defaults(cfg)
     add_color_jitter_config(cfg)
+    add_camera_rotation_config(cfg)
     if args.config_file:
         cfg.merge_from_file(args.config_file)
     cfg.merge_from_list(opts)
