@@ -8,8 +8,6 @@ import time
 import torch
 import torch.distributed as dist
 
-from .functional import total_loss
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FP32_MFMA_PEAK_TF = 157.3          # MI355X_MICROARCH.md: f32-input MFMA, dense
 TRAIN_GFLOP_PER_IMAGE = 307.8      # fwd 103.0 GFLOP, fwd+dgrad+wgrad 307.8 GFLOP
@@ -65,9 +63,6 @@ def stage_batch(model, priors, rank, n=IMS_PER_GPU, size=IMAGE_SIZE):
 
 
 def run_train(args, world, rank):
-    main_prio = int(os.environ.get("OMNI_MAIN_PRIORITY", "0"))
-    if main_prio != 0 and DEVICE == "cuda":       # A/B knob: the critical path on a high-priority stream (torch: -1 = high)
-        torch.cuda.set_stream(torch.cuda.Stream(priority=main_prio))
     cfg, model, opt, priors = build(world)
     if world > 1:
         dist.broadcast(opt.flat_param, src=0)
@@ -92,66 +87,32 @@ def run_train(args, world, rank):
         opt.step()
 
     def eager_step():
-        if getattr(model, "feature_cut", None) is not None and hasattr(graphed, "_eager"):    # staged backward installed
-            losses, total, pending = graphed._eager()
-            opt.all_reduce_finish(pending + graphed._late(graphed._eager_exchanged_all), defer_scale=True)
-            return finish(losses, total)
-        opt.zero_grad()
-        losses = model(batch, packed)
-        total = total_loss(losses)             # == sum(losses.values()), two launches
-        total.backward()
-        opt.all_reduce_finish(opt.all_reduce_begin("early") + opt.all_reduce_begin("late"), defer_scale=True)
-        finish(losses, total.detach())
+        losses, total, pending = graphed.eager_step()
+        opt.all_reduce_finish(pending, defer_scale=True)
+        finish(losses, total)
 
-    # zero_grad + forward + losses + backward replayed as one hipGraph (OMNI_BENCH_GRAPH=0: eager launches);
-    # all-reduce / non-finite scan / SGD update stay eager (host-side learning rate).  With more than one rank the
-    # backward is cut at the FPN features into two graphs so the all-reduce of the heads' gradients (61 % of the
-    # bytes) runs beside the backbone's backward (GraphedTwoPhase); the collective sequence is the same on every
-    # rank whether or not its capture succeeded.
+    # zero_grad + forward + losses + backward replayed as staged hipGraphs (OMNI_BENCH_GRAPH=0: the same stages with eager launches);
+    # all-reduce / non-finite scan / SGD update stay eager (host-side learning rate).  The collective sequence is the same on
+    # every rank whether or not its capture succeeded.
     use_graph = os.environ.get("OMNI_BENCH_GRAPH", "1") != "0" and DEVICE == "cuda"
-    two_phase = world > 1 or os.environ.get("OMNI_BENCH_TWO_PHASE") == "1"
-    graphed, graph_note = None, "eager (OMNI_BENCH_GRAPH=0)"
-    from omni3d_amd.cubercnn.solver.graphed import GraphedForwardBackward, GraphedPipelined, GraphedTwoPhase
-    pipelined = os.environ.get("OMNI_BENCH_PIPELINE", "1") != "0" and os.environ.get("OMNI_BENCH_TWO_PHASE") != "1"
+    from omni3d_amd.cubercnn.solver.graphed import GraphedPipelined
     if world > 1 and DEVICE == "cuda":
         from omni3d_amd.cubercnn.solver import graphed as _graphed_mod
         _graphed_mod.set_pipe_timing(True)       # per-stage device timestamps + exposed exchange time in every N > 1 line
         opt.exchange_timing = True
-    if pipelined:
-        try:
-            graphed = GraphedPipelined(model, opt, batch, packed, graphs=use_graph)
-            graph_note = (f"{len(graphed.stages)} backward stages x (critical-path hipGraph on the main stream | weight-gradient hipGraph "
-                          "on a second stream), all-reduce of every backward stage's gradient range behind that stage's weight-gradient graph" if use_graph
-                          else "eager staged backward, weight gradients on a second stream")
-        except Exception as e:   # capture refused: same sequence with eager launches
-            graphed = GraphedPipelined(model, opt, batch, packed, graphs=False)
-            graph_note = f"eager staged backward (capture failed: {type(e).__name__}: {str(e)[:160]})"
-        two_phase = True          # same call protocol: (losses, total, pending)
-    elif two_phase:
-        try:
-            graphed = GraphedTwoPhase(model, opt, batch, packed, graphs=use_graph)
-            graph_note = ("two hipGraphs (fwd+heads bwd | backbone bwd), all-reduce of the heads' gradients overlapped"
-                          if use_graph else "eager two-phase backward, all-reduce of the heads' gradients overlapped")
-        except Exception as e:   # capture refused: same sequence with eager launches
-            graphed = GraphedTwoPhase(model, opt, batch, packed, graphs=False)
-            graph_note = f"eager two-phase (capture failed: {type(e).__name__}: {str(e)[:160]})"
-    elif use_graph:
-        try:
-            graphed = GraphedForwardBackward(model, opt, batch, packed)
-            graph_note = "hipGraph replay of zero_grad+fwd+losses+bwd"
-        except Exception as e:   # capture refused: report it, measure the eager path
-            graphed, graph_note = None, f"eager (capture failed: {type(e).__name__}: {str(e)[:200]})"
+    try:
+        graphed = GraphedPipelined(model, opt, batch, packed, graphs=use_graph)
+        graph_note = (f"{len(graphed.stages)} backward stages x (critical-path hipGraph on the main stream | weight-gradient hipGraph "
+                      "on a second stream), all-reduce of every backward stage's gradient range behind that stage's weight-gradient graph" if use_graph
+                      else "eager staged backward, weight gradients on a second stream")
+    except Exception as e:   # capture refused: same sequence with eager launches
+        graphed = GraphedPipelined(model, opt, batch, packed, graphs=False)
+        graph_note = f"eager staged backward (capture failed: {type(e).__name__}: {str(e)[:160]})"
 
-    def graph_step():
-        if two_phase:
-            losses, total, pending = graphed()
-            opt.all_reduce_finish(pending, defer_scale=True)       # 1/world is folded into the SGD kernel
-        else:
-            losses, total = graphed()
-            opt.all_reduce_finish(opt.all_reduce_begin("early") + opt.all_reduce_begin("late"), defer_scale=True)
+    def step():
+        losses, total, pending = graphed()
+        opt.all_reduce_finish(pending, defer_scale=True)       # 1/world is folded into the SGD kernel
         finish(losses, total)
-
-    step = graph_step if graphed is not None else eager_step
 
     # executed (Winograd-aware) flops of one step: count the multiply-adds of every MFMA launch during one eager step (--full only)
     from omni3d_amd.profile_io import ExecutedFlops

@@ -135,7 +135,7 @@ class RCNN3D(nn.Module):
                                        hw_dev=getattr(packed, "image_hw", None))
         with training_pass():       # (eval-mode BatchNorms in here are frozen ones with gradients: freeze_bn / MODEL.USE_BN False)
             features = self.backbone(images.tensor)
-        if getattr(self, "feature_cut", None) is not None:   # data-parallel two-phase backward (solver/graphed.py)
+        if getattr(self, "feature_cut", None) is not None:   # the staged backward's cut at the FPN features (solver/graphed.py)
             features = self.feature_cut(features)
         self._bump_bn_counters()
         # the reference's call contracts (rcnn3d.py:50-70): list[Instances] ground truth, per-image intrinsics and scale

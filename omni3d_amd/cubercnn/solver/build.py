@@ -112,14 +112,10 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self.segments = []
         self._slot = {}      # id(param) -> (offset, numel) inside the flat buckets
         off = 0
-        # Inside a class, parameters whose gradients complete EARLY in backward (the heads: everything that is not the
-        # backbone, tagged `_omni_early_grad` by build_optimizer) sit behind the late ones, so each class is
-        # [late | early] and the data-parallel exchange can all-reduce the early ranges while the backbone is still
-        # back-propagating (all_reduce_begin / all_reduce_finish).
-        # Round 4: one exchange range per BACKWARD STAGE and class (`_omni_grad_stage`, tagged by build_optimizer from the backbone's
-        # cut points: 0 = heads, 1 = FPN + the deepest levels, ... last = the first layer), ordered last stage first, so the
-        # gradients of stage k are all-reduced behind that stage's weight-gradient graph while the stages below still back-propagate
-        # (graphed.py); `early_ranges` (stage 0) / `late_ranges` (everything else) keep the two-phase interface.
+        # One exchange range per BACKWARD STAGE and class (`_omni_grad_stage`, tagged by build_optimizer from the backbone's cut
+        # points: 0 = heads, 1 = FPN + the deepest levels, ... last = the first layer; without that tag `_omni_early_grad` gives
+        # 0 = everything outside the backbone, 1 = the backbone), ordered last stage first, so the gradients of stage k are
+        # all-reduced behind that stage's weight-gradient graph while the stages below still back-propagate (graphed.py).
         self.stage_ranges = {}
         for key, (items, entries) in layout.items():
             start = off
@@ -153,8 +149,6 @@ class _FlatOptimizer(torch.optim.Optimizer):
                 self.stage_ranges.setdefault(cur_stage, []).append((cur_start, off))
             self.segments.append((start, off, next(i for i, g in enumerate(self.param_groups) if g is items[0][0])))
         self.n_stages = (max(self.stage_ranges) + 1) if self.stage_ranges else 1
-        self.early_ranges = list(self.stage_ranges.get(0, []))
-        self.late_ranges = [r for k in sorted(self.stage_ranges) if k > 0 for r in self.stage_ranges[k]]
         self._clip_t = None      # the clip tiles (_clip_tables), built when clipping is first armed
 
     @staticmethod
@@ -328,8 +322,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
     def all_reduce_begin(self, which, group=None):
         """Starts the asynchronous all-reduce (sum) of a part of the flat gradient bucket and returns the pending work handles.
         which: "early" = backward stage 0 (every parameter outside the backbone: final once the heads have back-propagated), "late" =
-        every other stage, an int k = stage k, ("from", k) = stages k, k + 1, ...  cubercnn/solver/graphed.py issues stage k behind
-        that stage's weight-gradient graph, so RCCL moves each stage's bytes while the stages below still back-propagate."""
+        every other stage, an int k = stage k.  cubercnn/solver/graphed.py issues stage k behind that stage's weight-gradient graph,
+        so RCCL moves each stage's bytes while the stages below still back-propagate."""
         import torch.distributed as dist
         if getattr(self, "_exchange_muted", False):        # warm-up passes of a staged-graph capture (graphed.py): rank-local
             return []
@@ -340,8 +334,6 @@ class _FlatOptimizer(torch.optim.Optimizer):
             stages = [0]
         elif which == "late":
             stages = list(range(1, self.n_stages))
-        elif isinstance(which, tuple):
-            stages = list(range(int(which[1]), self.n_stages))
         else:
             stages = self.exchange_stages(int(which))
         return [(dist.all_reduce(self.flat_grad[s:e], group=group, async_op=True), s, e) for s, e in self.exchange_chunks(stages)]

@@ -2,9 +2,9 @@
 
 The HIP training path has fixed shapes and no device->host synchronisation (fixed-size ROI blocks, packed
 proposals + counts, sampling driven by device-side Exp(1) variates), so zero_grad + forward + the ten losses +
-backward of one (batch shape, model) pair is a static sequence of ~800 kernel launches.  Replaying it as ONE
-hipGraph removes the per-launch host cost (~17 ms of Python/ctypes enqueue per step, measured, against ~20 ms of
-GPU work) and the inter-kernel launch gaps.  The learning-rate dependent part (gradient all-reduce, non-finite
+backward of one (batch shape, model) pair is a static sequence of ~800 kernel launches.  Replaying it as a handful
+of hipGraphs (GraphedPipelined, the one stepper) removes the per-launch host cost of Python/ctypes enqueue
+and the inter-kernel launch gaps.  The learning-rate dependent part (gradient all-reduce, non-finite
 scan, SGD update: 3-4 launches) stays eager so schedulers keep working on host floats.
 
 The reference's loop is tools/train_net.py:do_train (:175-259); this object replaces its
@@ -126,132 +126,6 @@ def pipe_timing_table(graphed, last=10):
                                         "weight-gradient graph (W) and of the all-reduce calls issued behind it (X)"}
 
 
-class FeatureCut:
-    """Splits backward at the FPN features: `cut(features)` hands detached copies to the heads (RPN, ROI heads), so
-    `total.backward()` stops there with the heads' parameter gradients complete; `cut.backward()` then pushes the
-    gradients that reached the copies through FPN + bottom-up.  Between the two the data-parallel step starts the
-    all-reduce of the heads' gradient ranges (FlatSGD.all_reduce_begin("early"))."""
-
-    def __init__(self):
-        self.src, self.dst = None, None
-
-    def __call__(self, features):
-        from ...functional import fanout
-        self.src = features
-        self.dst = {k: fanout(v.detach().requires_grad_(True)) for k, v in features.items()}
-        return self.dst
-
-    def backward(self):
-        pairs = [(self.src[k], _leaf_grad(self.dst[k])) for k in self.src]
-        pairs = [p for p in pairs if p[1] is not None]
-        self.src, self.dst = None, None
-        if pairs:
-            torch.autograd.backward([p[0] for p in pairs], [p[1] for p in pairs])
-
-
-class GraphedTwoPhase:
-    """GraphedForwardBackward for data-parallel runs: graph A = zero_grad + forward + losses + backward of the heads,
-    graph B = backward of FPN + bottom-up (same memory pool).  `__call__` replays A, starts the asynchronous all-reduce
-    of the heads' gradients, replays B (RCCL runs beside the backbone's kernels), starts the all-reduce of the rest and
-    returns the pending handles for FlatSGD.all_reduce_finish.  graphs=False runs the same sequence with eager launches
-    (used when capture is refused, and by the CPU tests)."""
-
-    def __init__(self, model, optimizer, batch, packed, warmup=3, graphs=True, group=None):
-        self.model, self.optimizer, self.group = model, optimizer, group
-        self.static_batch, self.static_packed = batch, packed
-        self.cut = FeatureCut()
-        model.feature_cut = self.cut
-        self.graph_a = self.graph_b = None
-        if not graphs:
-            return
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._phase_a()
-                self._phase_b()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        from ... import functional as HF
-        from ...kernels import detmode
-        detmode.prewarm(torch.cuda.current_device())
-        prev_mode = HF.side_mode()
-        HF.side_mode("inline")      # single-branch graphs: a captured fork / join would be replayed node by node from the host
-        try:
-            ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with torch.cuda.graph(ga, capture_error_mode="thread_local"):
-                self.losses, self.total = self._phase_a()
-            with torch.cuda.graph(gb, pool=ga.pool(), capture_error_mode="thread_local"):
-                self._phase_b()
-        finally:
-            HF.side_mode(prev_mode)
-        self.graph_a, self.graph_b = ga, gb
-
-    def _phase_a(self):
-        self.optimizer.zero_grad()
-        losses = self.model(self.static_batch, self.static_packed)
-        total = total_loss(losses)             # == sum(losses.values()), two launches
-        total.backward(_unit(total))
-        return losses, total.detach()
-
-    def _phase_b(self):
-        self.cut.backward()
-
-    def __call__(self):
-        """-> (loss dict, total, pending all-reduce handles)"""
-        if self.graph_a is not None:
-            self.graph_a.replay()
-        else:
-            self.losses, self.total = self._phase_a()
-        pending = self.optimizer.all_reduce_begin("early", self.group)
-        if self.graph_b is not None:
-            self.graph_b.replay()
-        else:
-            self._phase_b()
-        pending += self.optimizer.all_reduce_begin("late", self.group)
-        return self.losses, self.total, pending
-
-
-class GraphedForwardBackward:
-    def __init__(self, model, optimizer, batch, packed, warmup=3):
-        assert torch.cuda.is_available(), "hipGraph capture needs the GPU"
-        self.model, self.optimizer = model, optimizer
-        self.static_batch, self.static_packed = batch, packed
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):       # warm-up off the capture: allocator pools, lazily built constants
-            for _ in range(warmup):
-                self._body()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        from ... import functional as HF
-        from ...kernels import detmode
-        detmode.prewarm(torch.cuda.current_device())
-        prev_mode = HF.side_mode()
-        HF.side_mode("inline")      # single-branch graph: a captured fork / join would be replayed node by node from the host
-        # thread_local: RCCL's watchdog thread (N > 1) and the autograd worker may issue HIP calls while this thread
-        # captures; only this thread's own unsafe calls should abort the capture
-        try:
-            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.losses, self.total = self._body()
-        finally:
-            HF.side_mode(prev_mode)
-
-    def _body(self):
-        self.optimizer.zero_grad()
-        losses = self.model(self.static_batch, self.static_packed)
-        total = total_loss(losses)             # == sum(losses.values()), two launches
-        total.backward(_unit(total))
-        return losses, total.detach()
-
-    def __call__(self):
-        """Replays zero_grad + forward + backward; gradients land in the optimizer's flat bucket.
-        -> (loss dict, total) as static device tensors (overwritten by the next replay)."""
-        self.graph.replay()
-        return self.losses, self.total
-
-
 class StageCuts:
     """Ordered cut points of one forward pass.  `cuts(x)` (a tensor or a dict of tensors) returns detached copies that the
     rest of the forward consumes; backward then runs in stages: `total.backward()` stops at the most recent cut, every
@@ -300,11 +174,13 @@ class StageCuts:
 
 
 class GraphedPipelined:
-    """The training step as a software pipeline over two HIP streams.
+    """The training step as a software pipeline over two HIP streams: the one stepper of this package.
 
-    Backward is cut into stages -- heads | FPN + DLA levels 5, 4 | level 3 | level 2 .. stem by default (`stage_cut_at` of the
-    bottom-up; two stages for a backbone without cut points).  A cut at level k is only valid together with the cuts at all
-    lower levels: an uncut p_j feeds both its FPN lateral and level j+1, and would be back-propagated through twice.
+    Backward is cut into stages.  The cut points are the bottom-up's `stage_cut_at` (a cut at level k is only valid together with
+    the cuts at all lower levels: an uncut p_j feeds both its FPN lateral and level j+1, and would be back-propagated through
+    twice), the cut at the FPN features (`model.feature_cut`) and, for heads that have one, the cut at the pooled ROI features
+    (`_pool_cut`), behind which the RPN's losses wait as roots of the next stage.  A backbone without cut points leaves the
+    feature cut alone: two stages, heads | the rest.
     Stage k is recorded as TWO single-branch hipGraphs: M_k = everything on the critical path (data gradients, BatchNorm,
     ROIAlign, losses; M_0 also holds zero_grad + forward) and W_k = the stage's weight-gradient launches, which the backward
     functions queue instead of running (functional.side_mode("collect")).  Replay:
@@ -313,21 +189,24 @@ class GraphedPipelined:
         side:        W_0 (after M_0) | W_1 (after M_1) | ... | W_last
 
     so weight gradients, which nothing on the critical path waits for, fill the CUs the small data-gradient kernels of the
-    next stages leave idle.  Measured on MI355X (batch 4 x 512 x 512): 14.07 ms / step with 4 stages against 14.65 ms for the
-    single graph (6 stages 14.18, 3 stages 14.42, 2 stages 14.92: when a weight-gradient graph starts, the critical-path
-    kernels wait up to ~200 us for CU slots, which bounds the useful number of stages).  A single graph with parallel branches is
-    no alternative: ROCm 7.2 replays such a graph node by node from the host, 12 ms per step instead of 0.7 ms; neither is a
-    high-priority main stream (graph replays on it run 2x slower).
+    next stages leave idle.  Where the RPN labels its anchors from the ground truth alone, stage 0 starts with a prologue: the
+    labelling launches as a graph of their own on the side stream, beside the forward pass up to the RPN head
+    (`_capture_stage0_labels`).  When a weight-gradient graph starts, the critical-path kernels wait for CU slots, which bounds the
+    useful number of stages.  A single graph with parallel branches is no alternative: ROCm 7.2 replays such a graph node by node
+    from the host; neither is a high-priority main stream (graph replays on it run slower).
 
     Memory: M graphs share one pool, W graphs another, so a W graph's temporaries are never handed to a main-stream kernel.
     The INPUTS of the W graphs (saved activations, output gradients) live in the M pool and stay referenced for as long as
-    the graphs exist, so no later M graph can be given their memory while a W graph may still be reading it (a few GB of the
-    288 GB).  Nothing allocated by a warm-up step may be released inside a capture (observed on ROCm 7.2 / torch 2.10: the
-    captured graph then replays garbage), hence the warm-up results are dropped before the first capture begins.
-    With more than one rank the all-reduce of the heads' gradient ranges is issued behind W_0 on the side stream and overlaps
-    the rest of backward; the remaining ranges follow W_last.  graphs=False runs the same stages eagerly (weight gradients
-    inline), which is what the CPU / gloo tests exercise.
-    `__call__` -> (loss dict, total, pending all-reduce handles)."""
+    the graphs exist, so no later M graph can be given their memory while a W graph may still be reading it.  Nothing allocated
+    by a warm-up step may be released inside a capture (observed on ROCm 7.2 / torch 2.10: the captured graph then replays
+    garbage), hence the warm-up results are dropped before the first capture begins.  The warm-up steps exchange nothing
+    (`_exchange_muted`): ranks decide on their own when to capture, so a warm-up all-reduce would pair with another rank's real one.
+    With more than one rank the all-reduce of stage k's gradient ranges is issued behind W_k on the side stream and overlaps
+    the stages below; when the gradient bucket is not laid out for these cut points (`_per_stage_exchange`) the heads' ranges
+    go out behind W_0 and the rest after the last stage -- the same sequence of calls either way.
+    graphs=False runs the same stages with eager launches (`eager_step`; weight gradients wherever functional.side_mode() puts
+    them): what a refused capture falls back to, and what the CPU / gloo tests exercise.
+    `__call__` and `eager_step` -> (loss dict, total, pending all-reduce handles)."""
 
     _warm_stream = None
 
@@ -585,14 +464,19 @@ class GraphedPipelined:
         self._eager_exchanged_all = per_stage
         return losses, total, pending
 
+    def eager_step(self):
+        """This step with eager launches, whether or not graphs were captured: the cut points are installed for its duration only
+        (replays need none, and iterations in between run uncut).  -> (loss dict, total, pending all-reduce handles)"""
+        self._install()
+        try:
+            losses, total, pending = self._eager()
+        finally:
+            self.uninstall()
+        return losses, total, pending + self._late(self._eager_exchanged_all)
+
     def __call__(self):
         if self.stages is None:
-            self._install()
-            try:
-                losses, total, pending = self._eager()
-            finally:
-                self.uninstall()
-            return losses, total, pending + self._late(self._eager_exchanged_all)
+            return self.eager_step()
         main, side = torch.cuda.current_stream(), self.side
         pending, n = [], len(self.stages)
         self._replay_per_stage = self._per_stage_exchange(n)

@@ -51,7 +51,7 @@ def _install_emulator():
 
 
 def _make_cut_net():
-    """backbone (conv+bn) | heads (flatten-linear + linear) with the FeatureCut between them, like RCNN3D.forward"""
+    """backbone (conv+bn) | heads (flatten-linear + linear) with the feature cut between them, like RCNN3D.forward"""
     from omni3d_amd.cubercnn.modeling.layers import BatchNorm2d, Conv2d, FlattenLinear, Linear
 
     class Net(torch.nn.Module):
@@ -78,17 +78,17 @@ def _tag_early(net):
         p._omni_early_grad = not n.startswith("backbone.")
 
 
-def _worker_two_phase(rank, world, port, out, pipelined=False):
+def _worker_staged_eager(rank, world, port, out):
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     _install_emulator()
     from omni3d_amd.cubercnn.solver.build import FlatSGD
-    from omni3d_amd.cubercnn.solver.graphed import GraphedPipelined, GraphedTwoPhase
+    from omni3d_amd.cubercnn.solver.graphed import GraphedPipelined
     net = _make_cut_net()
     _tag_early(net)
     opt = FlatSGD([{"params": [p], "weight_decay": 0.0 if p.dim() == 1 else 1e-3} for p in net.parameters()], lr=0.1, momentum=0.9)
-    assert opt.early_ranges and opt.late_ranges
-    stepper = (GraphedPipelined if pipelined else GraphedTwoPhase)(net, opt, _shard(rank), None, graphs=False)
+    assert opt.stage_ranges.get(0) and any(opt.stage_ranges.get(k) for k in range(1, opt.n_stages))
+    stepper = GraphedPipelined(net, opt, _shard(rank), None, graphs=False)
     for _ in range(2):
         _, _, pending = stepper()
         opt.all_reduce_finish(pending)
@@ -113,13 +113,12 @@ def _worker_single_phase(rank, world, port, out):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("pipelined", [False, True])
-def test_two_phase_overlapped_exchange_world2(emu_lib, tmp_path, pipelined):
+def test_staged_eager_overlapped_exchange_world2(emu_lib, tmp_path):
     """backward cut at the features + all-reduce of the heads' ranges started before the backbone's backward ==
-    plain backward + one exchange (same parameters after two SGD steps, on both ranks); GraphedTwoPhase and the staged
-    GraphedPipelined in their eager form"""
+    plain backward + one exchange (same parameters after two SGD steps, on both ranks): GraphedPipelined in its eager form
+    on a backbone without cut points"""
     world = 2
-    mp.spawn(_worker_two_phase, args=(world, _free_port(), str(tmp_path), pipelined), nprocs=world, join=True)
+    mp.spawn(_worker_staged_eager, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
     mp.spawn(_worker_single_phase, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
     tp = [torch.load(os.path.join(tmp_path, f"tp{r}.pt")) for r in range(world)]
     sp = [torch.load(os.path.join(tmp_path, f"sp{r}.pt")) for r in range(world)]
@@ -192,10 +191,10 @@ def _tiny_model_and_batch(rank):
     return model, batch
 
 
-def _real_step(model, opt, batch, guard, two_phase):
-    from omni3d_amd.cubercnn.solver.graphed import GraphedTwoPhase
-    if two_phase:
-        stepper = GraphedTwoPhase(model, opt, batch, model.prepack(batch), graphs=False)
+def _real_step(model, opt, batch, guard, staged):
+    from omni3d_amd.cubercnn.solver.graphed import GraphedPipelined
+    if staged:
+        stepper = GraphedPipelined(model, opt, batch, model.prepack(batch), graphs=False)
         losses, _, pending = stepper()
         opt.all_reduce_finish(pending, defer_scale=True)
     else:
@@ -209,7 +208,7 @@ def _real_step(model, opt, batch, guard, two_phase):
     return skipped, retry, red
 
 
-def _worker_real(rank, world, port, out, two_phase):
+def _worker_real(rank, world, port, out, staged):
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     _install_emulator()
@@ -220,25 +219,25 @@ def _worker_real(rank, world, port, out, two_phase):
     guard = StepGuard(["BoxHead/loss_cls", "BoxHead/loss_box_reg", "Cube/uncert", "Cube/loss_dims", "Cube/loss_xy", "Cube/loss_z",
                        "Cube/loss_pose", "Cube/loss_joint", "rpn/cls", "rpn/loc"], 0.01, 100, "cpu")
     opt.skip_flag = guard.skip
-    skipped, retry, red = _real_step(model, opt, batch, guard, two_phase)
+    skipped, retry, red = _real_step(model, opt, batch, guard, staged)
     torch.save({"param": opt.flat_param.clone(), "red": red, "skipped": skipped,
-                "bn": model.backbone.bottom_up.level2.tree1.bn1.running_mean.clone()}, os.path.join(out, f"real{int(two_phase)}_{rank}.pt"))
+                "bn": model.backbone.bottom_up.level2.tree1.bn1.running_mean.clone()}, os.path.join(out, f"real{int(staged)}_{rank}.pt"))
     dist.destroy_process_group()
 
 
 @pytest.mark.skipif(os.environ.get("OMNI_SLOW") != "1", reason="~20 min under the host emulator (four emulated model steps); set OMNI_SLOW=1")
 def test_real_model_data_parallel_step_world2(emu_lib, tmp_path):
-    """SURVEY.md 8(e) on the REAL model: two ranks, one image each, gradients all-reduced over gloo (two-phase overlapped and
-    single-phase), divergence guard with its one collective, 1/world folded into the SGD kernel.  Replicas stay bit-identical,
+    """SURVEY.md 8(e) on the REAL model: two ranks, one image each, gradients all-reduced over gloo (the staged step's overlapped
+    exchange and the single-phase one), divergence guard with its one collective, 1/world folded into the SGD kernel.  Replicas stay bit-identical,
     both exchange forms agree, per-rank BatchNorm statistics stay per-rank, and the result equals a single process that
     averages the two shards' gradients by hand."""
     world = 2
-    for two_phase in (True, False):
-        mp.spawn(_worker_real, args=(world, _free_port(), str(tmp_path), two_phase), nprocs=world, join=True)
+    for staged in (True, False):
+        mp.spawn(_worker_real, args=(world, _free_port(), str(tmp_path), staged), nprocs=world, join=True)
     tp = [torch.load(os.path.join(tmp_path, f"real1_{r}.pt"), weights_only=False) for r in range(world)]
     sp = [torch.load(os.path.join(tmp_path, f"real0_{r}.pt"), weights_only=False) for r in range(world)]
     assert torch.equal(tp[0]["param"], tp[1]["param"]) and torch.equal(sp[0]["param"], sp[1]["param"])      # identical replicas
-    assert (tp[0]["param"] - sp[0]["param"]).abs().max() <= 1e-6                                          # two-phase == single-phase
+    assert (tp[0]["param"] - sp[0]["param"]).abs().max() <= 1e-6                                          # staged == single-phase
     assert tp[0]["red"] == tp[1]["red"] and not tp[0]["skipped"]                                          # same reduced losses everywhere
     assert not torch.equal(tp[0]["bn"], tp[1]["bn"])                                                      # BN running stats are per rank
     # single process, two replicas, hand-averaged gradients
